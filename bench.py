@@ -14,13 +14,22 @@ fixed seeds, compared on rank 0 with a single-GPU render of the same seeds (and 
 seed rows with the single render's).
 A ray = one closest-hit or one any-hit (shadow) query, counted on the device.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a `roofline` object for
-the triangle kernel (algorithmic bytes from the device traversal counters / HIP-event kernel
-time) and a `cpu_baseline` object (the CPU oracle, bit-identical restatement of the reference
-kernel, on a bounded pixel sample, rank 0 at N = 1 only).
+A plain run does what the headline figure needs and no more: it sets the scene up, warms up,
+times the K steps and prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better,
+dtype, ms_per_step = the wall milliseconds of one timed step, and the workload's description).
+The timed frames always start from the seeds of the first frame, so the same arguments render
+the same frames from run to run; `--dump-outputs DIR` writes the last timed step's frame (what
+rayTrace handed back) as DIR/frame.npy.
+
+`--full` adds every other leg to the same line, each in runs of its own outside the timed steps:
+a `roofline` object for the triangle kernel (algorithmic bytes from the device traversal counters
+of a counting launch / HIP-event kernel time, the critical-path chain), the frame after a camera
+move (`cold_frame_ms` ...), at N > 1 the gathered frame's bit-exact check, and at N = 1 a
+`cpu_baseline` object (the reference kernel on the host cores, on a bounded pixel sample, with the
+GPU frame checked against it bit for bit) and the GPU linear-traversal leg.
 """
 from __future__ import annotations
 
@@ -82,10 +91,19 @@ def parse():
                     help="BVH builder: host binned SAH (default) or the GPU LBVH build")
     ap.add_argument("--ply", default=None, help="render this PLY mesh (normalised, SURVEY §8d) instead of "
                     "the synthetic mesh of the config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-linear-leg", action="store_true", help="skip the GPU linear-traversal leg (N = 1)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-baseline sample duration")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure (roofline and critical path, camera-move "
+                         "frames, CPU baseline and bit-exact check, GPU linear leg, the N > 1 gathered-frame check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame (RGBA float32, H x W x 4; a fixed seeded sample of "
+                         "pixels when it exceeds 64 MB) to DIR/frame.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the linear leg")
+    ap.add_argument("--no-linear-leg", action="store_true", help="--full: skip the GPU linear-traversal leg (N = 1)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: target CPU-baseline sample duration")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port() -> int:
@@ -279,6 +297,8 @@ def main():
         else:
             frame_full = torch.zeros((W * H * 4) if rank == 0 else 4, dtype=torch.float32, device=f"cuda:{device}")
 
+    gathered = [None]  # rank 0: the frame the last torch.distributed gather assembled
+
     def step():
         p = frame_no[0] if progressive else 0
         if comm is not None:
@@ -294,7 +314,7 @@ def main():
         frame_no[0] += 1
         c = rt.counters()
         if n_ranks > 1:
-            ptdist.gather_frame(out, H, W, args.stripe, owner=owner)
+            gathered[0] = ptdist.gather_frame(out, H, W, args.stripe, owner=owner)
         elif frames_per_rank:
             ptdist.gather_frames(out)
         return c["rays_closest"] + c["rays_shadow"]
@@ -303,43 +323,49 @@ def main():
     # first timed frame see the same seeds
     step()
     seeds0 = rt.getSeeds()
-    # counting launch (untimed): traversal node / triangle-test counts for the roofline
-    rt.setCounting(True)
-    rt.setSeeds(Wp, Hp, seeds0)
-    rt.rayTrace(out, W, H, 0, kernel=kernel, tile=tile)
-    cnt = rt.counters()
-    rt.setCounting(False)
-    # the whole frame's query counts: at N > 1 (strong scaling) every rank's counting launch
-    # covers its own stripes, so the frame's totals are the sum over ranks (the roofline below
-    # stays rank 0's: its tile's counts against its own kernel time)
-    cnt_frame = {k: int(cnt.get(k, 0)) for k in ("rays_closest", "rays_shadow", "rays_skipped")}
-    if dist and n_ranks > 1:
-        v = torch.tensor([cnt_frame[k] for k in ("rays_closest", "rays_shadow", "rays_skipped")],
-                         dtype=torch.float64, device=f"cuda:{device}")
-        dist.all_reduce(v, op=dist.ReduceOp.SUM)
-        cnt_frame = dict(zip(("rays_closest", "rays_shadow", "rays_skipped"), (int(x) for x in v.tolist())))
-    chain = None
-    if world == 1 and kernel == pt.RayTracer.KERNEL_TRIS and not args.linear:
-        chain = critical_chain(rt, pt, W, H, Wp, Hp, seeds0, kernel)
-    # the plain (timed) kernel's frame from seeds0, kept for the bit-exact check against the
-    # reference kernel's CPU render of the same pixels (cpu_baseline)
-    rt.setSeeds(Wp, Hp, seeds0)
-    rt.rayTrace(out, W, H, 0, kernel=kernel, tile=tile)
-    frame0 = out.cpu().numpy().copy() if world == 1 else None
-    seeds_after0 = rt.getSeeds() if world == 1 else None
-    rt.setSeeds(Wp, Hp, seeds0)
+    cnt = cnt_frame = chain = frame0 = seeds_after0 = None
+    if args.full:
+        # counting launch (untimed): traversal node / triangle-test counts for the roofline
+        rt.setCounting(True)
+        rt.setSeeds(Wp, Hp, seeds0)
+        rt.rayTrace(out, W, H, 0, kernel=kernel, tile=tile)
+        cnt = rt.counters()
+        rt.setCounting(False)
+        # the whole frame's query counts: at N > 1 (strong scaling) every rank's counting launch
+        # covers its own stripes, so the frame's totals are the sum over ranks (the roofline below
+        # stays rank 0's: its tile's counts against its own kernel time)
+        cnt_frame = {k: int(cnt.get(k, 0)) for k in ("rays_closest", "rays_shadow", "rays_skipped")}
+        if dist and n_ranks > 1:
+            v = torch.tensor([cnt_frame[k] for k in ("rays_closest", "rays_shadow", "rays_skipped")],
+                             dtype=torch.float64, device=f"cuda:{device}")
+            dist.all_reduce(v, op=dist.ReduceOp.SUM)
+            cnt_frame = dict(zip(("rays_closest", "rays_shadow", "rays_skipped"), (int(x) for x in v.tolist())))
+        if world == 1 and kernel == pt.RayTracer.KERNEL_TRIS and not args.linear:
+            chain = critical_chain(rt, pt, W, H, Wp, Hp, seeds0, kernel)
+        # the plain (timed) kernel's frame from seeds0, kept for the bit-exact check against the
+        # reference kernel's CPU render of the same pixels (cpu_baseline)
+        rt.setSeeds(Wp, Hp, seeds0)
+        rt.rayTrace(out, W, H, 0, kernel=kernel, tile=tile)
+        frame0 = out.cpu().numpy().copy() if world == 1 else None
+        seeds_after0 = rt.getSeeds() if world == 1 else None
+        rt.setSeeds(Wp, Hp, seeds0)
 
     # W warmup steps, then more (untimed) until the launch time has settled: the first
     # process on a freshly taken box has been seen running 4-17x slower for its first
-    # seconds. At most 30 s / 40 extra steps; the count is reported (extra_warmup_steps).
+    # seconds. At most 30 s (10 s in a plain run) / 40 extra steps; the count is reported
+    # (extra_warmup_steps). Several ranks dumping their frame take none: there the seeds
+    # carry on from step to step, and the frame written must not depend on the count.
     warm_ms = []
     for _ in range(args.warmup):
         step()
         warm_ms.append(rt.lastKernelMs())
     extra_warm = 0
+    settle_s = 30.0 if args.full else 10.0
+    if world > 1 and args.dump_outputs:
+        settle_s = 0.0
     t_w = time.perf_counter()
     while True:
-        want = (args.warmup > 0 and extra_warm < 40 and time.perf_counter() - t_w < 30.0
+        want = (args.warmup > 0 and extra_warm < 40 and time.perf_counter() - t_w < settle_s
                 and (len(warm_ms) < 2 or abs(warm_ms[-1] - warm_ms[-2]) > 0.03 * min(warm_ms[-1], warm_ms[-2])))
         if dist:  # one decision for all ranks: step() holds collectives
             w = torch.tensor([1 if want else 0], dtype=torch.int64, device=f"cuda:{device}")
@@ -361,7 +387,13 @@ def main():
     pipelined = world == 1 and halo is None and comm is None and not frames_per_rank
     rays_warm = None  # the last warm frame's count (same view), reported beside the measured mean
     if pipelined:
-        rays_warm = step()
+        if args.full:
+            rays_warm = step()
+        # the timed frames start from the first frame's seeds (and progression 0) however many
+        # warm-up steps ran, so the same arguments time and dump the same frames in every run
+        rt.setSeeds(Wp, Hp, seeds0)
+        frame_no[0] = 0
+        out.zero_()
         rt.counterTotals(reset=True)  # the timed frames' own counts accumulate on the device from here
     if dist:
         dist.barrier()
@@ -391,6 +423,12 @@ def main():
             raise RuntimeError(f"counter totals cover {tot['renders']} renders, {args.steps} were timed")
         rays = tot["rays_closest"] + tot["rays_shadow"]
         counted = {"rays_skipped": tot["rays_skipped"], "renders": tot["renders"]}
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: the frame (one GPU, or rank 0's own frame of a weak
+        # scaling step), or the frame gathered from every rank's stripes
+        last = out if n_ranks == 1 else (frame_full if comm is not None else gathered[0])
+        dump_outputs(args.dump_outputs, last.detach().cpu().numpy(), W, H)
+    if pipelined and args.full:
         for _ in range(min(args.steps, 5)):  # untimed: each frame's kernel time (HIP events)
             step()
             kernel_ms.append(rt.lastKernelMs())
@@ -408,10 +446,10 @@ def main():
     # key or drag, GlutCLWindow.cpp:229-279): wall clock including the host work of the new
     # schedule (cost probe, LPT order, pixel classes), against the next frame with the camera
     # unchanged
-    cold = interactive_cost(rt, step, cam_setup, azimuth, device, dist)
+    cold = interactive_cost(rt, step, cam_setup, azimuth, device, dist) if args.full else {}
 
     sharded = None
-    if n_ranks > 1:
+    if n_ranks > 1 and args.full:
         sharded = verify_sharded(rt, pt, sc, ptdist, comm, dist, W, H, Wp, Hp, kernel, args.stripe, n_ranks, rank,
                                  device, out, frame_full if comm is not None else None, owner)
 
@@ -425,18 +463,20 @@ def main():
     steps = args.steps
     mrays = rays / elapsed / 1e6
     ms_step = elapsed / steps * 1e3
-    frame_ms = float(np.mean(kernel_ms))  # all of a frame's kernels (rank 0), HIP events
-    # the dominant kernel's launches alone: the frame less the camera-ray candidate-list pre-pass
-    pre_ms = float(np.mean([p for p, _ in split_ms]))
-    k_ms = float(np.mean([m for _, m in split_ms]))
-    rays_cnt = cnt["rays_closest"] + cnt["rays_shadow"]
     workload = workload_name(cfg, n_tris, W, H, sr, args.traversal, args.builder)
-    pix = W * (len(ptdist.tile_rows(H, args.stripe, n_ranks, 0, owner)) if n_ranks > 1 else H)
-    roofline = roofline_block(pt, kernel, cnt, args.traversal, pix, k_ms, workload, n_ranks, chain, rays_cnt,
-                              frame_ms, pre_ms)
+    roofline = None
+    if args.full:
+        frame_ms = float(np.mean(kernel_ms))  # all of a frame's kernels (rank 0), HIP events
+        # the dominant kernel's launches alone: the frame less the camera-ray candidate-list pre-pass
+        pre_ms = float(np.mean([p for p, _ in split_ms]))
+        k_ms = float(np.mean([m for _, m in split_ms]))
+        rays_cnt = cnt["rays_closest"] + cnt["rays_shadow"]
+        pix = W * (len(ptdist.tile_rows(H, args.stripe, n_ranks, 0, owner)) if n_ranks > 1 else H)
+        roofline = roofline_block(pt, kernel, cnt, args.traversal, pix, k_ms, workload, n_ranks, chain, rays_cnt,
+                                  frame_ms, pre_ms)
 
     cpu = gpu_linear = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         print("cpu baseline", file=sys.stderr, flush=True)
         cpu = cpu_baseline(pt, sc, W, H, sr, S, seeds0, Wp, Hp, kernel, args.cpu_seconds,
                            verts if n_tris else None, idx if n_tris else None, frame0, seeds_after0)
@@ -450,10 +490,18 @@ def main():
             else:
                 gpu_linear = {"skipped": f"~{est_s:.0f} s estimated for {W}x{H} x {n_tris} triangles per query"}
 
-    frame_rays = cnt_frame["rays_closest"] + cnt_frame["rays_shadow"]
-    traversed_share = (frame_rays - cnt_frame["rays_skipped"]) / max(frame_rays, 1)
-    if counted is not None:  # the timed frames' own share (one GPU, pipelined frames)
+    # the share of the queries that ran a traversal: the timed frames' own (one GPU, pipelined
+    # frames), else the counting launch's (--full); a plain run at N > 1 has neither
+    traversed_share = rays_traversed = None
+    if cnt_frame is not None:
+        frame_rays = cnt_frame["rays_closest"] + cnt_frame["rays_shadow"]
+        traversed_share = (frame_rays - cnt_frame["rays_skipped"]) / max(frame_rays, 1)
+        rays_traversed = int(frame_rays - cnt_frame["rays_skipped"])
+    if counted is not None:
         traversed_share = (rays - counted["rays_skipped"]) / max(rays, 1)
+        if rays_traversed is None:
+            rays_traversed = int((rays - counted["rays_skipped"]) / steps)
+    mrays_traversed = round(mrays * traversed_share, 2) if traversed_share is not None else None
     line = {
         "metric": (METRIC_WEAK if frames_per_rank else METRIC) if cfg == "dragon" else CONFIG_METRIC.get(
             cfg, f"Mrays/sec + frames/sec, {cfg}"),
@@ -469,8 +517,8 @@ def main():
         "frames_per_sec": round(steps * (world if frames_per_rank else 1) / elapsed, 4),
         # the same frames counting only the queries that ran a traversal (rank 0's counting
         # launch share; DESIGN.md §5: shadow rays answered without one are still rays)
-        "mrays_traversed_per_sec": round(mrays * traversed_share, 2),
-        "value_traversed": round(mrays * traversed_share, 2),
+        "mrays_traversed_per_sec": mrays_traversed,
+        "value_traversed": mrays_traversed,
         "value_rule": ("value counts the reference's queries (closest-hit + shadow, equal to the oracle's counts) "
                        "of the timed frames themselves, summed on the device (rt_counter_totals); "
                        "value_traversed leaves out the shadow rays answered without a traversal (tmax <= tmin, or "
@@ -495,12 +543,15 @@ def main():
                    "rays_warm_frame": int(rays_warm) if rays_warm is not None else None,
                    # rays = the reference's queries (oracle-equal counts); shadow rays whose answer
                    # cannot change the pixel are answered without a traversal
-                   "rays_traversed_per_frame": int(cnt_frame["rays_closest"] + cnt_frame["rays_shadow"]
-                                                   - cnt_frame["rays_skipped"]),
+                   "rays_traversed_per_frame": rays_traversed,
                    "mesh": mesh_info},
-        "roofline": roofline,
-        "cpu_baseline": cpu,
+        "full": bool(args.full),
     }
+    if args.full:
+        line["roofline"] = roofline
+        line["cpu_baseline"] = cpu
+    if args.dump_outputs:
+        line["outputs"] = str(Path(args.dump_outputs) / "frame.npy")
     if kernel == pt.RayTracer.KERNEL_TRIS and info:
         line["config"]["candidate_lists"] = {"on": bool(info["lists"]), "capacity_records": int(info["list_capacity"]),
                                              "records": int(info["list_records"]),
@@ -525,6 +576,25 @@ def main():
         comm.close()
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(directory, frame, W, H):
+    """--dump-outputs: the last timed step's frame as DIR/frame.npy, float32 [H, W, 4] (RGBA).  A frame
+    over 64 MB is written as a fixed sample of whole pixels instead: frame.npy [n, 4] and their
+    indices y * W + x in frame_pixels.npy (float64), drawn once from a generator seeded with 0."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    px = np.ascontiguousarray(frame, dtype=np.float32).reshape(H * W, 4)
+    if px.nbytes + 4096 <= DUMP_LIMIT_BYTES:
+        np.save(d / "frame.npy", px.reshape(H, W, 4))
+        return
+    n = (DUMP_LIMIT_BYTES - 4096) // (16 + 8)  # 16 B of RGBA + 8 B of index per pixel, room for the two headers
+    pick = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+    np.save(d / "frame.npy", px[pick])
+    np.save(d / "frame_pixels.npy", pick.astype(np.float64))
 
 
 def interactive_cost(rt, step, cam_setup, azimuth, device, dist):

@@ -11,7 +11,7 @@ mkdir -p $OUT/prof
 export TMPDIR=/tmp
 export RT_DET_CULL=0 RT_CULL_UNHITTABLE=0
 ARGS="--config lucy --steps 3 --warmup 1 --no-cpu-baseline"
-timeout -k 10 600 python3 -u bench.py $ARGS > $OUT/bench_lucy_cullsoff.json 2> $OUT/bench_lucy_cullsoff.err
+timeout -k 10 600 python3 -u bench.py --full $ARGS > $OUT/bench_lucy_cullsoff.json 2> $OUT/bench_lucy_cullsoff.err
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof/trace -o run -- \
     python3 bench.py $ARGS > $OUT/prof/trace.log 2>&1
 for P in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "GRBM_GUI_ACTIVE GRBM_COUNT"; do

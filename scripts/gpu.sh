@@ -8,7 +8,7 @@
 # further GPU work starts after trouble.  Steps:
 #   tests[=<pytest -k expr>]   GPU parity tests (pytest -m gpu)            -> pytest.log
 #   smoke                      __graft_entry__.smoke()                       -> smoke.log
-#   bench[=<args>]             python bench.py <args> (',' separates args)   -> bench[_<n>].json / .err
+#   bench[=<args>]             python bench.py <args> (',' separates args; --full: every leg) -> bench[_<n>].json / .err
 #   profile[=<args>]           rocprofv3 kernel trace + stats of bench.py    -> prof_<tag>/ (profiles/run_profile.sh)
 #   pmc[=<args>]               separate rocprofv3 --pmc passes of bench.py   -> prof_<tag>/ (profiles/pmc_extra.sh)
 #   tiles[=<args>]             profiles/tile_scaling.py <args>               -> tiles[_<n>].json / .log

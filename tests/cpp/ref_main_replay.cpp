@@ -12,11 +12,21 @@
  * `frames` renders at progression 0, 1, ... and the last frame is written raw
  * (W*H*4 float32).
  *
- *   ref_main_replay main|ply W H FRAMES OUT.f32 [matrix]
+ *   ref_main_replay main|ply W H FRAMES OUT.f32 [matrix [VIEW.f32]]
+ *   ref_main_replay viewmatrix main|ply VIEW.f32
  *
  * `matrix` sets the same camera through setCameraMatrix(gmtl::Matrix44f) built by
  * gmtl from the spherical parameters (RayTracer.cpp:33-47's formula) instead of
- * setCameraSpherical, exercising the matrix overload.
+ * setCameraSpherical, exercising the matrix overload.  `viewmatrix` writes that
+ * matrix (16 float32, column-major) and renders nothing: tests/golden/view_main.f32
+ * is its record.
+ *
+ * Where the reference's headers are absent (a checkout on its own), the same call
+ * sequence is compiled against the header's own overloads instead: Sphere,
+ * material_t and vec3 name the byte-compatible rt_sphere, rt_material and rt_vec3,
+ * the target is a float[3], and `matrix` reads the recorded gmtl matrix from
+ * VIEW.f32 and hands it to setCameraMatrix(const float[16]).  REPLAY_WITH_REFERENCE_TYPES
+ * tells the two builds apart; only the first proves source compatibility.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -26,9 +36,8 @@
 
 #include "RayTracerHIP.hpp"
 
-#if !defined(RT_HIP_HAVE_REF_GEOMETRY) || !defined(RT_HIP_HAVE_GMTL)
-#error "build with the reference's geometry.h and gmtl on the include path"
-#endif
+#if defined(RT_HIP_HAVE_REF_GEOMETRY) && defined(RT_HIP_HAVE_GMTL)
+#define REPLAY_WITH_REFERENCE_TYPES 1
 
 #include <cmath>
 
@@ -38,6 +47,13 @@
 #include <gmtl/Vec.h>
 #include <gmtl/VecOps.h>
 #include <gmtl/Xforms.h>
+#elif defined(REPLAY_REQUIRE_REFERENCE_TYPES)
+#error "build with the reference's geometry.h and gmtl on the include path"
+#else
+typedef rt_sphere Sphere;
+typedef rt_material material_t;
+typedef rt_vec3 vec3;
+#endif
 
 /* main.cpp:13-42: every material/sphere field starts from these values. */
 static void reset_material(material_t *m)
@@ -131,6 +147,23 @@ static void add_scene(RayTracerHIP &rt, bool ply)
     rt.addSphere(s);
 }
 
+static bool read_floats(const char *path, float *v, size_t n)
+{
+    FILE *f = std::fopen(path, "rb");
+    const bool ok = f && std::fread(v, sizeof(float), n, f) == n;
+    if (f) std::fclose(f);
+    return ok;
+}
+
+static bool write_floats(const char *path, const float *v, size_t n)
+{
+    FILE *f = std::fopen(path, "wb");
+    const bool ok = f && std::fwrite(v, sizeof(float), n, f) == n;
+    if (f) std::fclose(f);
+    return ok;
+}
+
+#ifdef REPLAY_WITH_REFERENCE_TYPES
 /* RayTracer::setCameraSpherical's view matrix (RayTracer.cpp:33-47), built with the
    same gmtl calls, handed over through setCameraMatrix(gmtl::Matrix44f). */
 static gmtl::Matrix44f spherical_matrix(gmtl::Point3f const &target, float el, float az, float dist)
@@ -145,36 +178,66 @@ static gmtl::Matrix44f spherical_matrix(gmtl::Point3f const &target, float el, f
     gmtl::setTrans(m, position + target);
     return m;
 }
+#endif
 
 int main(int argc, char **argv)
 {
+    if (argc == 4 && std::strcmp(argv[1], "viewmatrix") == 0) {
+#ifdef REPLAY_WITH_REFERENCE_TYPES
+        const bool ply = std::strcmp(argv[2], "ply") == 0;
+        const gmtl::Matrix44f m =
+            spherical_matrix(gmtl::Point3f(0, -4, -0), ply ? 40.0f : 14.0f, ply ? 105.0f : 118.0f, 5);
+        if (!write_floats(argv[3], m.getData(), 16)) {
+            std::fprintf(stderr, "cannot write %s\n", argv[3]);
+            return 1;
+        }
+        return 0;
+#else
+        std::fprintf(stderr, "viewmatrix: built without the reference's headers (no gmtl)\n");
+        return 2;
+#endif
+    }
     if (argc < 6) {
-        std::fprintf(stderr, "usage: %s main|ply W H FRAMES OUT.f32 [matrix]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s main|ply W H FRAMES OUT.f32 [matrix [VIEW.f32]]\n"
+                             "       %s viewmatrix main|ply VIEW.f32\n", argv[0], argv[0]);
         return 2;
     }
     const bool ply = std::strcmp(argv[1], "ply") == 0;
     const unsigned W = (unsigned)std::atoi(argv[2]), H = (unsigned)std::atoi(argv[3]);
     const unsigned frames = (unsigned)std::atoi(argv[4]);
     const bool use_matrix = argc > 6 && std::strcmp(argv[6], "matrix") == 0;
+#ifndef REPLAY_WITH_REFERENCE_TYPES
+    float view[16];
+    if (use_matrix && (argc < 8 || !read_floats(argv[7], view, 16))) {
+        std::fprintf(stderr, "matrix: built without gmtl, needs the recorded matrix (VIEW.f32, 16 float32)\n");
+        return 2;
+    }
+#endif
     try {
         RayTracerHIP rayTracer; /* GlutCLWindow's `RayTracerCL rayTracer` member */
         add_scene(rayTracer, ply);
         rayTracer.setSampleRate(1);
         rayTracer.setMaxPathDepth(6);
-        const gmtl::Point3f target(0, -4, -0);
         const float el = ply ? 40.0f : 14.0f, az = ply ? 105.0f : 118.0f;
+#ifdef REPLAY_WITH_REFERENCE_TYPES
+        const gmtl::Point3f target(0, -4, -0);
         if (use_matrix)
             rayTracer.setCameraMatrix(spherical_matrix(target, el, az, 5));
         else
             rayTracer.setCameraSpherical(target, el, az, 5);
+#else
+        const float target[3] = {0, -4, -0};
+        if (use_matrix)
+            rayTracer.setCameraMatrix(view);
+        else
+            rayTracer.setCameraSpherical(target, el, az, 5);
+#endif
         std::vector<float> frame((size_t)W * H * 4);
         for (unsigned p = 0; p < frames; ++p) rayTracer.rayTrace(frame.data(), W, H, p);
-        FILE *f = std::fopen(argv[5], "wb");
-        if (!f || std::fwrite(frame.data(), sizeof(float), frame.size(), f) != frame.size()) {
+        if (!write_floats(argv[5], frame.data(), frame.size())) {
             std::fprintf(stderr, "cannot write %s\n", argv[5]);
             return 1;
         }
-        std::fclose(f);
     } catch (std::exception const &e) {
         std::fprintf(stderr, "ref_main_replay: %s\n", e.what());
         return 3;

@@ -62,6 +62,34 @@ def test_roofline_is_the_8d_byte_fraction_and_pmc_fractions_use_the_profiled_tim
     assert set(r2["fractions"]) == {"record_gather"} and r2["traffic"] is None
 
 
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs: a frame up to 64 MB is written whole as float32 [H, W, 4]; a larger one as the
+    same seeded sample of whole pixels in every run, with their indices, 64 MB at most in all."""
+    import numpy as np
+
+    b = _bench()
+    W, H = 7, 5
+    frame = np.arange(W * H * 4, dtype=np.float32)
+    b.dump_outputs(tmp_path / "small", frame, W, H)
+    got = np.load(tmp_path / "small" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (H, W, 4) and np.array_equal(got.reshape(-1), frame)
+    assert [p.name for p in (tmp_path / "small").iterdir()] == ["frame.npy"]
+
+    W = H = 2048  # 67.1 MB of RGBA float32: over the limit
+    frame = np.arange(W * H * 4, dtype=np.float32)
+    for d in ("a", "b"):
+        b.dump_outputs(tmp_path / d, frame, W, H)
+    pick = np.load(tmp_path / "a" / "frame_pixels.npy")
+    px = np.load(tmp_path / "a" / "frame.npy")
+    assert px.dtype == np.float32 and pick.dtype == np.float64 and px.shape == (len(pick), 4)
+    idx = pick.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < W * H
+    assert np.array_equal(px, frame.reshape(-1, 4)[idx])
+    assert np.array_equal(pick, np.load(tmp_path / "b" / "frame_pixels.npy"))
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert 0.9 * 64e6 < total <= 64e6
+
+
 def test_gpus_without_a_launcher_refuses_more_ranks_than_devices(monkeypatch):
     """bench.py --gpus N (no WORLD_SIZE): N ranks are started by bench.py itself; on a node with fewer
     GPUs than N (RCCL, one rank per GPU) it exits non-zero with a message instead of measuring one."""

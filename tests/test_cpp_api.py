@@ -5,10 +5,12 @@ sequence written against the reference's own types (`Sphere` from clrt/ocl/geome
 `gmtl::Point3f`, `gmtl::Matrix44f`), compiled against include/RayTracerHIP.hpp with the
 reference headers read in place.  CPU: it compiles and fails loudly without a GPU.
 GPU: its frames equal the reference kernel's golden frames and the oracle, bit for bit,
-through both camera overloads.
+through both camera overloads.  A checkout without the reference builds the same calls
+against the header's own types and takes gmtl's camera matrix from tests/golden/view_main.f32.
 """
 from __future__ import annotations
 
+import os
 import subprocess
 from pathlib import Path
 
@@ -19,12 +21,19 @@ from conftest import ROOT, bits
 
 REF = Path("/root/reference")
 BIN = ROOT / "tests" / "cpp" / "ref_main_replay"
+# main.cpp's camera as gmtl builds it (16 float32, column-major), written by `ref_main_replay viewmatrix`
+VIEW_MAIN = ROOT / "tests" / "golden" / "view_main.f32"
 
 
-@pytest.mark.skipif(not (REF / "clrt" / "ocl" / "geometry.h").exists(), reason="reference headers absent")
+@pytest.mark.skipif(not os.access(REF / "clrt" / "ocl" / "geometry.h", os.R_OK), reason="reference headers absent")
 def test_reference_caller_compiles_and_fails_loudly_without_gpu(pt, tmp_path):
     subprocess.run(["make", "-s", "-B", "-C", str(ROOT / "tests" / "cpp")], check=True, timeout=300)
     assert BIN.exists()
+    # the build with the reference's types (only it has gmtl): its setCameraSpherical matrix is
+    # the recorded one that a build without the reference hands to setCameraMatrix
+    subprocess.run([str(BIN), "viewmatrix", "main", str(tmp_path / "view.f32")], check=True, timeout=120)
+    np.testing.assert_array_equal(bits(np.fromfile(tmp_path / "view.f32", np.float32)),
+                                  bits(np.fromfile(VIEW_MAIN, np.float32)))
     from conftest import gpu_available
 
     if gpu_available():
@@ -36,9 +45,12 @@ def test_reference_caller_compiles_and_fails_loudly_without_gpu(pt, tmp_path):
 
 def _replay(tmp_path, *args):
     if not BIN.exists():
-        pytest.fail("tests/cpp/ref_main_replay was not built (build() builds it where the reference is)")
+        pytest.fail("tests/cpp/ref_main_replay was not built (build() builds it)")
     raw = tmp_path / "out.f32"
-    subprocess.run([str(BIN), args[0], *map(str, args[1:4]), str(raw), *args[4:]], check=True, timeout=120)
+    cmd = [str(BIN), args[0], *map(str, args[1:4]), str(raw), *args[4:]]
+    if "matrix" in args[4:]:
+        cmd.append(str(VIEW_MAIN))  # read by a build without gmtl, which cannot make the matrix itself
+    subprocess.run(cmd, check=True, timeout=120)
     return np.fromfile(raw, np.float32)
 
 
