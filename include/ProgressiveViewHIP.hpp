@@ -25,6 +25,15 @@
  * 40, distance 5, :24-28), independent of the camera the application set — as in the
  * reference.  A GLUT (or any toolkit) window forwards its callbacks here and draws
  * pixels() (RGBA32F, W*H*4, bottom row first as glDrawPixels expects: the tracer's row 0).
+ *
+ *   setDenoise(on, params)   (no counterpart in the reference) display the edge-avoiding a-trous
+ *                    filter of the frame instead of the raw Monte-Carlo frame: every traced
+ *                    display still renders into the accumulation buffer, which the filter only
+ *                    reads — the progressive result stays the reference's bit for bit — then
+ *                    filters it on the GPU into a second device buffer, guided by the first-hit
+ *                    features (rendered only after a reallocation or a camera change), and reads
+ *                    that one back into pixels().  rawPixels() fetches the undenoised frame on
+ *                    request.  Off (the default), every call does exactly what it did before.
  */
 #ifndef PROGRESSIVE_VIEW_HIP_HPP
 #define PROGRESSIVE_VIEW_HIP_HPP
@@ -103,7 +112,24 @@ public:
         return post;
     }
 
+    void setDenoise(bool on, const rt_denoise_params &params = RayTracerHIP::denoiseDefaults())
+    {
+        if (on && !denoise_) featDirty_ = true;
+        denoise_ = on;
+        denoiseParams_ = params;
+    }
+    bool denoising() const { return denoise_; }
+
     const std::vector<float> &pixels() const { return pbo_; }
+    /* The accumulation buffer as rendered (what pixels() holds with the denoiser off), read back now. */
+    const std::vector<float> &rawPixels()
+    {
+        if (!denoise_) return pbo_;
+        raw_.assign(pbo_.size(), 0.0f);
+        if (dev_ && hipMemcpy(raw_.data(), dev_, raw_.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("ProgressiveViewHIP: raw frame readback failed");
+        return raw_;
+    }
     unsigned progression() const { return progression_; }
     unsigned maxProgression() const { return maxProgression_; }
     bool rendered() const { return rendered_; }
@@ -118,6 +144,7 @@ private:
     {
         const float target[3] = {0.0f, -4.0f, 0.0f};
         rt_.setCameraSpherical(target, elevation_, azimuth_, distance_);
+        featDirty_ = true;
     }
     void allocate()
     {
@@ -125,24 +152,46 @@ private:
         if (hipMalloc(&dev_, (size_t)width_ * height_ * 4 * sizeof(float)) != hipSuccess)
             throw std::runtime_error("ProgressiveViewHIP: framebuffer allocation failed");
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
+        featDirty_ = true;
     }
     void release()
     {
         if (dev_) (void)hipFree(dev_);
-        dev_ = nullptr;
+        if (den_) (void)hipFree(den_);
+        if (feat_) (void)hipFree(feat_);
+        dev_ = den_ = feat_ = nullptr;
     }
     void trace()
     {
         rt_.rayTrace(dev_, width_, height_, progression_, kernel_, true);
-        rt_.read(pbo_.data(), pbo_.size()); /* the non-sharing readback into the PBO */
+        if (denoise_) {
+            const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
+            if (!den_ && hipMalloc(&den_, frame) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: denoised framebuffer allocation failed");
+            if (!feat_ && hipMalloc(&feat_, 2 * frame) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: feature buffer allocation failed");
+            if (featDirty_) {
+                rt_.renderFeatures(feat_, width_, height_, kernel_, true);
+                featDirty_ = false;
+            }
+            rt_.denoise(dev_, feat_, den_, width_, height_, denoiseParams_, true);
+            if (hipMemcpy(pbo_.data(), den_, frame, hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: denoised frame readback failed");
+        } else {
+            rt_.read(pbo_.data(), pbo_.size()); /* the non-sharing readback into the PBO */
+        }
         rendered_ = true;
     }
 
     RayTracerHIP &rt_;
     unsigned width_, height_;
     int kernel_;
-    float *dev_ = nullptr;
-    std::vector<float> pbo_;
+    float *dev_ = nullptr;  /* the accumulation buffer the tracer renders into */
+    float *den_ = nullptr;  /* setDenoise: the filtered frame */
+    float *feat_ = nullptr; /* setDenoise: the view's first-hit features */
+    bool denoise_ = false, featDirty_ = true;
+    rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
+    std::vector<float> pbo_, raw_;
     bool realloc_ = true, rendered_ = false;
     unsigned progression_ = 0, maxProgression_ = 10000;
     float azimuth_ = 105.0f, elevation_ = 40.0f, distance_ = 5.0f;

@@ -202,6 +202,38 @@ public:
        path, GlutCLWindow.cpp:214-225); n_floats = capacity of `host`. */
     void read(float *host, size_t n_floats) { check(rt_read(ctx_, host, n_floats), "read"); }
 
+    /* ---- first-hit features and the display denoiser (pathtracer_rt.h; nothing in the
+       reference corresponds to them).  None of them changes a render's state. ---- */
+    /* The pixel-centre camera rays of a W x H frame under the current camera, row-major. */
+    std::vector<rt_ray> primaryRays(unsigned width, unsigned height) const
+    {
+        rt_camera cam;
+        check(rt_get_camera(ctx_, width, &cam), "primaryRays: camera");
+        std::vector<rt_ray> rays((size_t)width * height);
+        check(rt_primary_rays(&cam, width, height, rays.data()), "primaryRays");
+        return rays;
+    }
+    /* feat: 2 planes of W*H float4, (P, t) then (N, surface id bits); device or host memory. */
+    void renderFeatures(float *feat, unsigned width, unsigned height, int kernel = RT_KERNEL_SPHERES,
+                        bool on_device = false)
+    {
+        flushScene();
+        check(rt_render_features(ctx_, feat, width, height, kernel, on_device ? RT_OUT_DEVICE : 0), "renderFeatures");
+    }
+    static rt_denoise_params denoiseDefaults()
+    {
+        rt_denoise_params p;
+        rt_denoise_defaults(&p);
+        return p;
+    }
+    /* Edge-avoiding a-trous filter of `in` guided by `feat` into `out` (may be `in`); all three
+       device pointers when on_device, else host memory. */
+    void denoise(const float *in, const float *feat, float *out, unsigned width, unsigned height,
+                 const rt_denoise_params &params = denoiseDefaults(), bool on_device = false)
+    {
+        check(rt_denoise(ctx_, in, feat, out, width, height, &params, on_device ? RT_OUT_DEVICE : 0), "denoise");
+    }
+
     rt_counters counters() const
     {
         rt_counters c;

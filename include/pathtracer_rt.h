@@ -267,6 +267,58 @@ int rt_last_long_chains(rt_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n);
    any_hit=1: out_idx = 1 if occluded in (tmin, tmax). ---- */
 int rt_trace_rays(rt_ctx *ctx, const rt_ray *rays, uint32_t n, int any_hit, int32_t *out_idx, float *out_t);
 
+/* ---- first-hit feature buffers and the display denoiser.  Nothing in the reference corresponds
+   to them (raytracer.cl:220 leaves a TODO at the camera ray); their arithmetic is pinned in
+   DESIGN.md §4.9 under the model of rt_math.h, so both are reproducible to the bit.  They
+   serve the DISPLAYED image only: no call here changes any render state (seeds, schedule / list /
+   pilot caches, counters, rt_last_kernel_ms, rt_last_render_info, rt_read's framebuffer), and the
+   accumulation buffer a progressive render mixes into is never written.  `flags` takes
+   RT_OUT_DEVICE only: with it every buffer of the call is a device pointer on the context's GPU,
+   without it every buffer is host memory and the library stages them.  On any stream the calls
+   order themselves after the context's pending render, and the next render after them.
+   The features cover the whole frame — there is no rt_tile: in a multi-GPU run the root computes
+   them itself for the gathered frame. ---- */
+/* surface ids in a feature buffer: >= 0 triangle index (the caller's numbering, as rt_trace_rays) */
+enum { RT_FEAT_BOX = -1, RT_FEAT_NONE = -2, RT_FEAT_SPHERE0 = -16 /* sphere s: RT_FEAT_SPHERE0 - s */ };
+/* The Camera rt_render would use for a frame of this width: the explicit override, or the one
+   derived from the view matrix and the field of view (RayTracerCL::updateCLCamera). */
+int rt_get_camera(const rt_ctx *ctx, uint32_t width, rt_camera *out);
+/* host only: the pixel-centre camera rays of a W x H frame, row-major y*W+x: raytracer.cl:221-224
+   with the stratified draw replaced by 0.5; o = position, tmin = 1e-4f, tmax = INFINITY,
+   propagation 1, extinction 0, diffuse flag 0. */
+int rt_primary_rays(const rt_camera *cam, uint32_t width, uint32_t height, rt_ray *out);
+/* The first hit of every pixel-centre ray under the context's current camera (derived for
+   `width`), as the kernel's first path segment finds it: RT_KERNEL_TRIS the mesh (closest hit,
+   ties to the highest index; N = normalize(cross(e2, e1)), never flipped) then the box;
+   RT_KERNEL_SPHERES / _SS the spheres (strict interval, lowest index on ties) then the box.
+   feat: 2 planes of W*H float4; plane 0 = (Px,Py,Pz,t), plane 1 = (Nx,Ny,Nz, id as int32 bits);
+   a pixel that meets nothing: id RT_FEAT_NONE, P = N = 0, t = INFINITY.  The same bits under
+   every rt_set_traversal mode and both builders.  RT_ERR_NO_SCENE / RT_ERR_NO_MESH as rt_render. */
+int rt_render_features(rt_ctx *ctx, float *feat, uint32_t width, uint32_t height, int kernel, int flags);
+int rt_render_features_async(rt_ctx *ctx, float *feat, uint32_t width, uint32_t height, int kernel, int flags,
+                             void *hip_stream);
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; plane-distance position term) of an
+   RGBA32F frame guided by its feature buffer: `iterations` passes (1..8) of a 5x5 B3-spline kernel
+   at tap distance 1 << pass; each tap weighted by exp(-(|dc|^2/sc^2 + |dN|^2/sn^2 + (dP.N)^2/sp^2)),
+   the colour tolerance sc halving every pass.  A sigma of +INFINITY switches its term off; a sigma
+   <= 0 or NaN is RT_ERR_ARG.  Alpha is copied.  out_rgba == in_rgba is allowed (no other overlap);
+   in_rgba (otherwise) and feat are never written; intermediate passes live in scratch the context
+   owns.  Inputs are assumed finite, apart from the t of RT_FEAT_NONE pixels, which the filter
+   does not read. */
+typedef struct rt_denoise_params {
+    uint32_t iterations;
+    float sigma_color, sigma_normal, sigma_plane;
+} rt_denoise_params;
+int rt_denoise_defaults(rt_denoise_params *p); /* 5, 2.0f, 0.3f, 0.1f */
+int rt_denoise(rt_ctx *ctx, const float *in_rgba, const float *feat, float *out_rgba, uint32_t width, uint32_t height,
+               const rt_denoise_params *params, int flags);
+int rt_denoise_async(rt_ctx *ctx, const float *in_rgba, const float *feat, float *out_rgba, uint32_t width,
+                     uint32_t height, const rt_denoise_params *params, int flags, void *hip_stream);
+/* Device time of the last feature kernel / of all passes of the last denoise (HIP events of their
+   own, apart from rt_last_kernel_ms), ms. */
+int rt_last_features_ms(const rt_ctx *ctx, float *ms);
+int rt_last_denoise_ms(const rt_ctx *ctx, float *ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

@@ -43,6 +43,11 @@ RT_BUILD_GPU = 1
 RT_OUT_DEVICE = 1
 RT_SEEDS_HALO = 2
 
+# surface ids of a feature buffer (>= 0: a triangle index; sphere s: RT_FEAT_SPHERE0 - s)
+RT_FEAT_BOX = -1
+RT_FEAT_NONE = -2
+RT_FEAT_SPHERE0 = -16
+
 # --- record layouts (rt_types.h) --------------------------------------------------------
 VEC3 = ("<f4", 3)
 SPHERE_DTYPE = np.dtype(
@@ -150,6 +155,11 @@ class RtRenderInfo(ctypes.Structure):
     ]
 
 
+class RtDenoiseParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_plane", ctypes.c_float)]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -190,6 +200,16 @@ SIGNATURES = {
     "rt_last_render_info": (_i32, [_vp, ctypes.POINTER(RtRenderInfo)]),
     "rt_last_long_chains": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
     "rt_trace_rays": (_i32, [_vp, _vp, _u32, _i32, _vp, _vp]),
+    # first-hit feature buffers and the display denoiser (csrc/rt_denoise.hip)
+    "rt_get_camera": (_i32, [_vp, _u32, _vp]),
+    "rt_primary_rays": (_i32, [_vp, _u32, _u32, _vp]),
+    "rt_render_features": (_i32, [_vp, _vp, _u32, _u32, _i32, _i32]),
+    "rt_render_features_async": (_i32, [_vp, _vp, _u32, _u32, _i32, _i32, _vp]),
+    "rt_denoise_defaults": (_i32, [ctypes.POINTER(RtDenoiseParams)]),
+    "rt_denoise": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseParams), _i32]),
+    "rt_denoise_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseParams), _i32, _vp]),
+    "rt_last_features_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
+    "rt_last_denoise_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

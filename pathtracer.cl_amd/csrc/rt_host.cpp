@@ -285,6 +285,17 @@ struct rt_ctx {
     size_t last_bytes = 0;
     /* persistent-grid size per (traversal kind, counting, kernel form): index (trav * 2 + count) * 3 + form */
     int grid_cache[6 * (RT_TRAV_BVH4Q + 1)] = {};
+    /* first-hit features and the display denoiser (rt_denoise.hip): scratch and events of their own.
+       aux_stream: the stream of the last such call not yet followed by a render (ev_aux: its end) —
+       the next render, ray query or probe on another stream waits for it (the spill area, the
+       framebuffer the filter reads) */
+    float *d_dn_tmp[2] = {nullptr, nullptr}; /* the filter's intermediate passes */
+    size_t dn_tmp_bytes[2] = {0, 0};
+    float *d_dn_stage = nullptr; /* host buffers' staging: colour then the two feature planes */
+    size_t dn_stage_bytes = 0;
+    hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr, ev_d0 = nullptr, ev_d1 = nullptr, ev_aux = nullptr;
+    bool have_feat_ms = false, have_dn_ms = false;
+    hipStream_t aux_stream = nullptr;
 };
 
 namespace {
@@ -479,6 +490,13 @@ int ensure_spill(rt_ctx *c, size_t entries)
     c->spill_entries = 0;
     HIPCHK(c, hipMalloc(&c->d_spill, entries * sizeof(int32_t)));
     c->spill_entries = entries;
+    return RT_OK;
+}
+
+/* work on `st` that shares buffers with a pending feature / denoise call on another stream: after it */
+int wait_aux(rt_ctx *c, hipStream_t st)
+{
+    if (c->aux_stream && st != c->aux_stream) HIPCHK(c, hipStreamWaitEvent(st, c->ev_aux, 0));
     return RT_OK;
 }
 
@@ -1066,6 +1084,12 @@ try {
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
     if (c->h_counters) (void)hipHostFree(c->h_counters);
     free_dev(c->d_stage);
+    if (c->aux_stream) (void)hipEventSynchronize(c->ev_aux);
+    free_dev(c->d_dn_tmp[0]);
+    free_dev(c->d_dn_tmp[1]);
+    free_dev(c->d_dn_stage);
+    for (hipEvent_t ev : {c->ev_f0, c->ev_f1, c->ev_d0, c->ev_d1, c->ev_aux})
+        if (ev) (void)hipEventDestroy(ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->evm) (void)hipEventDestroy(c->evm);
@@ -1470,6 +1494,7 @@ try {
         if (c->sync_stream == c->stream) HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_done, 0));
     }
+    if (const int r = wait_aux(c, st)) return r;
     const size_t npx = (size_t)W * H;
     if (c->part_probe_px < npx) {
         HIPCHK(c, hipStreamSynchronize(st));
@@ -1643,6 +1668,10 @@ try {
     if (c->sync_stream && st != c->sync_stream) {
         if (c->sync_stream == c->stream) HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_done, 0));
+    }
+    if (c->aux_stream) { /* and after a feature / denoise call enqueued since (rt_denoise.hip) */
+        if (const int r = wait_aux(c, st)) return r;
+        c->aux_stream = nullptr;
     }
     /* the counters, the guard word and the queue cursors: one memset (none when the last render's
        k_counters_out left them zeroed) */
@@ -2064,6 +2093,7 @@ try {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->sync_stream && c->sync_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->sync_stream));
+    if (c->aux_stream) HIPCHK(c, hipEventSynchronize(c->ev_aux));
     const unsigned long long *h = c->h_counters;
     if (c->info.lists_rebuilt) { /* the list area the new lists took: sizes the next build's area */
         const uint32_t used = (uint32_t)(h[RT_COUNTER_WORDS] & 0xffffffffu);
@@ -2309,6 +2339,7 @@ try {
         if (c->sync_stream && c->sync_stream != c->stream) {
             e = hipStreamWaitEvent(c->stream, c->ev_done, 0); /* (recorded on the caller's stream) */
         }
+        if (e == hipSuccess && c->aux_stream && c->aux_stream != c->stream) e = hipStreamWaitEvent(c->stream, c->ev_aux, 0);
         if (e == hipSuccess && c->counting) e = hipMemsetAsync(c->d_counters, 0, RT_COUNTER_WORDS * sizeof(unsigned long long), c->stream);
         if (e == hipSuccess) {
             const int le = rt_launch_trace_rays(trav_nodes(c), c->d_tris, c->n_tris, d_rays, n, any_hit, kind, c->d_spill,
@@ -2334,6 +2365,233 @@ try {
     cleanup();
     if (e != hipSuccess) return hip_fail(c, e, "rt_trace_rays");
     return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+/* ---- first-hit features and the display denoiser --------- */
+
+namespace {
+
+rt_camera frame_camera(const rt_ctx *c, uint32_t W)
+{
+    rt_camera cam;
+    if (c->cam_override) cam = c->cam_explicit;
+    else camera_from_view(c->view, c->fov, W, &cam);
+    return cam;
+}
+
+/* A feature / denoise call on `st` begins: its events exist, and it is ordered after the context's
+   pending render the way a render on another stream is (ev_done), and after an earlier such call. */
+int aux_begin(rt_ctx *c, hipStream_t st)
+{
+    for (hipEvent_t *ev : {&c->ev_f0, &c->ev_f1, &c->ev_d0, &c->ev_d1})
+        if (!*ev) HIPCHK(c, hipEventCreate(ev));
+    if (!c->ev_aux) HIPCHK(c, hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming));
+    if (c->sync_stream && st != c->sync_stream) {
+        if (c->sync_stream == c->stream) HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(st, c->ev_done, 0));
+    }
+    return wait_aux(c, st);
+}
+
+/* ... and ends: the next render (rt_render_async) orders itself after ev_aux */
+int aux_end(rt_ctx *c, hipStream_t st)
+{
+    HIPCHK(c, hipEventRecord(c->ev_aux, st));
+    c->aux_stream = st;
+    return RT_OK;
+}
+
+int ensure_dev(rt_ctx *c, float *&buf, size_t &have, size_t need)
+{
+    if (need <= have) return RT_OK;
+    if (c->aux_stream) HIPCHK(c, hipEventSynchronize(c->ev_aux)); /* a pending call may still use it */
+    free_dev(buf);
+    buf = nullptr;
+    have = 0;
+    HIPCHK(c, hipMalloc(&buf, need));
+    have = need;
+    return RT_OK;
+}
+
+bool frame_ok(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H < (1ull << 28); }
+
+} // namespace
+
+int rt_get_camera(const rt_ctx *c, uint32_t width, rt_camera *out)
+try {
+    if (!c || !out || width == 0) return RT_ERR_ARG;
+    *out = frame_camera(c, width);
+    return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_primary_rays(const rt_camera *cam, uint32_t W, uint32_t H, rt_ray *out)
+try {
+    if (!cam || !out || W == 0 || H == 0) return RT_ERR_ARG;
+    const float hw = ((float)W) / 2.0f, hh = ((float)H) / 2.0f;
+    for (uint32_t y = 0; y < H; ++y)
+        for (uint32_t x = 0; x < W; ++x) {
+            /* the kernels' camera_dir (raytracer.cl:81-85): float4 lanes incl. w, v / sqrt(dot(v, v)) */
+            const float a = ((float)x + 0.5f) - hw, b = ((float)y + 0.5f) - hh;
+            const float vx = (cam->view.x + cam->right.x * a) + cam->up.x * b;
+            const float vy = (cam->view.y + cam->right.y * a) + cam->up.y * b;
+            const float vz = (cam->view.z + cam->right.z * a) + cam->up.z * b;
+            const float vw = (cam->view.w + cam->right.w * a) + cam->up.w * b;
+            const float len = rt_sqrtf(((vx * vx + vy * vy) + vz * vz) + vw * vw);
+            rt_ray &r = out[(size_t)y * W + x];
+            r.o = {cam->position.x, cam->position.y, cam->position.z};
+            r.d = {vx / len, vy / len, vz / len};
+            r.tmin = RT_SMALL_F;
+            r.tmax = rt_inff();
+            r.propagation = {1.0f, 1.0f, 1.0f};
+            r.extinction = {0.0f, 0.0f, 0.0f};
+            r.diffuse_bounce = 0;
+        }
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_render_features_async(rt_ctx *c, float *feat, uint32_t W, uint32_t H, int kernel, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!feat) return fail(c, RT_ERR_ARG, "null feature buffer");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (kernel < RT_KERNEL_SPHERES || kernel > RT_KERNEL_TRIS) return fail(c, RT_ERR_ARG, "unknown kernel");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_render_features: flags other than RT_OUT_DEVICE");
+    if (kernel == RT_KERNEL_TRIS && c->n_tris == 0) return fail(c, RT_ERR_NO_MESH, "no mesh set");
+    if (kernel != RT_KERNEL_TRIS && c->spheres.empty()) return fail(c, RT_ERR_NO_SCENE, "no spheres set");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t bytes = (size_t)W * H * 2 * 4 * sizeof(float);
+    float *dfeat = feat;
+    if (!(flags & RT_OUT_DEVICE)) {
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, bytes)) return r;
+        dfeat = c->d_dn_stage;
+    }
+    RtFeatLaunch a{};
+    a.feat = dfeat;
+    a.cam = frame_camera(c, W);
+    a.W = W;
+    a.H = H;
+    int trav = 0;
+    if (kernel == RT_KERNEL_TRIS) {
+        trav = trav_kind(c);
+        a.nodes = trav_nodes(c);
+        a.tris = c->d_tris;
+        a.n_tris = c->n_tris;
+        a.spill_cap = spill_cap(c);
+        if (a.spill_cap) {
+            const size_t blocks = ((size_t)W * H + RT_BLOCK - 1) / RT_BLOCK;
+            /* (growing it frees the old area: hipFree waits for whatever still runs on it) */
+            if (const int r = ensure_spill(c, blocks * RT_BLOCK * a.spill_cap)) return r;
+        }
+        a.spill = c->d_spill;
+    } else {
+        a.spheres = c->d_spheres;
+        a.n_spheres = (uint32_t)c->spheres.size();
+    }
+    if (const int r = aux_begin(c, st)) return r;
+    HIPCHK(c, hipEventRecord(c->ev_f0, st));
+    const int e = rt_launch_features(a, trav, st);
+    if (e) return hip_fail(c, (hipError_t)e, "feature kernel launch");
+    HIPCHK(c, hipEventRecord(c->ev_f1, st));
+    c->have_feat_ms = true;
+    if (!(flags & RT_OUT_DEVICE)) HIPCHK(c, hipMemcpyAsync(feat, dfeat, bytes, hipMemcpyDeviceToHost, st));
+    return aux_end(c, st);
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_render_features(rt_ctx *c, float *feat, uint32_t W, uint32_t H, int kernel, int flags)
+try {
+    const int r = rt_render_features_async(c, feat, W, H, kernel, flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_denoise_defaults(rt_denoise_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->iterations = 5;
+    p->sigma_color = 2.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_denoise_async(rt_ctx *c, const float *in, const float *feat, float *out, uint32_t W, uint32_t H,
+                     const rt_denoise_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!in || !feat || !out || !prm) return fail(c, RT_ERR_ARG, "rt_denoise: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_denoise: flags other than RT_OUT_DEVICE");
+    if (prm->iterations < 1 || prm->iterations > 8) return fail(c, RT_ERR_ARG, "rt_denoise: iterations outside 1..8");
+    const float sig[3] = {prm->sigma_color, prm->sigma_normal, prm->sigma_plane};
+    for (float s : sig)
+        if (!(s > 0.0f)) return fail(c, RT_ERR_ARG, "rt_denoise: a sigma is not positive"); /* <= 0 or NaN */
+    /* the inverse variances, in float (+INFINITY: 0, the term is off) */
+    const float isn = 1.0f / (sig[1] * sig[1]), isp = 1.0f / (sig[2] * sig[2]);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t plane = (size_t)W * H * 4 * sizeof(float);
+    const uint32_t n = prm->iterations;
+    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) /* (three passes and more alternate between two) */
+        if (const int r = ensure_dev(c, c->d_dn_tmp[k], c->dn_tmp_bytes[k], plane)) return r;
+    const float *din = in, *dfeat = feat;
+    float *dout = out;
+    if (!(flags & RT_OUT_DEVICE)) {
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, 3 * plane)) return r;
+    }
+    if (const int r = aux_begin(c, st)) return r;
+    if (!(flags & RT_OUT_DEVICE)) {
+        float *stage = c->d_dn_stage;
+        HIPCHK(c, hipMemcpyAsync(stage, in, plane, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(stage + plane / sizeof(float), feat, 2 * plane, hipMemcpyHostToDevice, st));
+        din = stage;
+        dfeat = stage + plane / sizeof(float);
+        dout = stage; /* the last pass never reads it (below) */
+    }
+    HIPCHK(c, hipEventRecord(c->ev_d0, st));
+    /* pass i reads the previous pass's output (pass 0: the input) and writes a scratch buffer, the
+       last one the output — through scratch and a copy when that is the buffer it reads (one pass
+       in place) */
+    const float *src = din;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float sc = ldexpf(prm->sigma_color, -(int)i); /* the colour tolerance halves every pass */
+        const float isc = 1.0f / (sc * sc);
+        float *dst = (i + 1 == n && dout != src) ? dout : c->d_dn_tmp[src == c->d_dn_tmp[0] ? 1 : 0];
+        const int e = rt_launch_atrous(src, dfeat, dst, W, H, 1u << i, isc, isn, isp, st);
+        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
+        src = dst;
+    }
+    if (src != dout) HIPCHK(c, hipMemcpyAsync(dout, src, plane, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipEventRecord(c->ev_d1, st));
+    c->have_dn_ms = true;
+    if (!(flags & RT_OUT_DEVICE)) HIPCHK(c, hipMemcpyAsync(out, dout, plane, hipMemcpyDeviceToHost, st));
+    return aux_end(c, st);
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_denoise(rt_ctx *c, const float *in, const float *feat, float *out, uint32_t W, uint32_t H,
+               const rt_denoise_params *prm, int flags)
+try {
+    const int r = rt_denoise_async(c, in, feat, out, W, H, prm, flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_last_features_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->have_feat_ms) return RT_ERR_STATE;
+    if (hipEventSynchronize(c->ev_f1) != hipSuccess) return RT_ERR_HIP;
+    return hipEventElapsedTime(ms, c->ev_f0, c->ev_f1) == hipSuccess ? RT_OK : RT_ERR_HIP;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_last_denoise_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->have_dn_ms) return RT_ERR_STATE;
+    if (hipEventSynchronize(c->ev_d1) != hipSuccess) return RT_ERR_HIP;
+    return hipEventElapsedTime(ms, c->ev_d0, c->ev_d1) == hipSuccess ? RT_OK : RT_ERR_HIP;
 } RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
 
 /* ---- synthetic meshes ---------------------------------------------------- */

@@ -298,6 +298,27 @@ int rt_launch_spheres(const RtSphLaunch &a, bool single_sample, void *stream);
 int rt_launch_trace_rays(const float *nodes, const float *tris, uint32_t n_tris, const rt_ray *rays, uint32_t n,
                          int any_hit, int trav, int32_t *spill, uint32_t spill_cap, int32_t *out_idx, float *out_t,
                          unsigned long long *counters, void *stream); /* counters: NULL, or counting (queries, nodes, tests, leaves) */
+/* First-hit feature buffers and the display filter (rt_denoise.hip).  feat: 2 planes of W x H
+   float4 on the device, (P, t) then (N, surface id bits).  spheres != NULL: the sphere kernels'
+   scene (trav ignored); else the mesh through traversal kind `trav`, spill indexed by block
+   (ceil(W H / RT_BLOCK) blocks of RT_BLOCK lanes, spill_cap entries each). */
+struct RtFeatLaunch {
+    float *feat;
+    const float *nodes;
+    const float *tris;
+    uint32_t n_tris;
+    const rt_sphere *spheres;
+    uint32_t n_spheres;
+    rt_camera cam;
+    uint32_t W, H;
+    int32_t *spill;
+    uint32_t spill_cap;
+};
+int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
+/* One a-trous pass at tap distance `step` with the inverse variances of its colour, normal and
+   plane terms; col, feat and out are device buffers, out apart from col. */
+int rt_launch_atrous(const float *col, const float *feat, float *out, uint32_t W, uint32_t H, uint32_t step, float isc,
+                     float isn, float isp, void *stream);
 /* Camera-ray candidate lists for the launch's pixels (writes a.pixel_lists and the list
    records in the triangle buffer at a.list_base); nodes4 = full-precision 4-wide tree,
    q4 = compressed nodes (their normal boxes; may be NULL). */

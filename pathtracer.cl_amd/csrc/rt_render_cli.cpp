@@ -13,6 +13,13 @@
  *              one JSON line per event on stdout: the view state and whether a redisplay was
  *              posted) [--max-progression N] [--frames-out FILE]   (every displayed frame,
  *              appended as raw RGBA32F)
+ *             [--denoise [ITER]]   (the display denoiser, ITER passes (default 5): the frame written by
+ *              --raw / --pfm stays the raw one; the filtered frame goes to --denoised FILE (raw RGBA32F)
+ *              and / or --denoised-pfm FILE; with --events the view displays the filtered frame
+ *              (ProgressiveViewHIP::setDenoise): --frames-out holds what it shows, --raw-frames-out FILE
+ *              the accumulation buffer of every displayed frame)
+ *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
+ *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
  *              is the compact tile — the sharding path rehearsed as separate processes)
  *             [--comm-ranks N --comm-rank R --comm-id FILE]   (native multi-GPU: one process per
@@ -94,7 +101,8 @@ int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
-                         "[--device K] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
+                         "[--device K] [--denoise [ITER]] [--denoised f] [--denoised-pfm f] [--features-out f] "
+                         "[--raw-frames-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
 
@@ -125,7 +133,9 @@ bool share_comm_id(const std::string &path, int rank, uint8_t id[RT_COMM_ID_BYTE
 
 int main(int argc, char **argv)
 {
-    std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out;
+    std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out;
+    bool denoise = false;
+    rt_denoise_params den_params = RayTracerHIP::denoiseDefaults();
     unsigned W = 512, H = 512, frames = 1, sr = 1, depth = 6, n_tris = 0, max_prog = 10000;
     int device = 0, comm_ranks = 0, comm_rank = 0;
     rt_tile tile{8, 1, 0};
@@ -138,8 +148,17 @@ int main(int argc, char **argv)
             linear = true;
             continue;
         }
+        if (a == "--denoise") { /* an optional pass count follows */
+            denoise = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') den_params.iterations = (unsigned)std::atoi(argv[++i]);
+            continue;
+        }
         if (!(v = next())) return usage();
         if (a == "--scene") scene = v;
+        else if (a == "--denoised") den_raw = v;
+        else if (a == "--denoised-pfm") den_pfm = v;
+        else if (a == "--features-out") feat_out = v;
+        else if (a == "--raw-frames-out") raw_frames_out = v;
         else if (a == "--width") W = (unsigned)std::atoi(v);
         else if (a == "--height") H = (unsigned)std::atoi(v);
         else if (a == "--frames") frames = (unsigned)std::atoi(v);
@@ -185,8 +204,12 @@ int main(int argc, char **argv)
         if (!events.empty()) { /* interactive replay through the display state machine */
             ProgressiveViewHIP view(rt, W, H, kernel);
             view.setProgressive(max_prog);
+            if (denoise) view.setDenoise(true, den_params);
             FILE *fo = frames_out.empty() ? nullptr : std::fopen(frames_out.c_str(), "wb");
             if (!frames_out.empty() && !fo) return 1;
+            FILE *fr = raw_frames_out.empty() ? nullptr : std::fopen(raw_frames_out.c_str(), "wb");
+            FILE *ff = feat_out.empty() ? nullptr : std::fopen(feat_out.c_str(), "wb");
+            if ((!raw_frames_out.empty() && !fr) || (!feat_out.empty() && !ff)) return 1;
             size_t pos = 0;
             while (pos <= events.size()) {
                 const size_t end = std::min(events.find(',', pos), events.size());
@@ -200,6 +223,15 @@ int main(int argc, char **argv)
                     if (traced && fo) {
                         const std::vector<float> &px = view.pixels();
                         if (std::fwrite(px.data(), 4, px.size(), fo) != px.size()) return 1;
+                    }
+                    if (traced && fr) {
+                        const std::vector<float> &px = view.rawPixels();
+                        if (std::fwrite(px.data(), 4, px.size(), fr) != px.size()) return 1;
+                    }
+                    if (traced && ff) {
+                        std::vector<float> ft((size_t)view.width() * view.height() * 8);
+                        rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
+                        if (std::fwrite(ft.data(), 4, ft.size(), ff) != ft.size()) return 1;
                     }
                 } else if (ev == "l") post = view.specialKey(ProgressiveViewHIP::KEY_LEFT);
                 else if (ev == "r") post = view.specialKey(ProgressiveViewHIP::KEY_RIGHT);
@@ -217,6 +249,8 @@ int main(int argc, char **argv)
                             view.azimuth(), view.elevation(), view.width(), view.height());
             }
             if (fo) std::fclose(fo);
+            if (fr) std::fclose(fr);
+            if (ff) std::fclose(ff);
             std::printf("{\"progression\": %u, \"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, "
                         "\"height\": %u}\n",
                         view.progression(), view.azimuth(), view.elevation(), view.width(), view.height());
@@ -268,6 +302,40 @@ int main(int argc, char **argv)
         std::vector<float> img((size_t)W * rows * 4);
         if (hipMemcpy(img.data(), dbuf, img.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return 1;
         (void)hipFree(dbuf);
+        if (denoise || !feat_out.empty()) { /* whole frames only: the features know no tile */
+            if (tiled) {
+                std::fprintf(stderr, "rt_render: --denoise / --features-out need the whole frame (no --tile)\n");
+                return 1;
+            }
+            std::vector<float> feat((size_t)W * H * 8), den(img.size());
+            rt.renderFeatures(feat.data(), W, H, kernel);
+            float fms = 0.0f, dms = 0.0f;
+            rt_last_features_ms(rt.handle(), &fms);
+            if (denoise) {
+                rt.denoise(img.data(), feat.data(), den.data(), W, H, den_params);
+                rt_last_denoise_ms(rt.handle(), &dms);
+            }
+            std::printf("{\"features_ms\": %.4f, \"denoise_ms\": %.4f, \"denoise_passes\": %u}\n", fms, dms,
+                        denoise ? den_params.iterations : 0u);
+            if (!feat_out.empty()) {
+                FILE *f = std::fopen(feat_out.c_str(), "wb");
+                if (!f || std::fwrite(feat.data(), 4, feat.size(), f) != feat.size()) return 1;
+                std::fclose(f);
+            }
+            if (denoise && !den_raw.empty()) {
+                FILE *f = std::fopen(den_raw.c_str(), "wb");
+                if (!f || std::fwrite(den.data(), 4, den.size(), f) != den.size()) return 1;
+                std::fclose(f);
+            }
+            if (denoise && !den_pfm.empty()) {
+                FILE *f = std::fopen(den_pfm.c_str(), "wb");
+                if (!f) return 1;
+                std::fprintf(f, "PF\n%u %u\n-1.0\n", W, H);
+                for (int y = (int)H - 1; y >= 0; --y)
+                    for (unsigned x = 0; x < W; ++x) std::fwrite(&den[((size_t)y * W + x) * 4], 4, 3, f);
+                std::fclose(f);
+            }
+        }
         std::printf("{\"frames\": %u, \"seconds\": %.6f, \"frames_per_sec\": %.4f, \"mrays_per_sec\": %.2f}\n", frames,
                     dt, frames / dt, rays / dt / 1e6);
         if (!raw.empty()) {

@@ -229,6 +229,91 @@ class RayTracer:
             if sync:
                 self.synchronize()
 
+    # ---- first-hit features and the display denoiser (pathtracer_rt.h) --------------------
+    @staticmethod
+    def _frame_buffer(buf, need: int, what: str) -> int:
+        """The checks of rayTrace's framebuffer (float32, contiguous, `need` floats); returns the
+        RT_OUT_DEVICE flag of a torch CUDA tensor, 0 for host memory."""
+        if isinstance(buf, np.ndarray):
+            if buf.dtype != np.float32 or not buf.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{what} must be a contiguous float32 array")
+            n, dev = buf.size, 0
+        else:
+            if buf.dtype.__str__() not in ("torch.float32",):
+                raise TypeError(f"{what} must be float32")
+            if not buf.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+            n, dev = buf.numel(), _abi.RT_OUT_DEVICE if getattr(buf, "is_cuda", False) else 0
+        if n < need:
+            raise ValueError(f"{what} holds {n} floats, {need} needed")
+        return dev
+
+    def getCamera(self, width: int) -> np.ndarray:
+        """The Camera (16 floats) a render of this width would use."""
+        cam = np.empty(_abi.CAMERA_FLOATS, np.float32)
+        self._check(self._lib.rt_get_camera(self._h, int(width), _abi.ptr(cam)), "rt_get_camera")
+        return cam
+
+    def primaryRays(self, width: int, height: int) -> np.ndarray:
+        """The pixel-centre camera rays of a W x H frame under the current camera (RAY_DTYPE, row-major)."""
+        cam = self.getCamera(width)
+        rays = np.empty(int(width) * int(height), _abi.RAY_DTYPE)
+        st = self._lib.rt_primary_rays(_abi.ptr(cam), int(width), int(height), _abi.ptr(rays))
+        self._check(st, "rt_primary_rays")
+        return rays
+
+    def renderFeatures(self, feat, width: int, height: int, kernel: int = _abi.RT_KERNEL_TRIS, stream=None,
+                       sync: bool = True) -> None:
+        """First-hit features of every pixel-centre ray into `feat` (2 planes of W*H float4: (P, t),
+        then (N, surface id as int32 bits); numpy or torch CUDA tensor)."""
+        self._sync_scene()
+        flags = self._frame_buffer(feat, 2 * int(width) * int(height) * 4, "feature buffer")
+        if sync and stream is None:
+            st = self._lib.rt_render_features(self._h, _abi.ptr(feat), int(width), int(height), int(kernel), flags)
+            self._check(st, "rt_render_features")
+        else:
+            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
+            st = self._lib.rt_render_features_async(self._h, _abi.ptr(feat), int(width), int(height), int(kernel),
+                                                    flags, sp)
+            self._check(st, "rt_render_features_async")
+            if sync:
+                self.synchronize()
+
+    def denoise(self, src, feat, dst, width: int, height: int, iterations: int = 5, sigma_color: float = 2.0,
+                sigma_normal: float = 0.3, sigma_plane: float = 0.1, stream=None, sync: bool = True) -> None:
+        """Edge-avoiding a-trous filter of the RGBA32F frame `src` guided by `feat` (renderFeatures)
+        into `dst` (may be `src`); all three numpy arrays, or all three torch CUDA tensors.  The
+        accumulation buffer of a progressive render is `src`: it is only read."""
+        px = int(width) * int(height)
+        f_src = self._frame_buffer(src, px * 4, "source frame")
+        f_feat = self._frame_buffer(feat, px * 8, "feature buffer")
+        f_dst = self._frame_buffer(dst, px * 4, "destination frame")
+        if not f_src == f_feat == f_dst:
+            raise ValueError("denoise: source, features and destination must all be host arrays or all device tensors")
+        prm = _abi.RtDenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_plane))
+        if sync and stream is None:
+            st = self._lib.rt_denoise(self._h, _abi.ptr(src), _abi.ptr(feat), _abi.ptr(dst), int(width), int(height),
+                                      ctypes.byref(prm), f_src)
+            self._check(st, "rt_denoise")
+        else:
+            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
+            st = self._lib.rt_denoise_async(self._h, _abi.ptr(src), _abi.ptr(feat), _abi.ptr(dst), int(width),
+                                            int(height), ctypes.byref(prm), f_src, sp)
+            self._check(st, "rt_denoise_async")
+            if sync:
+                self.synchronize()
+
+    def lastFeaturesMs(self) -> float:
+        ms = ctypes.c_float()
+        self._check(self._lib.rt_last_features_ms(self._h, ctypes.byref(ms)), "rt_last_features_ms")
+        return ms.value
+
+    def lastDenoiseMs(self) -> float:
+        """Device time of all passes of the last denoise, ms."""
+        ms = ctypes.c_float()
+        self._check(self._lib.rt_last_denoise_ms(self._h, ctypes.byref(ms)), "rt_last_denoise_ms")
+        return ms.value
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
