@@ -34,6 +34,14 @@
  *                    features (rendered only after a reallocation or a camera change), and reads
  *                    that one back into pixels().  rawPixels() fetches the undenoised frame on
  *                    request.  Off (the default), every call does exactly what it did before.
+ *   setTemporal(on, params)  (no counterpart in the reference) carry the displayed frame across
+ *                    camera moves: the view keeps the last displayed (merged)
+ *                    frame with its per-pixel history length, features and camera; at the first
+ *                    display after a key press, a drag or a restart it reprojects them into the new
+ *                    view, and every display shows the blend of that carried history with the
+ *                    accumulation buffer (then filtered, with the denoiser on).  The accumulation
+ *                    buffer is only read; rawPixels() returns it.  The history is dropped at a
+ *                    reshape; the scene is assumed static.  Off (the default), nothing changes.
  */
 #ifndef PROGRESSIVE_VIEW_HIP_HPP
 #define PROGRESSIVE_VIEW_HIP_HPP
@@ -42,6 +50,8 @@
 
 #include <cmath>
 #include <stdexcept>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "RayTracerHIP.hpp"
@@ -109,6 +119,7 @@ public:
     {
         const bool post = progression_ >= maxProgression_;
         progression_ = 0;
+        carry_ = true;
         return post;
     }
 
@@ -119,12 +130,22 @@ public:
         denoiseParams_ = params;
     }
     bool denoising() const { return denoise_; }
+    void setTemporal(bool on, const rt_reproject_params &params = RayTracerHIP::reprojectDefaults())
+    {
+        if (on && !temporal_) {
+            featDirty_ = true;
+            haveHist_ = false;
+        }
+        temporal_ = on;
+        temporalParams_ = params;
+    }
+    bool temporal() const { return temporal_; }
 
     const std::vector<float> &pixels() const { return pbo_; }
     /* The accumulation buffer as rendered (what pixels() holds with the denoiser off), read back now. */
     const std::vector<float> &rawPixels()
     {
-        if (!denoise_) return pbo_;
+        if (!denoise_ && !temporal_) return pbo_;
         raw_.assign(pbo_.size(), 0.0f);
         if (dev_ && hipMemcpy(raw_.data(), dev_, raw_.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             throw std::runtime_error("ProgressiveViewHIP: raw frame readback failed");
@@ -153,18 +174,67 @@ private:
             throw std::runtime_error("ProgressiveViewHIP: framebuffer allocation failed");
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
         featDirty_ = true;
+        haveHist_ = false;
     }
     void release()
     {
         if (dev_) (void)hipFree(dev_);
         if (den_) (void)hipFree(den_);
         if (feat_) (void)hipFree(feat_);
-        dev_ = den_ = feat_ = nullptr;
+        if (featPrev_) (void)hipFree(featPrev_);
+        if (hist_) (void)hipFree(hist_);
+        if (carried_) (void)hipFree(carried_);
+        dev_ = den_ = feat_ = featPrev_ = hist_ = carried_ = nullptr;
+    }
+    void alloc(float *&buf, size_t bytes, const char *what)
+    {
+        if (!buf && hipMalloc(&buf, bytes) != hipSuccess)
+            throw std::runtime_error(std::string("ProgressiveViewHIP: ") + what + " allocation failed");
+    }
+    void traceTemporal()
+    {
+        const size_t px = (size_t)width_ * height_, frame = px * 4 * sizeof(float);
+        /* hist_ / carried_: a colour frame followed by its plane of history lengths */
+        alloc(feat_, 2 * frame, "feature buffer");
+        alloc(featPrev_, 2 * frame, "feature buffer");
+        alloc(hist_, frame + px * sizeof(float), "history buffer");
+        alloc(carried_, frame + px * sizeof(float), "history buffer");
+        if (denoise_) alloc(den_, frame, "denoised framebuffer");
+        const rt_camera cam = rt_.getCamera(width_);
+        const float *histFeat = feat_; /* the features of the view the kept frame was displayed in */
+        if (featDirty_) {
+            std::swap(feat_, featPrev_);
+            histFeat = featPrev_;
+            rt_.renderFeatures(feat_, width_, height_, kernel_, true);
+            featDirty_ = false;
+            carry_ = true;
+        }
+        if (!haveHist_) { /* after a (re)allocation: no history anywhere */
+            if (hipMemset(carried_, 0, frame + px * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: history reset failed");
+        } else if (carry_) { /* a new accumulation begins: carry the kept frame into it */
+            rt_.reproject(hist_, hist_ + 4 * px, histFeat, histCam_, feat_, carried_, carried_ + 4 * px, width_, height_,
+                          temporalParams_, true);
+        }
+        carry_ = false;
+        rt_.temporalMerge(carried_, carried_ + 4 * px, dev_, (float)(progression_ > 1 ? progression_ : 1),
+                          temporalParams_.max_history, hist_, hist_ + 4 * px, width_, height_, true);
+        histCam_ = cam;
+        haveHist_ = true;
+        const float *shown = hist_;
+        if (denoise_) {
+            rt_.denoise(hist_, feat_, den_, width_, height_, denoiseParams_, true);
+            shown = den_;
+        }
+        if (hipMemcpy(pbo_.data(), shown, frame, hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
     }
     void trace()
     {
         rt_.rayTrace(dev_, width_, height_, progression_, kernel_, true);
-        if (denoise_) {
+        if (temporal_) {
+            traceTemporal();
+        } else if (denoise_) {
             const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
             if (!den_ && hipMalloc(&den_, frame) != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: denoised framebuffer allocation failed");
@@ -190,6 +260,12 @@ private:
     float *den_ = nullptr;  /* setDenoise: the filtered frame */
     float *feat_ = nullptr; /* setDenoise: the view's first-hit features */
     bool denoise_ = false, featDirty_ = true;
+    /* setTemporal: the last displayed frame (merged colour + history length), its features and
+       camera; the history carried into the current view (colour + length) */
+    float *hist_ = nullptr, *featPrev_ = nullptr, *carried_ = nullptr;
+    rt_camera histCam_{};
+    bool temporal_ = false, haveHist_ = false, carry_ = false;
+    rt_reproject_params temporalParams_ = RayTracerHIP::reprojectDefaults();
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
     std::vector<float> pbo_, raw_;
     bool realloc_ = true, rendered_ = false;

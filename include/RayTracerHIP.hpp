@@ -234,6 +234,46 @@ public:
         check(rt_denoise(ctx_, in, feat, out, width, height, &params, on_device ? RT_OUT_DEVICE : 0), "denoise");
     }
 
+    /* ---- temporal reprojection of the displayed frame (pathtracer_rt.h) ---- */
+    rt_camera getCamera(unsigned width) const
+    {
+        rt_camera cam;
+        check(rt_get_camera(ctx_, width, &cam), "getCamera");
+        return cam;
+    }
+    static rt_reproject_params reprojectDefaults()
+    {
+        rt_reproject_params p;
+        rt_reproject_defaults(&p);
+        return p;
+    }
+    /* Carry the previous view's displayed frame (prev_rgba, its history lengths prev_len, its
+       features and camera) over to the view of cur_feat: out_rgba / out_len, apart from prev_*. */
+    void reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &prev_cam,
+                   const float *cur_feat, float *out_rgba, float *out_len, unsigned width, unsigned height,
+                   const rt_reproject_params &params = reprojectDefaults(), bool on_device = false)
+    {
+        check(rt_reproject(ctx_, prev_rgba, prev_len, prev_feat, &prev_cam, cur_feat, out_rgba, out_len, width, height,
+                           &params, on_device ? RT_OUT_DEVICE : 0),
+              "reproject");
+    }
+    /* Blend the carried history with the accumulation buffer `cur` of n_cur frames; out_* may be hist_*. */
+    void temporalMerge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                       float max_history, float *out_rgba, float *out_len, unsigned width, unsigned height,
+                       bool on_device = false)
+    {
+        check(rt_temporal_merge(ctx_, hist_rgba, hist_len, cur_rgba, n_cur, max_history, out_rgba, out_len, width, height,
+                                on_device ? RT_OUT_DEVICE : 0),
+              "temporalMerge");
+    }
+    /* Device time of the last reprojection kernel, or (merge) of the last merge kernel, ms. */
+    float lastReprojectMs(bool merge = false) const
+    {
+        float ms = 0.0f;
+        check(rt_last_reproject_ms(ctx_, merge ? nullptr : &ms, merge ? &ms : nullptr), "lastReprojectMs");
+        return ms;
+    }
+
     rt_counters counters() const
     {
         rt_counters c;

@@ -319,6 +319,52 @@ int rt_denoise_async(rt_ctx *ctx, const float *in_rgba, const float *feat, float
 int rt_last_features_ms(const rt_ctx *ctx, float *ms);
 int rt_last_denoise_ms(const rt_ctx *ctx, float *ms);
 
+/* ---- temporal reprojection of the displayed frame across camera moves.  The
+   rules of the feature / denoise calls above hold: display only, no render state is changed, the
+   accumulation buffer is only read, `flags` takes RT_OUT_DEVICE only, the same stream ordering, and
+   arithmetic that a float32 restatement reproduces to the bit.  A history is a displayed RGBA32F
+   frame with, per pixel, the number of frames it averages (`*_len`, one plane of W*H floats; 0: none).
+   The scene is assumed static between the two views, both frames W x H; the caller drops its
+   history on a reshape or a scene change.  Inputs are assumed finite where they are read. ---- */
+typedef struct rt_reproject_params {
+    float plane_tol;   /* tap q lies on pixel p's surface when |(P_q - P_p).N_p| <= plane_tol * t_p */
+    float normal_min;  /* ... and N_q.N_p >= normal_min */
+    float max_history; /* cap of the carried history length, in frames */
+} rt_reproject_params;
+int rt_reproject_defaults(rt_reproject_params *p); /* 0.01f, 0.9f, 32.0f */
+/* Backward reprojection, once per view change: for every pixel p of the new view (cur_feat, as
+   rt_render_features wrote it) solve P_p - prev_cam.position = s (view + a right + b up) (the
+   general 3x3 solve, prev_cam need not be orthogonal); fx = a + W/2 - 0.5, fy = b + H/2 - 0.5 is its
+   place in the previous frame (the inverse of rt_primary_rays).  No history (out rgb = 0, out_len =
+   0) when p met nothing, s <= 0, the determinant is 0, or the place is not finite or has no tap
+   inside the frame.  Otherwise the four bilinear taps (floor fx + {0,1}, floor fy + {0,1}); tap q
+   counts when it is inside the frame, prev_len[q] > 0, q met a surface of p's class (any two
+   triangles match, a sphere only itself, the box only the box) and passes the two tests above:
+   out rgb = sum(w c_q) / wsum, out_len = min(sum(w len_q) / wsum, max_history), out a = 0; no
+   counting tap (wsum = 0): no history.  plane_tol < 0 or NaN, normal_min NaN, max_history < 1 or
+   NaN: RT_ERR_ARG; plane_tol +INFINITY switches that test off.  out_* may not be prev_*
+   (RT_ERR_ARG); no input is written. */
+int rt_reproject(rt_ctx *ctx, const float *prev_rgba, const float *prev_len, const float *prev_feat,
+                 const rt_camera *prev_cam, const float *cur_feat, float *out_rgba, float *out_len, uint32_t width,
+                 uint32_t height, const rt_reproject_params *params, int flags);
+int rt_reproject_async(rt_ctx *ctx, const float *prev_rgba, const float *prev_len, const float *prev_feat,
+                       const rt_camera *prev_cam, const float *cur_feat, float *out_rgba, float *out_len, uint32_t width,
+                       uint32_t height, const rt_reproject_params *params, int flags, void *hip_stream);
+/* Every displayed frame: blend the carried history (h, m) with the accumulation buffer c of n_cur
+   frames (max(progression, 1): a progressive render's frame 0 is overwritten by frame 1).  Where
+   m > 0: out rgb = h + (c - h) (n / (n + m)), out_len = min(n + m, max_history); elsewhere out rgb =
+   c's bits, out_len = min(n, max_history).  out a = c.a.  out_rgba == hist_rgba and out_len ==
+   hist_len are allowed; cur_rgba is never written (out_rgba == cur_rgba: RT_ERR_ARG).  n_cur < 1 or NaN, max_history < 1 or NaN:
+   RT_ERR_ARG. */
+int rt_temporal_merge(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                      float max_history, float *out_rgba, float *out_len, uint32_t width, uint32_t height, int flags);
+int rt_temporal_merge_async(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                            float n_cur, float max_history, float *out_rgba, float *out_len, uint32_t width,
+                            uint32_t height, int flags, void *hip_stream);
+/* Device time of the last reprojection kernel and of the last merge kernel (HIP events of their
+   own), ms; either pointer may be NULL.  RT_ERR_STATE when a kernel asked for has not run. */
+int rt_last_reproject_ms(const rt_ctx *ctx, float *reproject_ms, float *merge_ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

@@ -160,6 +160,10 @@ class RtDenoiseParams(ctypes.Structure):
                 ("sigma_plane", ctypes.c_float)]
 
 
+class RtReprojectParams(ctypes.Structure):
+    _fields_ = [("plane_tol", ctypes.c_float), ("normal_min", ctypes.c_float), ("max_history", ctypes.c_float)]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -210,6 +214,14 @@ SIGNATURES = {
     "rt_denoise_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseParams), _i32, _vp]),
     "rt_last_features_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
     "rt_last_denoise_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
+    # temporal reprojection of the displayed frame (csrc/rt_temporal.hip)
+    "rt_reproject_defaults": (_i32, [ctypes.POINTER(RtReprojectParams)]),
+    "rt_reproject": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtReprojectParams), _i32]),
+    "rt_reproject_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtReprojectParams),
+                                  _i32, _vp]),
+    "rt_temporal_merge": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32]),
+    "rt_temporal_merge_async": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "rt_last_reproject_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

@@ -295,6 +295,9 @@ struct rt_ctx {
     size_t dn_stage_bytes = 0;
     hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr, ev_d0 = nullptr, ev_d1 = nullptr, ev_aux = nullptr;
     bool have_feat_ms = false, have_dn_ms = false;
+    /* the temporal stage (rt_temporal.hip): its two kernels' events */
+    hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;
+    bool have_reproj_ms = false, have_merge_ms = false;
     hipStream_t aux_stream = nullptr;
 };
 
@@ -1088,7 +1091,7 @@ try {
     free_dev(c->d_dn_tmp[0]);
     free_dev(c->d_dn_tmp[1]);
     free_dev(c->d_dn_stage);
-    for (hipEvent_t ev : {c->ev_f0, c->ev_f1, c->ev_d0, c->ev_d1, c->ev_aux})
+    for (hipEvent_t ev : {c->ev_f0, c->ev_f1, c->ev_d0, c->ev_d1, c->ev_r0, c->ev_r1, c->ev_m0, c->ev_m1, c->ev_aux})
         if (ev) (void)hipEventDestroy(ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2383,7 +2386,7 @@ rt_camera frame_camera(const rt_ctx *c, uint32_t W)
    pending render the way a render on another stream is (ev_done), and after an earlier such call. */
 int aux_begin(rt_ctx *c, hipStream_t st)
 {
-    for (hipEvent_t *ev : {&c->ev_f0, &c->ev_f1, &c->ev_d0, &c->ev_d1})
+    for (hipEvent_t *ev : {&c->ev_f0, &c->ev_f1, &c->ev_d0, &c->ev_d1, &c->ev_r0, &c->ev_r1, &c->ev_m0, &c->ev_m1})
         if (!*ev) HIPCHK(c, hipEventCreate(ev));
     if (!c->ev_aux) HIPCHK(c, hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming));
     if (c->sync_stream && st != c->sync_stream) {
@@ -2592,6 +2595,144 @@ try {
     if (!c->have_dn_ms) return RT_ERR_STATE;
     if (hipEventSynchronize(c->ev_d1) != hipSuccess) return RT_ERR_HIP;
     return hipEventElapsedTime(ms, c->ev_d0, c->ev_d1) == hipSuccess ? RT_OK : RT_ERR_HIP;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+/* ---- temporal reprojection of the displayed frame ------- */
+
+int rt_reproject_defaults(rt_reproject_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->plane_tol = 0.01f;
+    p->normal_min = 0.9f;
+    p->max_history = 32.0f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_reproject_async(rt_ctx *c, const float *prev_rgba, const float *prev_len, const float *prev_feat,
+                       const rt_camera *prev_cam, const float *cur_feat, float *out_rgba, float *out_len, uint32_t W,
+                       uint32_t H, const rt_reproject_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!prev_rgba || !prev_len || !prev_feat || !prev_cam || !cur_feat || !out_rgba || !out_len || !prm)
+        return fail(c, RT_ERR_ARG, "rt_reproject: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_reproject: flags other than RT_OUT_DEVICE");
+    if (!(prm->plane_tol >= 0.0f)) return fail(c, RT_ERR_ARG, "rt_reproject: plane_tol negative or NaN");
+    if (prm->normal_min != prm->normal_min) return fail(c, RT_ERR_ARG, "rt_reproject: normal_min is NaN");
+    if (!(prm->max_history >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_reproject: max_history below 1 or NaN");
+    if (out_rgba == prev_rgba || out_len == prev_len)
+        return fail(c, RT_ERR_ARG, "rt_reproject: an output is the previous frame's buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t px = (size_t)W * H;
+    const float *d_prgba = prev_rgba, *d_plen = prev_len, *d_pfeat = prev_feat, *d_cfeat = cur_feat;
+    float *d_orgba = out_rgba, *d_olen = out_len;
+    const bool host = !(flags & RT_OUT_DEVICE);
+    if (host) /* staged: the float4 streams first (px may be odd), then the two length planes */
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, 26 * px * sizeof(float))) return r;
+    if (const int r = aux_begin(c, st)) return r;
+    if (host) {
+        float *s = c->d_dn_stage;
+        HIPCHK(c, hipMemcpyAsync(s, prev_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 4 * px, prev_feat, 8 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 12 * px, cur_feat, 8 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 24 * px, prev_len, px * sizeof(float), hipMemcpyHostToDevice, st));
+        d_prgba = s;
+        d_pfeat = s + 4 * px;
+        d_cfeat = s + 12 * px;
+        d_orgba = s + 20 * px;
+        d_plen = s + 24 * px;
+        d_olen = s + 25 * px;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_r0, st));
+    const int e = rt_launch_reproject(d_prgba, d_plen, d_pfeat, *prev_cam, d_cfeat, d_orgba, d_olen, W, H, prm->plane_tol,
+                                      prm->normal_min, prm->max_history, st);
+    if (e) return hip_fail(c, (hipError_t)e, "reprojection kernel launch");
+    HIPCHK(c, hipEventRecord(c->ev_r1, st));
+    c->have_reproj_ms = true;
+    if (host) {
+        HIPCHK(c, hipMemcpyAsync(out_rgba, d_orgba, 4 * px * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out_len, d_olen, px * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    return aux_end(c, st);
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_reproject(rt_ctx *c, const float *prev_rgba, const float *prev_len, const float *prev_feat,
+                 const rt_camera *prev_cam, const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H,
+                 const rt_reproject_params *prm, int flags)
+try {
+    const int r = rt_reproject_async(c, prev_rgba, prev_len, prev_feat, prev_cam, cur_feat, out_rgba, out_len, W, H, prm,
+                                     flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_temporal_merge_async(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                            float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags,
+                            void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!hist_rgba || !hist_len || !cur_rgba || !out_rgba || !out_len)
+        return fail(c, RT_ERR_ARG, "rt_temporal_merge: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_temporal_merge: flags other than RT_OUT_DEVICE");
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_temporal_merge: n_cur below 1 or NaN");
+    if (!(max_history >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_temporal_merge: max_history below 1 or NaN");
+    if (out_rgba == cur_rgba) return fail(c, RT_ERR_ARG, "rt_temporal_merge: the output is the current frame's buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t px = (size_t)W * H;
+    const float *d_hist = hist_rgba, *d_hlen = hist_len, *d_cur = cur_rgba;
+    float *d_orgba = out_rgba, *d_olen = out_len;
+    const bool host = !(flags & RT_OUT_DEVICE);
+    if (host)
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, 9 * px * sizeof(float))) return r;
+    if (const int r = aux_begin(c, st)) return r;
+    if (host) { /* staged, and merged in place there */
+        float *s = c->d_dn_stage;
+        HIPCHK(c, hipMemcpyAsync(s, hist_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 4 * px, cur_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 8 * px, hist_len, px * sizeof(float), hipMemcpyHostToDevice, st));
+        d_hist = d_orgba = s;
+        d_cur = s + 4 * px;
+        d_hlen = d_olen = s + 8 * px;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_m0, st));
+    const int e = rt_launch_temporal_merge(d_hist, d_hlen, d_cur, n_cur, max_history, d_orgba, d_olen, W, H, st);
+    if (e) return hip_fail(c, (hipError_t)e, "temporal merge kernel launch");
+    HIPCHK(c, hipEventRecord(c->ev_m1, st));
+    c->have_merge_ms = true;
+    if (host) {
+        HIPCHK(c, hipMemcpyAsync(out_rgba, d_orgba, 4 * px * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out_len, d_olen, px * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    return aux_end(c, st);
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_temporal_merge(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                      float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags)
+try {
+    const int r = rt_temporal_merge_async(c, hist_rgba, hist_len, cur_rgba, n_cur, max_history, out_rgba, out_len, W, H,
+                                          flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_last_reproject_ms(const rt_ctx *c, float *reproject_ms, float *merge_ms)
+try {
+    if (!c || (!reproject_ms && !merge_ms)) return RT_ERR_ARG;
+    if ((reproject_ms && !c->have_reproj_ms) || (merge_ms && !c->have_merge_ms)) return RT_ERR_STATE;
+    if (reproject_ms) {
+        if (hipEventSynchronize(c->ev_r1) != hipSuccess) return RT_ERR_HIP;
+        if (hipEventElapsedTime(reproject_ms, c->ev_r0, c->ev_r1) != hipSuccess) return RT_ERR_HIP;
+    }
+    if (merge_ms) {
+        if (hipEventSynchronize(c->ev_m1) != hipSuccess) return RT_ERR_HIP;
+        if (hipEventElapsedTime(merge_ms, c->ev_m0, c->ev_m1) != hipSuccess) return RT_ERR_HIP;
+    }
+    return RT_OK;
 } RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
 
 /* ---- synthetic meshes ---------------------------------------------------- */

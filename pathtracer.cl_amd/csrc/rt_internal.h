@@ -319,6 +319,13 @@ int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
    plane terms; col, feat and out are device buffers, out apart from col. */
 int rt_launch_atrous(const float *col, const float *feat, float *out, uint32_t W, uint32_t H, uint32_t step, float isc,
                      float isn, float isp, void *stream);
+/* Temporal reprojection of the displayed frame (rt_temporal.hip): device buffers;
+   the outputs of the reprojection apart from its inputs, those of the merge possibly its history. */
+int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &prev_cam,
+                        const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H, float plane_tol,
+                        float normal_min, float max_history, void *stream);
+int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
 /* Camera-ray candidate lists for the launch's pixels (writes a.pixel_lists and the list
    records in the triangle buffer at a.list_base); nodes4 = full-precision 4-wide tree,
    q4 = compressed nodes (their normal boxes; may be NULL). */

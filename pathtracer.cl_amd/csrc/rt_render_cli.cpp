@@ -18,6 +18,9 @@
  *              and / or --denoised-pfm FILE; with --events the view displays the filtered frame
  *              (ProgressiveViewHIP::setDenoise): --frames-out holds what it shows, --raw-frames-out FILE
  *              the accumulation buffer of every displayed frame)
+ *             [--temporal [MAXHIST]]   (with --events: the view carries its displayed frame across camera
+ *              moves (ProgressiveViewHIP::setTemporal, history capped at MAXHIST frames, default 32), with or
+ *              without --denoise: --frames-out holds what it shows, --raw-frames-out and --features-out as above)
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -101,7 +104,7 @@ int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
-                         "[--device K] [--denoise [ITER]] [--denoised f] [--denoised-pfm f] [--features-out f] "
+                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
@@ -134,7 +137,8 @@ bool share_comm_id(const std::string &path, int rank, uint8_t id[RT_COMM_ID_BYTE
 int main(int argc, char **argv)
 {
     std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out;
-    bool denoise = false;
+    bool denoise = false, temporal = false;
+    rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
     rt_denoise_params den_params = RayTracerHIP::denoiseDefaults();
     unsigned W = 512, H = 512, frames = 1, sr = 1, depth = 6, n_tris = 0, max_prog = 10000;
     int device = 0, comm_ranks = 0, comm_rank = 0;
@@ -151,6 +155,11 @@ int main(int argc, char **argv)
         if (a == "--denoise") { /* an optional pass count follows */
             denoise = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') den_params.iterations = (unsigned)std::atoi(argv[++i]);
+            continue;
+        }
+        if (a == "--temporal") { /* an optional history cap follows */
+            temporal = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') temporal_params.max_history = (float)std::atof(argv[++i]);
             continue;
         }
         if (!(v = next())) return usage();
@@ -180,6 +189,10 @@ int main(int argc, char **argv)
         else return usage();
     }
     const bool ply = scene == "ply" || n_tris > 0 || !ply_path.empty();
+    if (temporal && events.empty()) {
+        std::fprintf(stderr, "rt_render: --temporal needs --events (it carries the display across camera moves)\n");
+        return 2;
+    }
     try {
         RayTracerHIP rt(device);
         add_scene(rt, ply);
@@ -205,6 +218,7 @@ int main(int argc, char **argv)
             ProgressiveViewHIP view(rt, W, H, kernel);
             view.setProgressive(max_prog);
             if (denoise) view.setDenoise(true, den_params);
+            if (temporal) view.setTemporal(true, temporal_params);
             FILE *fo = frames_out.empty() ? nullptr : std::fopen(frames_out.c_str(), "wb");
             if (!frames_out.empty() && !fo) return 1;
             FILE *fr = raw_frames_out.empty() ? nullptr : std::fopen(raw_frames_out.c_str(), "wb");

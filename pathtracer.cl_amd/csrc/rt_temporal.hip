@@ -1,0 +1,188 @@
+/*
+ * rt_temporal.hip — temporal reprojection of the displayed frame across camera moves (gfx950).
+ *
+ *   k_reproject        per pixel of the new view: project its first-hit position into the previous
+ *                      view, gather the four bilinear taps of the previous displayed frame that lie
+ *                      on the same surface, and carry their colour and history length over
+ *   k_temporal_merge   per pixel: blend the carried history with the accumulation buffer by their
+ *                      frame counts
+ *
+ * Nothing in the reference corresponds to these kernels; their arithmetic is pinned in
+ * DESIGN.md §4.10 under the model of include/rt_math.h (no contraction, IEEE division), so that a
+ * float32 restatement reproduces every bit.  Neither touches a render's state, and neither writes
+ * any of its inputs (the merge may write its history operands in place).
+ */
+#include <hip/hip_runtime.h>
+
+#include "pathtracer_rt.h"
+#include "rt_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+/* One lane per pixel; a block covers 32 x 8 pixels as the a-trous kernels', a wave two rows of 32
+   (512-B row segments per float4 stream). */
+#define RT_TEMPORAL_BX 32
+#define RT_TEMPORAL_BY 8
+
+struct ReprojArgs {
+    const float4 *prev_col;
+    const float *prev_len;
+    const float4 *prev_feat;
+    const float4 *cur_feat;
+    float4 *out_col;
+    float *out_len;
+    /* the previous camera's position and the cofactor columns of (view, right, up): cs = right x up,
+       ca = up x view, cb = view x right; det = view . cs (rt_launch_reproject) */
+    float px, py, pz;
+    float csx, csy, csz, cax, cay, caz, cbx, cby, cbz, det;
+    uint32_t W, H;
+    float plane_tol, normal_min, max_history;
+};
+
+/* The taps are gathered straight from global memory: for the small camera moves this stage exists
+   for, neighbouring lanes project onto neighbouring pixels of the previous frame, so a wave's taps
+   share cache lines (vector L1 / L2). */
+__global__ __launch_bounds__(RT_TEMPORAL_BX *RT_TEMPORAL_BY) void k_reproject(ReprojArgs a)
+{
+    const int x = (int)(blockIdx.x * RT_TEMPORAL_BX + threadIdx.x);
+    const int y = (int)(blockIdx.y * RT_TEMPORAL_BY + threadIdx.y);
+    const int W = (int)a.W, H = (int)a.H;
+    if (x >= W || y >= H) return;
+    const size_t npx = (size_t)a.W * a.H, p = (size_t)y * a.W + x;
+    const float4 pp = a.cur_feat[p], np = a.cur_feat[npx + p];
+    const int idp = __float_as_int(np.w);
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f, ol = 0.0f;
+    if (idp != RT_FEAT_NONE && a.det != 0.0f) {
+        /* P - position = s (view + a right + b up): Cramer, s = ns / det, a = na / ns, b = nb / ns */
+        const float dx = pp.x - a.px, dy = pp.y - a.py, dz = pp.z - a.pz;
+        const float ns = (dx * a.csx + dy * a.csy) + dz * a.csz;
+        const float na = (dx * a.cax + dy * a.cay) + dz * a.caz;
+        const float nb = (dx * a.cbx + dy * a.cby) + dz * a.cbz;
+        const float s = ns / a.det;
+        if (s > 0.0f) { /* in front of the previous camera (false for a NaN) */
+            const float fx = ((na / ns) + ((float)a.W) / 2.0f) - 0.5f;
+            const float fy = ((nb / ns) + ((float)a.H) / 2.0f) - 0.5f;
+            /* in float, before any conversion: false for a NaN or an infinity, and every tap of a
+               coordinate outside (-1, W) x (-1, H) is outside the frame */
+            if (fx > -1.0f && fx < (float)a.W && fy > -1.0f && fy < (float)a.H) {
+                const float x0f = floorf(fx), y0f = floorf(fy);
+                const int x0 = (int)x0f, y0 = (int)y0f; /* in [-1, W-1] x [-1, H-1] */
+                const float wx1 = fx - x0f, wy1 = fy - y0f;
+                const float wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
+                const float tol = a.plane_tol * pp.w;
+                float ax = 0.0f, ay = 0.0f, az = 0.0f, al = 0.0f, wsum = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int qx = x0 + i, qy = y0 + j;
+                        if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                        const size_t q = (size_t)qy * a.W + (size_t)qx;
+                        const float m = a.prev_len[q];
+                        if (!(m > 0.0f)) continue;
+                        const float4 nq = a.prev_feat[npx + q];
+                        const int idq = __float_as_int(nq.w);
+                        if (idq == RT_FEAT_NONE) continue;
+                        if (!((idp >= 0 && idq >= 0) || idp == idq)) continue; /* the surface class */
+                        const float4 pq = a.prev_feat[q];
+                        const float pl = ((pq.x - pp.x) * np.x + (pq.y - pp.y) * np.y) + (pq.z - pp.z) * np.z;
+                        if (!(fabsf(pl) <= tol)) continue;
+                        const float nn = (nq.x * np.x + nq.y * np.y) + nq.z * np.z;
+                        if (!(nn >= a.normal_min)) continue;
+                        const float w = (i ? wx1 : wx0) * (j ? wy1 : wy0);
+                        const float4 cq = a.prev_col[q];
+                        ax = ax + w * cq.x;
+                        ay = ay + w * cq.y;
+                        az = az + w * cq.z;
+                        al = al + w * m;
+                        wsum = wsum + w;
+                    }
+                }
+                if (wsum > 0.0f) {
+                    ox = ax / wsum;
+                    oy = ay / wsum;
+                    oz = az / wsum;
+                    const float l = al / wsum;
+                    ol = l < a.max_history ? l : a.max_history;
+                }
+            }
+        }
+    }
+    a.out_col[p] = make_float4(ox, oy, oz, 0.0f);
+    a.out_len[p] = ol;
+}
+
+/* out = h + (c - h) (n / (n + m)) where the history is m > 0 frames long, c's bits elsewhere; h, m
+   and the outputs may be the same buffers (each lane reads its pixel before it writes it). */
+__global__ __launch_bounds__(256) void k_temporal_merge(const float4 *hist, const float *hist_len, const float4 *cur,
+                                                        float n, float max_history, float4 *out, float *out_len,
+                                                        uint32_t npx)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= npx) return;
+    const float4 c = cur[p];
+    const float m = hist_len[p];
+    float4 o = c;
+    float l = n;
+    if (m > 0.0f) {
+        const float4 h = hist[p];
+        l = n + m;
+        const float f = n / l;
+        o.x = h.x + (c.x - h.x) * f;
+        o.y = h.y + (c.y - h.y) * f;
+        o.z = h.z + (c.z - h.z) * f;
+    }
+    out[p] = o;
+    out_len[p] = l < max_history ? l : max_history;
+}
+
+} // namespace
+
+int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &cam,
+                        const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H, float plane_tol,
+                        float normal_min, float max_history, void *stream)
+{
+    ReprojArgs a;
+    a.prev_col = reinterpret_cast<const float4 *>(prev_rgba);
+    a.prev_len = prev_len;
+    a.prev_feat = reinterpret_cast<const float4 *>(prev_feat);
+    a.cur_feat = reinterpret_cast<const float4 *>(cur_feat);
+    a.out_col = reinterpret_cast<float4 *>(out_rgba);
+    a.out_len = out_len;
+    const rt_float4 &v = cam.view, &r = cam.right, &u = cam.up;
+    a.px = cam.position.x;
+    a.py = cam.position.y;
+    a.pz = cam.position.z;
+    /* cross(a, b) = (ay bz - az by, az bx - ax bz, ax by - ay bx), each product and difference rounded */
+    a.csx = r.y * u.z - r.z * u.y;
+    a.csy = r.z * u.x - r.x * u.z;
+    a.csz = r.x * u.y - r.y * u.x;
+    a.cax = u.y * v.z - u.z * v.y;
+    a.cay = u.z * v.x - u.x * v.z;
+    a.caz = u.x * v.y - u.y * v.x;
+    a.cbx = v.y * r.z - v.z * r.y;
+    a.cby = v.z * r.x - v.x * r.z;
+    a.cbz = v.x * r.y - v.y * r.x;
+    a.det = (v.x * a.csx + v.y * a.csy) + v.z * a.csz;
+    a.W = W;
+    a.H = H;
+    a.plane_tol = plane_tol;
+    a.normal_min = normal_min;
+    a.max_history = max_history;
+    const dim3 grid((W + RT_TEMPORAL_BX - 1) / RT_TEMPORAL_BX, (H + RT_TEMPORAL_BY - 1) / RT_TEMPORAL_BY);
+    const dim3 block(RT_TEMPORAL_BX, RT_TEMPORAL_BY);
+    hipLaunchKernelGGL(k_reproject, grid, block, 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream)
+{
+    const uint32_t npx = W * H; /* < 2^28 (the host's frame check) */
+    hipLaunchKernelGGL(k_temporal_merge, dim3((npx + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4 *>(hist_rgba), hist_len, reinterpret_cast<const float4 *>(cur_rgba),
+                       n_cur, max_history, reinterpret_cast<float4 *>(out_rgba), out_len, npx);
+    return (int)hipGetLastError();
+}

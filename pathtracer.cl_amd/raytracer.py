@@ -314,6 +314,68 @@ class RayTracer:
         self._check(self._lib.rt_last_denoise_ms(self._h, ctypes.byref(ms)), "rt_last_denoise_ms")
         return ms.value
 
+    # ---- temporal reprojection of the displayed frame (pathtracer_rt.h) ----
+    def reprojectDefaults(self) -> dict:
+        prm = _abi.RtReprojectParams()
+        self._check(self._lib.rt_reproject_defaults(ctypes.byref(prm)), "rt_reproject_defaults")
+        return dict(plane_tol=prm.plane_tol, normal_min=prm.normal_min, max_history=prm.max_history)
+
+    def reproject(self, prev_rgba, prev_len, prev_feat, prev_cam, cur_feat, out_rgba, out_len, width: int, height: int,
+                  plane_tol: float = 0.01, normal_min: float = 0.9, max_history: float = 32.0, stream=None,
+                  sync: bool = True) -> None:
+        """Carry the previous view's displayed frame `prev_rgba` with its per-pixel history lengths
+        `prev_len` (W*H floats), features `prev_feat` and Camera `prev_cam` (16 floats, getCamera)
+        over to the view whose features are `cur_feat`: `out_rgba`, `out_len`.  The six buffers are
+        all numpy arrays or all torch CUDA tensors; the inputs are only read."""
+        px = int(width) * int(height)
+        need = [(prev_rgba, 4, "previous frame"), (prev_len, 1, "previous history lengths"),
+                (prev_feat, 8, "previous feature buffer"), (cur_feat, 8, "feature buffer"),
+                (out_rgba, 4, "destination frame"), (out_len, 1, "destination history lengths")]
+        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
+        if len(set(flags)) != 1:
+            raise ValueError("reproject: the buffers must all be host arrays or all device tensors")
+        cam = np.ascontiguousarray(prev_cam, np.float32)
+        if cam.size != _abi.CAMERA_FLOATS:
+            raise ValueError(f"prev_cam holds {cam.size} floats, {_abi.CAMERA_FLOATS} needed")
+        prm = _abi.RtReprojectParams(float(plane_tol), float(normal_min), float(max_history))
+        args = (self._h, _abi.ptr(prev_rgba), _abi.ptr(prev_len), _abi.ptr(prev_feat), _abi.ptr(cam), _abi.ptr(cur_feat),
+                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags[0])
+        if sync and stream is None:
+            self._check(self._lib.rt_reproject(*args), "rt_reproject")
+        else:
+            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
+            self._check(self._lib.rt_reproject_async(*args, sp), "rt_reproject_async")
+            if sync:
+                self.synchronize()
+
+    def temporalMerge(self, hist_rgba, hist_len, cur_rgba, n_cur: float, out_rgba, out_len, width: int, height: int,
+                      max_history: float = 32.0, stream=None, sync: bool = True) -> None:
+        """Blend the carried history (`hist_rgba`, `hist_len`) with the accumulation buffer `cur_rgba`
+        of `n_cur` = max(progression, 1) frames into `out_rgba`, `out_len` (may be the history's
+        buffers); all numpy arrays or all torch CUDA tensors.  `cur_rgba` is only read."""
+        px = int(width) * int(height)
+        need = [(hist_rgba, 4, "history frame"), (hist_len, 1, "history lengths"), (cur_rgba, 4, "current frame"),
+                (out_rgba, 4, "destination frame"), (out_len, 1, "destination history lengths")]
+        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
+        if len(set(flags)) != 1:
+            raise ValueError("temporalMerge: the buffers must all be host arrays or all device tensors")
+        args = (self._h, _abi.ptr(hist_rgba), _abi.ptr(hist_len), _abi.ptr(cur_rgba), float(n_cur), float(max_history),
+                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), flags[0])
+        if sync and stream is None:
+            self._check(self._lib.rt_temporal_merge(*args), "rt_temporal_merge")
+        else:
+            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
+            self._check(self._lib.rt_temporal_merge_async(*args, sp), "rt_temporal_merge_async")
+            if sync:
+                self.synchronize()
+
+    def lastReprojectMs(self, merge: bool = False) -> float:
+        """Device time of the last reprojection kernel, or (merge=True) of the last merge kernel, ms."""
+        ms = ctypes.c_float()
+        a, b = (None, ctypes.byref(ms)) if merge else (ctypes.byref(ms), None)
+        self._check(self._lib.rt_last_reproject_ms(self._h, a, b), "rt_last_reproject_ms")
+        return ms.value
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
