@@ -23,9 +23,9 @@ int rt_exception_status(std::string *err) noexcept;
     catch (...) { return rt_exception_status(err_ptr); }
 
 /* Traversal stack entries per lane kept in LDS (20 x 256 lanes x 4 B = 20 KB per block, which
-   with k_tris's other per-lane LDS — pixel sum and throughput, list word, hit normal: 31,232 B
-   per block in all — keeps 5 blocks per CU; one block more of LDS measured 3.5 % slower:
-   profiles/r03z, r03zb); deeper entries go to a per-lane global spill tail sized from the tree
+   with k_tris's other per-lane LDS — pixel sum and throughput, list word, hit normal, the shadow
+   cache's 16-bit word: 31,744 B per block in all — keeps 5 blocks per CU; one block more of LDS
+   measured 3.5 % slower: profiles/r03z, r03zb); deeper entries go to a per-lane global spill tail sized from the tree
    (rt_host.cpp spill_cap). */
 #ifndef RT_STACK_DEPTH
 #define RT_STACK_DEPTH 20
@@ -245,6 +245,10 @@ struct RtTriLaunch {
        every segment; the chunk tasks answer the closest-hit queries above it (box segments: no
        triangle accepted) without a traversal.  NULL: every query traverses. */
     uint8_t *split_hit_depth;
+    /* the shadow cache's cut (rt_traverse.h ShadowCut): the nodes of one level of the shadow queries'
+       tree, [lo, hi) — breadth-first numbering makes a level an index range; lo = hi = 0: no cache
+       (RT_SHADOW_CACHE=0, a tree without that level, traversal kinds other than BVH4Q) */
+    uint32_t shadow_cut_lo, shadow_cut_hi;
 };
 enum { RT_SPLIT_ALL = 0, RT_SPLIT_MESH = 1, RT_SPLIT_BOX = 2 };
 /* k_split_finish parts: every pixel; a list's pixels (split_box: the long chains, the repaired); the mesh

@@ -32,6 +32,13 @@
 #define RT_DIAG_RAYSPLIT 0 /* diagnostics build: counting launches sum the stepping loop's steps of shadow rays
                               from mesh hits / shadow rays from the box / camera rays into counters 10 / 11 / 12 */
 #endif
+#ifndef RT_DIAG_SHCACHE
+#define RT_DIAG_SHCACHE 0 /* diagnostics build: counting launches sum the shadow cache's tries / the tries that
+                             answered (rt_traverse.h ShadowCut) into counters 10 / 11 */
+#endif
+#ifndef RT_NO_SHADOW_CACHE
+#define RT_NO_SHADOW_CACHE 0 /* A/B build: k_tris without the shadow cache's code (RT_SHADOW_CACHE=0 only empties the cut) */
+#endif
 #ifndef RT_DIAG_MIX
 #define RT_DIAG_MIX 0 /* diagnostics build (profiles/step_mix.py): counting launches report the stepping
                          rounds' wave-step mix in the per-pixel-maximum counters */
@@ -160,7 +167,7 @@ __device__ __forceinline__ void flush_counters(unsigned long long *dst, const un
     }
     if (with_trav) /* per-pixel maxima (RT_DIAG_MIX builds: the wave-step mix, summed) */
         for (int i = RT_N_SUM_COUNTERS; i < RT_N_COUNTERS; ++i) {
-            if (RT_DIAG_MIX || RT_DIAG_RAYSPLIT) atomicAdd(&dst[i], v[i]);
+            if (RT_DIAG_MIX || RT_DIAG_RAYSPLIT || RT_DIAG_SHCACHE) atomicAdd(&dst[i], v[i]);
             else atomicMax(&dst[i], v[i]);
         }
 }
@@ -1268,12 +1275,17 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
     __shared__ float s_state[6 * RT_BLOCK];
     /* the lane's pixel's candidate list (list_pack), read when it takes the pixel instead of before
        every camera ray (LDS budget: 5 blocks per CU beside the RT_STACK_DEPTH = 20-entry stack and
-       the hit normal: 31,232 B per block) */
+       the hit normal: 31,232 B per block, 31,744 B with the shadow cache's words below) */
     __shared__ uint32_t s_list[RT_BLOCK];
     /* the closest hit's unnormalised normal, formed at its accept from the record in registers
        (trav_step_q), so the path advance needs no second fetch of the hit's edges */
     __shared__ float s_hn[3 * RT_BLOCK];
     lds_float *const st_hn = (lds_float *)(s_hn + threadIdx.x);
+    /* the shadow cache (rt_traverse.h ShadowCut): the cut node this pixel's last occluded shadow query
+       from a mesh hit went through (0: none); 512 B, which the 5 blocks per CU still hold */
+    __shared__ uint16_t s_entry[RT_NO_SHADOW_CACHE ? 1 : RT_BLOCK];
+    lds_u16 *const st_entry = (lds_u16 *)(s_entry + (RT_NO_SHADOW_CACHE ? 0 : threadIdx.x));
+    if (!RT_NO_SHADOW_CACHE) *st_entry = 0;
     float *const st_acc = s_state + threadIdx.x, *const st_prop = s_state + 3 * RT_BLOCK + threadIdx.x;
 #define ACC_GET(k) st_acc[(k) * RT_BLOCK]
 #define ACC_SET(k, v) (st_acc[(k) * RT_BLOCK] = (v))
@@ -1336,6 +1348,8 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
        queries above it meet only the box); 0 otherwise */
     int hit_depth = 0;
     bool fin = false;     /* the lane's query completed: ts.best / ts.best_t hold its result */
+    const ShadowCut sc_cut = {a.shadow_cut_lo, RT_NO_SHADOW_CACHE ? 0u : a.shadow_cut_hi - a.shadow_cut_lo,
+                              (int)a.shadow_root};
     TravState ts;
     ts.node = 0;
     ts.best = -1;
@@ -1415,6 +1429,9 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
             } else {
                 ++cnt[1];
                 if (COUNT || RT_PLAIN_PIXEL_STATS) ++pix_q;
+                /* the shadow cache: an unoccluded answer from a mesh hit (-1, from the full traversal;
+                   not the -2 of a ray answered without one) leaves the pixel no cut node to start at */
+                if (!RT_NO_SHADOW_CACHE && tri_hit && ts.best == -1) *st_entry = 0;
                 if (ts.best < 0) { /* unoccluded: rtcommon.h:93-101 */
                     const float cw = qd.x * hn.x + qd.y * hn.y + qd.z * hn.z;
                     if (cw > 0) {
@@ -1555,7 +1572,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         ps[6] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_c >> 6) : 0u;
                         ps[7] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_it : 0u;
                     }
-                    if (COUNT && !RT_DIAG_MIX && !RT_DIAG_RAYSPLIT) {
+                    if (COUNT && !RT_DIAG_MIX && !RT_DIAG_RAYSPLIT && !RT_DIAG_SHCACHE) {
                         const unsigned long long dt = wave_clock() - pix_t0;
                         cnt[10] = dt > cnt[10] ? dt : cnt[10];
                         cnt[11] = pix_q > cnt[11] ? pix_q : cnt[11];
@@ -1581,7 +1598,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
         const bool redo = (issued && !need_trav) || known_miss || off_mesh;
         if (!__any(redo)) break;
         if (redo) {
-            ts.best = -1;
+            ts.best = -2; /* no hit, without a traversal */
             fin = true;
             ++cnt[RT_CNT_SKIPPED];
         }
@@ -1645,6 +1662,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         take = take && (x >> 3) == (dx >> 3) && (yl >> 3) == (dy >> 3) && ((in - in0) & 63u) < a.diag_k;
                     }
                     if (take) s_list[threadIdx.x] = list_pack(a, x, yl, tiles_x);
+                    if (!RT_NO_SHADOW_CACHE && take) *st_entry = 0; /* a pixel's (a chunk's) cache is its own */
                     if (SPLIT && take && a.split_spec && a.split_which == RT_SPLIT_MESH) {
                         /* a speculated mesh pixel: the chunk's first seed jumped ahead from the
                            frame seed (split_spec_draws numbers per sample before it) */
@@ -1745,12 +1763,20 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                     (SPLIT && !shadow && (int)depth < hit_depth) || /* a long chain's box segment */
                     (!SPLIT && a.mesh_bounds && !tri_hit && (shadow || depth > 0) && /* (short frames: never split) */
                      segment_misses_box(qo, qd, RT_SMALL_F, qt, a.mesh_lo, a.mesh_hi))) { /* off the mesh */
-                    ts.best = -1;
+                    ts.best = -2; /* no hit, without a traversal */
                     fin = true;
                     ++cnt[RT_CNT_SKIPPED];
                 } else {
                     trav_begin(ts, stk, qo, qd, qt);
                     if (shadow) ts.node = (int)a.shadow_root; /* the shadow queries' tree */
+                    if (shadow && tri_hit && sc_cut.n) { /* a try under the cached cut node; the root on its failure */
+                        const uint32_t e = *st_entry;
+                        if (e) {
+                            ts.node = (int)(sc_cut.lo + e - 1u);
+                            ts.best = RT_SC_TRYING;
+                            if (COUNT && RT_DIAG_SHCACHE) ++cnt[10];
+                        }
+                    }
                     running = true;
                     if (!shadow && depth == 0) { /* a camera ray: the pixel's candidate list */
                         const uint32_t lpack = s_list[threadIdx.x];
@@ -1798,10 +1824,13 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                     if (running) {
                         const bool shadow = (mode == M_SHADOW);
                         TravCounts tc = {0u, 0u, 0u};
+                        const bool sc_try = COUNT && RT_DIAG_SHCACHE && ts.best == RT_SC_TRYING;
                         if (trav_step<TRAV, COUNT>(nodes, tris, ts, stk, qo, qd, RT_SMALL_F, shadow, tc,
-                                                   shadow && tri_hit, st_hn)) {
+                                                   shadow && tri_hit, st_hn, RT_NO_SHADOW_CACHE ? nullptr : st_entry,
+                                                   sc_cut)) {
                             running = false;
                             fin = true;
+                            if (COUNT && RT_DIAG_SHCACHE && sc_try) ++cnt[11]; /* (a try only ends a query occluded) */
                         }
                         if (COUNT) {
                             cnt[2] += tc.nodes;

@@ -300,15 +300,41 @@ __device__ __forceinline__ int node_children(uint4 q0, uint4 q1, uint4 q2, uint4
     return nhit;
 }
 
+/* The shadow cache.  An any-hit answer is existential: an accepted triangle
+   found in ANY subtree makes the ray occluded, whatever the full traversal would have met first,
+   and `best` of such a query is only read as a flag.  So a lane keeps the node of one tree level
+   (the cut: the nodes are numbered breadth-first, so a level is an index range [lo, lo + n))
+   that its last occluded shadow query from a mesh hit entered last, and the pixel's next such
+   query starts there instead of at the root (a try: `best` = RT_SC_TRYING until a hit); when that
+   subtree holds no occluder the step that finds the stack empty restarts the query at the root,
+   so an unoccluded answer always comes from the full traversal.
+   The lane's word: 0 none, else the cut node's index in its level + 1 — 16 bits in LDS, written
+   by the step under the lanes that enter the cut, so the stepping loop carries no register for
+   it (k_tris clears it in the path advance, when such a query ends unoccluded).  Culling only:
+   same frames, fewer steps.  n = 0: no cache. */
+struct ShadowCut {
+    uint32_t lo, n; /* the cut level's nodes (n <= 0xffff) */
+    int root;       /* the shadow queries' root */
+};
+#define RT_SC_TRYING (-3) /* TravState::best of a try (any negative value: no hit yet) */
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(3))) uint16_t lds_u16;
+#else
+typedef uint16_t lds_u16;
+#endif
+
 /* One step of the compressed 4-wide traversal (rt_quant.h).  Every lane fetches
    exactly one 64-B record per step — a node, or ONE triangle of its current leaf —
    with the same three dwordx4 loads, so a wave-step costs one memory round trip
    whatever mix of node and leaf lanes it holds (a leaf of k triangles takes k
-   steps; the leaf cursor is the leaf code itself: first slot and remaining count). */
+   steps; the leaf cursor is the leaf code itself: first slot and remaining count).
+   `sc` (k_tris): the lane's shadow-cache word, for its `longest` queries (any hit, from a mesh
+   hit) — see ShadowCut. */
 template <bool COUNT>
 __device__ __forceinline__ bool trav_step_q(const float4 *__restrict__ nodes, const float4 *__restrict__ tris,
                                             TravState &s, Stack &stk, V3 o, V3 d, float tmin, bool any_hit,
-                                            TravCounts &cnt, bool longest = false, lds_float *hn_out = nullptr)
+                                            TravCounts &cnt, bool longest = false, lds_float *hn_out = nullptr,
+                                            lds_u16 *sc = nullptr, ShadowCut cut = ShadowCut{0u, 0u, 0})
 {
     const V3 inv = s.inv, oi = s.oi;
     const int node = s.node;
@@ -381,6 +407,10 @@ __device__ __forceinline__ bool trav_step_q(const float4 *__restrict__ nodes, co
         }
     } else {
         if (COUNT) cnt.nodes++;
+        if (sc && longest) { /* the cut node this descent is under */
+            const uint32_t r = (uint32_t)node - cut.lo;
+            if (r < cut.n) *sc = (uint16_t)(r + 1u);
+        }
         float t[4];
         int c[4];
         const int nhit = node_children(q0, q1, q2, q3, inv, oi, d, s.best_t, any_hit, longest, t, c);
@@ -404,7 +434,15 @@ __device__ __forceinline__ bool trav_step_q(const float4 *__restrict__ nodes, co
             return false;
         }
     }
-    if (stk.sp == 0) return true;
+    if (stk.sp == 0) {
+        if (sc && s.best == RT_SC_TRYING) { /* no occluder under the cached node: the full traversal, from
+                                               the next step on (tmax unchanged) */
+            s.best = -1;
+            s.node = cut.root;
+            return false;
+        }
+        return true;
+    }
     if (lds_only) s.node = stk.lds[--stk.sp * RT_BLOCK];
     else s.node = stk.pop();
     return false;
@@ -419,10 +457,11 @@ __device__ __forceinline__ bool trav_step_q(const float4 *__restrict__ nodes, co
 template <int TRAV, bool COUNT>
 __device__ __forceinline__ bool trav_step(const float4 *__restrict__ nodes, const float4 *__restrict__ tris,
                                           TravState &s, Stack &stk, V3 o, V3 d, float tmin, bool any_hit,
-                                          TravCounts &cnt, bool longest = false, lds_float *hn_out = nullptr)
+                                          TravCounts &cnt, bool longest = false, lds_float *hn_out = nullptr,
+                                          lds_u16 *sc = nullptr, ShadowCut cut = ShadowCut{0u, 0u, 0})
 {
     if (TRAV == RT_TRAV_BVH4Q)
-        return trav_step_q<COUNT>(nodes, tris, s, stk, o, d, tmin, any_hit, cnt, longest, hn_out);
+        return trav_step_q<COUNT>(nodes, tris, s, stk, o, d, tmin, any_hit, cnt, longest, hn_out, sc, cut);
     const float tmin_c = -1e-3f;
     const V3 inv = s.inv, oi = s.oi;
     int node = s.node;

@@ -8,6 +8,11 @@
 //   g++ -O2 -std=c++17 -I include -I pathtracer.cl_amd/csrc scripts/sim_pixel_paths.cpp \
 //       pathtracer.cl_amd/csrc/rt_bvh.cpp -L pathtracer.cl_amd -lrtmi -Wl,-rpath,$PWD/pathtracer.cl_amd -o /tmp/simp
 //   /tmp/simp X Y [samples]        (pixel of the 1920x1080 frame)
+//   /tmp/simp sweep [pixels] [samples] [tree]
+//       the shadow cache: over a strided sample of mesh pixels, the steps of the
+//       shadow queries from camera hits without the cache and with it at cuts 4 to 8, on the
+//       lights' tree (tree = 1, the default: built as rt_set_mesh builds it) or the closest-hit
+//       tree (0), with the kernel's cull (7) and any-hit order (5)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -35,6 +40,11 @@ static const uint32_t *g_q4; /* compressed nodes: the kernel's own cull (mode 7)
 static long g_node_steps, g_tri_steps; /* of all queries */
 static long g_near[2], g_far[2];         /* shadow-query steps entered within / beyond t = 0.05 (node, tri) */
 static bool g_track;
+/* the shadow cache: the tree level (depth) that is the cut, each node's depth in the tree the
+   shadow queries walk, and the cut node a query last entered (-1: none) */
+static int g_cut = 0;
+static std::vector<int> g_depth;
+static int g_cand = -1;
 static bool g_from_mesh; /* the shadow query leaves a mesh hit */
 static bool g_backface; /* ... a back face (the closest-hit ray met the triangle from behind) */
 static float g_tmin_shadow = -1e-3f; /* experiment: node-cull tmin of shadow rays leaving the mesh */
@@ -102,7 +112,7 @@ static bool mt(const float *tr, V o, V d, float &t)
 static const float *g_bin; /* the host's binary tree (16 floats per node) */
 static int g_wide = 0;      /* > 0: traverse an n-wide collapse of it (query_wide) */
 static long query_wide(V o, V d, float tmax, bool any, float &t_hit, int &hit);
-static long query(V o, V d, float tmax, bool any, float &t_hit, int &hit)
+static long query(V o, V d, float tmax, bool any, float &t_hit, int &hit, int start = 0)
 {
     if (g_wide) return query_wide(o, d, tmax, any, t_hit, hit);
     V inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
@@ -110,13 +120,17 @@ static long query(V o, V d, float tmax, bool any, float &t_hit, int &hit)
         int c;
         float tn;
     };
-    std::vector<It> st{{0, 0.0f}};
+    std::vector<It> st{{start, 0.0f}};
     float best = tmax;
     hit = -1;
     long steps = 0;
     while (!st.empty()) {
         It it = st.back();
         st.pop_back();
+        if (g_cut && it.c >= 0) { /* nodes above the cut clear the candidate, a node of the cut becomes it */
+            if (g_depth[it.c] < g_cut) g_cand = -1;
+            else if (g_depth[it.c] == g_cut) g_cand = it.c;
+        }
         if (g_track) (it.tn < 0.05f ? g_near : g_far)[it.c >= 0 ? 0 : 1] += it.c >= 0 ? 1 : ((~it.c) & 7) + 1;
         if (it.c >= 0) {
             ++steps;
@@ -341,8 +355,121 @@ static V frame_dir(V n, float r1, float r2) /* cosine-weighted about n */
     return norm(add(add(mul(t, std::cos(ph) * st), mul(b, std::sin(ph) * st)), mul(n, ct)));
 }
 
+/* The shadow cache over a strided sample of mesh pixels: per pixel one `entry` per cut; a query
+   starts at it when set and restarts at the root (entry dropped) when its subtree holds no
+   occluder; an occluded answer stores the cut node it was found under, an unoccluded one none. */
+static int sweep(int argc, char **argv)
+{
+    const uint32_t W = 1920, H = 1080, n_tris = 871414;
+    const int want = argc > 2 ? atoi(argv[2]) : 200, spp = argc > 3 ? atoi(argv[3]) : 256;
+    const int which = argc > 4 ? atoi(argv[4]) : 1;
+    std::vector<float> verts(3ull * rt_mesh_vertex_count(n_tris));
+    std::vector<int32_t> idx(3ull * n_tris);
+    rt_make_mesh(n_tris, 0.0f, -2.2f, 0.0f, 2.5f, verts.data(), idx.data());
+    const V light{0, 4, 2};
+    RtBvh bvh, sb;
+    std::string err;
+    bvh.light_cost_weight = 0.0f;
+    if (!rt_build_bvh(verts.data(), (uint32_t)(verts.size() / 3), idx.data(), n_tris, bvh, err)) return 1;
+    sb.light_centres = {light.x, light.y, light.z};
+    if (!rt_build_bvh(verts.data(), (uint32_t)(verts.size() / 3), idx.data(), n_tris, sb, err)) return 1;
+    const RtBvh &sh = which ? sb : bvh;
+    auto use = [](const RtBvh &t) {
+        g_n4 = t.nodes4.data();
+        g_tris = t.tris.data();
+        g_q4 = t.nodes4q.data();
+    };
+    /* depths of the shadow queries' tree (breadth-first numbering: children after parents) */
+    g_depth.assign(sh.n_nodes4, 0);
+    int max_depth = 0;
+    for (uint32_t i = 0; i < sh.n_nodes4; ++i)
+        for (int k = 0; k < 4; ++k) {
+            int c;
+            memcpy(&c, &sh.nodes4[32ull * i + 24 + k], 4);
+            if (c >= 0 && c != RT_EMPTY_CHILD) g_depth[c] = g_depth[i] + 1, max_depth = std::max(max_depth, g_depth[c]);
+        }
+    g_det_cull = 7;
+    g_order = 5;
+    float cam[16];
+    rt_camera_spherical(0, -4, 0, 40, 105, 5, 53, W, reinterpret_cast<rt_camera *>(cam));
+    const V view{cam[0], cam[1], cam[2]}, up{cam[4], cam[5], cam[6]}, right{cam[8], cam[9], cam[10]},
+        pos{cam[12], cam[13], cam[14]};
+    std::mt19937 rng(11);
+    std::uniform_real_distribution<float> U(0, 1);
+    constexpr int kCuts = 5, kCut0 = 4;
+    /* [0]: no cache, [1 + j]: cut kCut0 + j; by answer: unoccluded / occluded */
+    double steps[1 + kCuts][2] = {}, n_q[2] = {}, tried[kCuts] = {}, answered[kCuts] = {};
+    int pixels = 0;
+    for (int stride = 64; pixels < want && stride >= 8; stride /= 2)
+        for (int py = stride / 2; py < (int)H && pixels < want; py += stride)
+            for (int px = stride / 2; px < (int)W && pixels < want; px += stride) {
+                float t;
+                int hit;
+                use(bvh);
+                g_cut = 0;
+                query(pos, norm(add(add(view, mul(right, px + 0.5f - W / 2.0f)), mul(up, py + 0.5f - H / 2.0f))), 1e30f,
+                      false, t, hit);
+                if (hit < 0) continue;
+                ++pixels;
+                int entry[kCuts];
+                for (int j = 0; j < kCuts; ++j) entry[j] = -1;
+                for (int s = 0; s < spp; ++s) {
+                    const V d = norm(add(add(view, mul(right, px + U(rng) - W / 2.0f)), mul(up, py + U(rng) - H / 2.0f)));
+                    use(bvh);
+                    g_cut = 0;
+                    query(pos, d, 1e30f, false, t, hit);
+                    const float r1 = U(rng), r2 = U(rng);
+                    if (hit < 0) continue;
+                    const V p = add(pos, mul(d, t));
+                    const float *tr = g_tris + 12 * hit;
+                    const V n = norm(cross(V{tr[8], tr[9], tr[10]}, V{tr[4], tr[5], tr[6]}));
+                    const V so = add(p, mul(n, 1e-4f));
+                    const V ld = norm(sub(add(light, V{r1 * 0.5f - 0.25f, r2 * 0.5f - 0.25f, 0}), so));
+                    if (!(dot(ld, n) > 0)) continue;
+                    const float tl = std::sqrt(dot(sub(light, so), sub(light, so))) - 0.5f;
+                    use(sh);
+                    g_from_mesh = true;
+                    int h2;
+                    float t2;
+                    const long k0 = query(so, ld, tl, true, t2, h2);
+                    const int occ = h2 >= 0;
+                    n_q[occ] += 1;
+                    steps[0][occ] += k0;
+                    for (int j = 0; j < kCuts; ++j) {
+                        g_cut = kCut0 + j;
+                        long k = 0;
+                        int hc = -1;
+                        if (entry[j] >= 0) {
+                            tried[j] += 1;
+                            k += query(so, ld, tl, true, t2, hc, entry[j]);
+                            if (hc >= 0) answered[j] += 1;
+                        }
+                        if (hc < 0) {
+                            g_cand = -1;
+                            k += query(so, ld, tl, true, t2, hc);
+                            entry[j] = hc >= 0 ? g_cand : -1;
+                        }
+                        if ((hc >= 0) != (h2 >= 0)) printf("MISMATCH any-hit at cut %d\n", g_cut);
+                        steps[1 + j][occ] += k;
+                    }
+                    g_cut = 0;
+                }
+            }
+    printf("%s tree (depth %d), %d mesh pixels x %d samples: %.0f shadow queries from camera hits, %.1f%% occluded\n",
+           which ? "lights'" : "closest-hit", max_depth, pixels, spp, n_q[0] + n_q[1], 100 * n_q[1] / (n_q[0] + n_q[1]));
+    printf("| cut | occluded | unoccluded | all | tried | answered | steps saved |\n|---|---|---|---|---|---|---|\n");
+    const double all0 = steps[0][0] + steps[0][1], nq = n_q[0] + n_q[1];
+    printf("| none | %.1f | %.1f | %.1f | | | |\n", steps[0][1] / n_q[1], steps[0][0] / n_q[0], all0 / nq);
+    for (int j = 0; j < kCuts; ++j)
+        printf("| %d | %.1f | %.1f | %.1f | %.0f | %.0f | %.1f %% |\n", kCut0 + j, steps[1 + j][1] / n_q[1],
+               steps[1 + j][0] / n_q[0], (steps[1 + j][0] + steps[1 + j][1]) / nq, tried[j], answered[j],
+               100 * (1 - (steps[1 + j][0] + steps[1 + j][1]) / all0));
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "sweep")) return sweep(argc, argv);
     const uint32_t W = 1920, H = 1080, n_tris = 871414;
     const int px = argc > 1 ? atoi(argv[1]) : 1807, py = argc > 2 ? atoi(argv[2]) : 633;
     const int spp = argc > 3 ? atoi(argv[3]) : 256;
