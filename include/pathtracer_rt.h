@@ -261,6 +261,11 @@ int rt_last_render_info(rt_ctx *ctx, rt_render_info *out);
    order of their slots), the pixels whose seed pass ran on the second stream with split_coop lanes
    per query.  Copies min(cap, *n) entries; *n = pixels_long.  Diagnostics and parity tests. */
 int rt_last_long_chains(rt_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n);
+/* The camera-ray candidate lists of the last triangle render, per pixel (tile-local y * W + x): the
+   records of its list, 0 for a pixel no triangle can be hit through, 0xffff for a pixel without a
+   list (its camera rays take the tree).  Copies min(cap, *n) entries; *n = the render's pixels, 0
+   when it used no lists.  Diagnostics and parity tests. */
+int rt_last_list_counts(rt_ctx *ctx, uint16_t *out, uint32_t cap, uint32_t *n);
 
 /* ---- ray queries for hit-index parity (rtcommon.h:39-52 / :59-68 semantics).
    Host arrays; any_hit=0: out_idx = closest triangle (-1 none), out_t = its t;

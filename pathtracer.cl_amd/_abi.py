@@ -203,6 +203,7 @@ SIGNATURES = {
     "rt_last_kernel_split_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
     "rt_last_render_info": (_i32, [_vp, ctypes.POINTER(RtRenderInfo)]),
     "rt_last_long_chains": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
+    "rt_last_list_counts": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
     "rt_trace_rays": (_i32, [_vp, _vp, _u32, _i32, _vp, _vp]),
     # first-hit feature buffers and the display denoiser (csrc/rt_denoise.hip)
     "rt_get_camera": (_i32, [_vp, _u32, _vp]),

@@ -125,6 +125,15 @@ constexpr uint32_t kFetchFrac = 24;
 /* the shadow cache's default cut: the tree level whose subtrees hold one pixel's bundle of shadow
    rays best (dragon class, cuts 4 / 5 / 6: 72.6 / 71.0 / 72.4 ms against 75.6 without) */
 constexpr size_t kShadowCutDepth = 5;
+/* the inline list resolve of k_tris's phase B: the records of a pixel's candidate
+   list its camera rays are tested against where they are made (RT_INLINE_LIST, 0 to RT_INLINE_MAX;
+   0: none), and the passes of an iteration's path advance after the first that may still do so
+   (RT_INLINE_CHAIN); scheduling only.  Dragon frame, K 0 / 1 / 2 / 3 / 4 without chained rounds:
+   71.1 / 77.2 / 69.4 / 70.4 / 71.7 ms, K 2 with one / two chained rounds 74.7 / 79.9.
+   Short frames (they lose with it) and sample-split launches (not measured with it) keep K 0 unless
+   RT_INLINE_LIST is set */
+constexpr uint32_t kInlineList = 2;
+constexpr uint32_t kInlineChain = 0;
 
 /* The levels of the compressed 4-wide tree rooted at `root` as node index ranges [lo, hi), level 0
    the root (q4: every node's RT_QNODE_DWORDS, n nodes; the links are dwords 12-15).  Both builders
@@ -1814,6 +1823,11 @@ try {
         a.spill = c->d_spill;
         a.fetch_k = env_u32("RTMI_FETCH_K", kFetchK);
         a.fetch_frac = env_u32("RTMI_FETCH_FRAC", kFetchFrac);
+        /* (short frames keep K 0 by default: bunny class at 1 spp 0.425 -> 0.454 ms with K 2) */
+        a.inline_k = trav == RT_TRAV_BVH4Q
+                         ? std::min<uint32_t>(env_u32("RT_INLINE_LIST", short_frame ? 0u : kInlineList), RT_INLINE_MAX)
+                         : 0u;
+        a.inline_passes = 1u + std::min<uint32_t>(env_u32("RT_INLINE_CHAIN", kInlineChain), 8u);
         a.probe_n = probe_n(c->sample_rate);
         a.diag_pixel = 0xffffffffu;
 #if RT_DIAG_ONE_PIXEL
@@ -2058,6 +2072,7 @@ try {
                     (unsigned long long)b[3], (unsigned long long)b[4], (unsigned long long)b[5],
                     (unsigned long long)b[6], nl ? (double)sum / (double)nl : 0.0);
         }
+        if (a.split_chunks && !getenv("RT_INLINE_LIST")) a.inline_k = 0; /* (the default is the whole-pixel launches') */
         if (!e && a.split_chunks) {
             a.n_recs = (uint32_t)std::min<size_t>(c->tris_cap, 0xffffffffu); /* the list area included */
             c->last_hit_depth = false;
@@ -2324,6 +2339,22 @@ try {
     HIPCHK(c, hipMemcpy(out, c->d_split_box, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 } RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_last_list_counts(rt_ctx *c, uint16_t *out, uint32_t cap, uint32_t *n)
+try {
+    if (!c || !n || (cap && !out)) return RT_ERR_ARG;
+    *n = c->info.lists ? (uint32_t)c->info_list_px : 0u;
+    const uint32_t k = std::min(cap, *n);
+    if (!k) return RT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->d_list_code, (size_t)k * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < k; ++i)
+        out[i] = out[i] == RT_LIST_NONE ? (uint16_t)0xffffu
+                 : out[i] == RT_LIST_EMPTY ? (uint16_t)0u
+                                           : (uint16_t)((out[i] & (RT_LIST_MAX - 1u)) + 1u);
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
 
 int rt_get_counters(const rt_ctx *c, rt_counters *out)
 try {

@@ -249,7 +249,13 @@ struct RtTriLaunch {
        tree, [lo, hi) — breadth-first numbering makes a level an index range; lo = hi = 0: no cache
        (RT_SHADOW_CACHE=0, a tree without that level, traversal kinds other than BVH4Q) */
     uint32_t shadow_cut_lo, shadow_cut_hi;
+    /* the inline list resolve (k_tris phase B, BVH4Q): a new sample's camera ray is tested against the
+       first inline_k records of its pixel's candidate list where it is made (0: every camera query
+       goes to the stepping loop; at most RT_INLINE_MAX), in the first inline_passes passes of an
+       iteration's path advance (later passes hand their camera queries to the loop) */
+    uint32_t inline_k, inline_passes;
 };
+#define RT_INLINE_MAX 4
 enum { RT_SPLIT_ALL = 0, RT_SPLIT_MESH = 1, RT_SPLIT_BOX = 2 };
 /* k_split_finish parts: every pixel; a list's pixels (split_box: the long chains, the repaired); the mesh
    pixels no chunk of which missed */

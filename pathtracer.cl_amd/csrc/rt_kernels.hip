@@ -36,6 +36,10 @@
 #define RT_DIAG_SHCACHE 0 /* diagnostics build: counting launches sum the shadow cache's tries / the tries that
                              answered (rt_traverse.h ShadowCut) into counters 10 / 11 */
 #endif
+#ifndef RT_DIAG_INLINE
+#define RT_DIAG_INLINE 0 /* diagnostics build: counting launches sum the camera queries of listed pixels that k_tris's
+                            phase B resolved inline / handed to the stepping loop into counters 10 / 11 */
+#endif
 #ifndef RT_NO_SHADOW_CACHE
 #define RT_NO_SHADOW_CACHE 0 /* A/B build: k_tris without the shadow cache's code (RT_SHADOW_CACHE=0 only empties the cut) */
 #endif
@@ -167,7 +171,7 @@ __device__ __forceinline__ void flush_counters(unsigned long long *dst, const un
     }
     if (with_trav) /* per-pixel maxima (RT_DIAG_MIX builds: the wave-step mix, summed) */
         for (int i = RT_N_SUM_COUNTERS; i < RT_N_COUNTERS; ++i) {
-            if (RT_DIAG_MIX || RT_DIAG_RAYSPLIT || RT_DIAG_SHCACHE) atomicAdd(&dst[i], v[i]);
+            if (RT_DIAG_MIX || RT_DIAG_RAYSPLIT || RT_DIAG_SHCACHE || RT_DIAG_INLINE) atomicAdd(&dst[i], v[i]);
             else atomicMax(&dst[i], v[i]);
         }
 }
@@ -1264,7 +1268,9 @@ enum : int { M_IDLE = 0, M_NEWSAMPLE = 1, M_CLOSEST = 2, M_SHADOW = 3, M_DONE = 
 /* path-advance passes that may answer an off-mesh box-path query in place (0 / 1 / all: bunny class
    0.484 / 0.457 / 0.594 ms, profiles/r05ag-r05ah); later ones at the stepping round's start, without a step */
 constexpr int kOffMeshRedo = 1;
-template <int TRAV, bool COUNT, bool SPLIT = false, bool MQ = false> /* MQ: the multi-head queue (mq_take) */
+/* INL: the instantiations with the inline list resolve of phase B (BVH4Q launches with inline_k > 0);
+   the others compile to the loop without it, register for register (the kernel has none to spare) */
+template <int TRAV, bool COUNT, bool SPLIT = false, bool MQ = false, bool INL = false> /* MQ: the multi-head queue (mq_take) */
 __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
 {
     constexpr bool RESUME = TRAV == RT_TRAV_BVH4 || TRAV == RT_TRAV_BVH4Q;
@@ -1328,6 +1334,8 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
     const float mix_t = uniform_f(a.progressive > 0 ? 1.0f / (float)a.progressive : 0.0f);
     const float bw = (float)RT_BOX_WIDTH, bh = (float)RT_BOX_HEIGHT;
     const int fetch_k_all = (int)a.fetch_k;
+    const uint32_t inline_k = !INL ? 0u : a.inline_k < (uint32_t)RT_INLINE_MAX ? a.inline_k : (uint32_t)RT_INLINE_MAX;
+    const int inline_passes = INL ? (int)a.inline_passes : 0;
 
     int mode = M_IDLE;
     uint32_t x = 0, yl = 0; /* pixel column and local row (global row / seed slot derived) */
@@ -1372,6 +1380,12 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
     uint32_t qs = (blockIdx.x % RT_QHEADS) << 4;
 
     for (;;) {
+        /* INL: D, A and B run again (one copy of each, a jump back from the end of B) when B resolved
+           camera rays against their candidate lists (below), so those lanes shade and issue their
+           shadow rays before the next stepping round; round 0 is for the lanes the stepping loop
+           finished, the idle lanes and the new samples */
+        int pass = 0;
+    advance:
         const unsigned long long t_d0 = (COUNT || RT_PLAIN_PIXEL_STATS) ? wave_clock() : 0ull;
         /* ---- D: advance the path (trace_path_tri, rtcommon.h:378-468) ---- */
         for (int redo_pass = 0;; ++redo_pass) {
@@ -1572,7 +1586,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         ps[6] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_c >> 6) : 0u;
                         ps[7] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_it : 0u;
                     }
-                    if (COUNT && !RT_DIAG_MIX && !RT_DIAG_RAYSPLIT && !RT_DIAG_SHCACHE) {
+                    if (COUNT && !RT_DIAG_MIX && !RT_DIAG_RAYSPLIT && !RT_DIAG_SHCACHE && !RT_DIAG_INLINE) {
                         const unsigned long long dt = wave_clock() - pix_t0;
                         cnt[10] = dt > cnt[10] ? dt : cnt[10];
                         cnt[11] = pix_q > cnt[11] ? pix_q : cnt[11];
@@ -1608,7 +1622,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
         if (COUNT) cnt[RT_CNT_SHADE] += t_d1 - t_d0;
         if (COUNT || RT_PLAIN_PIXEL_STATS) { /* (the plain launch's phase clocks: RT_PLAIN_PIXEL_STATS builds) */
             pix_d += t_d1 - t_d0;
-            ++pix_it;
+            if (!INL || pass == 0) ++pix_it;
         }
         /* ---- A: refill idle lanes from the pixel queue (wave-private batches: one atomic per
                 64 items; bunny class 1024^2 at 1 spp 0.95 -> 0.55 ms, the dragon frame +-0.5 %) ---- */
@@ -1729,6 +1743,17 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
         /* ---- B: camera ray of a new sample (raytracer.cl:216-224; sx outer,
                 sy inner, the x draw before the y draw) ---- */
         if (mode == M_NEWSAMPLE) {
+            /* The inline list resolve (INL instantiations): the camera query of a pixel with a
+               candidate list is started here as phase C starts it, and stepped up to inline_k
+               records through the stepping loop's own step (trav_step: the one copy of the test,
+               the accept rule with its tie read-back, the hit normal and the list's early end),
+               before the wave's next stepping round.  A query that ends there — most do, DESIGN.md
+               §4.3 — never enters the loop: the lane is `fin` and the advance runs another round
+               for it; the others go on in phase C from the record they stand at. */
+            const uint32_t lpack = s_list[threadIdx.x];
+            /* (a long chain's box segment, split_hit_depth, is answered without a query as before) */
+            const bool inl = INL && TRAV == RT_TRAV_BVH4Q && inline_k && pass < inline_passes && lpack < RT_LPACK_EMPTY &&
+                             !(SPLIT && hit_depth > 0);
             const uint32_t sx = sample / a.sample_rate, sy = sample % a.sample_rate;
             const float fa = (float)x + strat_rand(seed, (int)sx, (int)a.sample_rate);
             const uint32_t y = global_row(a, yl);
@@ -1741,6 +1766,47 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
             col_x = col_y = col_z = 0.0f;
             depth = 0;
             mode = M_CLOSEST;
+            if (INL && TRAV == RT_TRAV_BVH4Q && inline_k && __any(inl)) {
+                if (inl) { /* the list as virtual leaves: its first block the cursor, the later ones stacked */
+                    const uint32_t pc = (lpack & (RT_LIST_MAX - 1u)) + 1u, first = (lpack >> RT_LIST_BITS) << 3;
+                    trav_begin(ts, stk, qo, qd, kInf);
+                    for (uint32_t b = (pc - 1u) >> 3; b > 0u; --b) {
+                        const uint32_t k = pc - 8u * b < 8u ? pc - 8u * b : 8u;
+                        stk.push(~(int)(((first + 8u * b) << 3) | (k - 1u)));
+                    }
+                    ts.node = ~(int)((first << 3) | ((pc < 8u ? pc : 8u) - 1u));
+                    running = true;
+                }
+                for (uint32_t i = 0; i < inline_k; ++i) {
+                    if (inl && running) {
+                        TravCounts tc = {0u, 0u, 0u};
+                        if (trav_step<TRAV, COUNT>(nodes, tris, ts, stk, qo, qd, RT_SMALL_F, false, tc, false, st_hn,
+                                                   RT_NO_SHADOW_CACHE ? nullptr : st_entry, sc_cut)) {
+                            running = false;
+                            fin = true;
+                            if (COUNT && RT_DIAG_INLINE) ++cnt[10];
+                        }
+                        /* steps of the pixel's measured cost and tests of a counting launch like the
+                           loop's; lane_slots (cnt[5]) stays the loop's */
+                        if (COUNT) {
+                            cnt[2] += tc.nodes;
+                            cnt[3] += tc.tests;
+                            cnt[4] += tc.leaves;
+                            pix_steps += tc.nodes + tc.leaves;
+                        } else {
+                            ++pix_steps;
+                        }
+                    }
+                    if (!__any(inl && running)) break;
+                }
+                if (COUNT && RT_DIAG_INLINE && inl && running) ++cnt[11];
+            }
+            if (COUNT && RT_DIAG_INLINE && !inl && lpack < RT_LPACK_EMPTY) ++cnt[11];
+        }
+        if (INL && __any(fin)) {
+            if (COUNT || RT_PLAIN_PIXEL_STATS) pix_ab += wave_clock() - t_d1; /* (the last round's: before phase C) */
+            ++pass;
+            goto advance;
         }
 
         /* ---- C: ray queries ---- */
@@ -2724,7 +2790,12 @@ int rt_launch_tris(const RtTriLaunch &a, int trav, bool count, int grid_blocks, 
     const bool mq = a.queue_batch && trav == RT_TRAV_BVH4Q && a.split_which != RT_SPLIT_BOX;
 #define RT_LAUNCH_TRIS(T, S)                                                                                           \
     do {                                                                                                               \
-        if (mq && count) hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, true, S, true>), grid, block, 0, st, a);            \
+        if (T == RT_TRAV_BVH4Q && a.inline_k) {                                                                        \
+            if (mq && count) hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, true, S, true, true>), grid, block, 0, st, a);  \
+            else if (mq) hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, false, S, true, true>), grid, block, 0, st, a);     \
+            else if (count) hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, true, S, false, true>), grid, block, 0, st, a);  \
+            else hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, false, S, false, true>), grid, block, 0, st, a);            \
+        } else if (mq && count) hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, true, S, true>), grid, block, 0, st, a);            \
         else if (mq) hipLaunchKernelGGL((k_tris<RT_TRAV_BVH4Q, false, S, true>), grid, block, 0, st, a);               \
         else if (count) hipLaunchKernelGGL((k_tris<T, true, S>), grid, block, 0, st, a);                               \
         else hipLaunchKernelGGL((k_tris<T, false, S>), grid, block, 0, st, a);                                         \

@@ -450,6 +450,18 @@ class RayTracer:
                         "rt_last_long_chains")
         return out
 
+    def listCounts(self) -> np.ndarray:
+        """rt_last_list_counts: per pixel of the last triangle render (tile-local y * W + x) the records
+        of its camera-ray candidate list; 0: no candidate, 0xffff: no list (the tree).  Empty when the
+        render used no lists."""
+        n = ctypes.c_uint32(0)
+        self._check(self._lib.rt_last_list_counts(self._h, None, 0, ctypes.byref(n)), "rt_last_list_counts")
+        out = np.empty(n.value, np.uint16)
+        if n.value:
+            self._check(self._lib.rt_last_list_counts(self._h, _abi.ptr(out), n.value, ctypes.byref(n)),
+                        "rt_last_list_counts")
+        return out
+
     def traceRays(self, rays: np.ndarray, any_hit: bool = False) -> tuple[np.ndarray, np.ndarray]:
         r = np.ascontiguousarray(rays, _abi.RAY_DTYPE)
         idx = np.empty(r.size, np.int32)
