@@ -42,6 +42,16 @@
  *                    accumulation buffer (then filtered, with the denoiser on).  The accumulation
  *                    buffer is only read; rawPixels() returns it.  The history is dropped at a
  *                    reshape; the scene is assumed static.  Off (the default), nothing changes.
+ *   setVarianceGuided(on, params)  (no counterpart in the reference) display the variance-guided
+ *                    filter in place of setDenoise's: the view copies the
+ *                    accumulation buffer on the device before every render that refines it, folds
+ *                    the frame's luminance into its moments after the render, estimates the variance
+ *                    of the frame about to be displayed (the accumulation buffer with the history
+ *                    length n everywhere, or with setTemporal the merged frame, whose moments are
+ *                    reprojected and merged next to the colour, with the merged lengths) and shows
+ *                    rt_denoise_var's output.  Features are rendered as with setDenoise; rawPixels()
+ *                    is unchanged; a reshape drops the moments.  Switched on in mid-accumulation,
+ *                    the moments start from the accumulated frame.  Off (the default), nothing changes.
  */
 #ifndef PROGRESSIVE_VIEW_HIP_HPP
 #define PROGRESSIVE_VIEW_HIP_HPP
@@ -140,12 +150,23 @@ public:
         temporalParams_ = params;
     }
     bool temporal() const { return temporal_; }
+    void setVarianceGuided(bool on, const rt_denoise_var_params &params = RayTracerHIP::denoiseVarDefaults())
+    {
+        if (on && !varGuided_) {
+            featDirty_ = true;
+            haveHist_ = false;
+            momValid_ = false;
+        }
+        varGuided_ = on;
+        varParams_ = params;
+    }
+    bool varianceGuided() const { return varGuided_; }
 
     const std::vector<float> &pixels() const { return pbo_; }
     /* The accumulation buffer as rendered (what pixels() holds with the denoiser off), read back now. */
     const std::vector<float> &rawPixels()
     {
-        if (!denoise_ && !temporal_) return pbo_;
+        if (!denoise_ && !temporal_ && !varGuided_) return pbo_;
         raw_.assign(pbo_.size(), 0.0f);
         if (dev_ && hipMemcpy(raw_.data(), dev_, raw_.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             throw std::runtime_error("ProgressiveViewHIP: raw frame readback failed");
@@ -175,6 +196,7 @@ private:
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
         featDirty_ = true;
         haveHist_ = false;
+        momValid_ = false;
     }
     void release()
     {
@@ -184,14 +206,19 @@ private:
         if (featPrev_) (void)hipFree(featPrev_);
         if (hist_) (void)hipFree(hist_);
         if (carried_) (void)hipFree(carried_);
+        for (float *b : {accPrev_, mom_, momHist_, momCarried_, var_, len_})
+            if (b) (void)hipFree(b);
         dev_ = den_ = feat_ = featPrev_ = hist_ = carried_ = nullptr;
+        accPrev_ = mom_ = momHist_ = momCarried_ = var_ = len_ = nullptr;
     }
     void alloc(float *&buf, size_t bytes, const char *what)
     {
         if (!buf && hipMalloc(&buf, bytes) != hipSuccess)
             throw std::runtime_error(std::string("ProgressiveViewHIP: ") + what + " allocation failed");
     }
-    void traceTemporal()
+    /* the merged frame of this display into hist_ (colour, then its plane of history lengths); with
+       setVarianceGuided the view's moments mom_ go the same way into momHist_ */
+    void mergeTemporal()
     {
         const size_t px = (size_t)width_ * height_, frame = px * 4 * sizeof(float);
         /* hist_ / carried_: a colour frame followed by its plane of history lengths */
@@ -199,7 +226,10 @@ private:
         alloc(featPrev_, 2 * frame, "feature buffer");
         alloc(hist_, frame + px * sizeof(float), "history buffer");
         alloc(carried_, frame + px * sizeof(float), "history buffer");
-        if (denoise_) alloc(den_, frame, "denoised framebuffer");
+        if (varGuided_) {
+            alloc(momHist_, frame + px * sizeof(float), "moments history buffer");
+            alloc(momCarried_, frame + px * sizeof(float), "moments history buffer");
+        }
         const rt_camera cam = rt_.getCamera(width_);
         const float *histFeat = feat_; /* the features of the view the kept frame was displayed in */
         if (featDirty_) {
@@ -210,17 +240,31 @@ private:
             carry_ = true;
         }
         if (!haveHist_) { /* after a (re)allocation: no history anywhere */
-            if (hipMemset(carried_, 0, frame + px * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+            if (hipMemset(carried_, 0, frame + px * sizeof(float)) != hipSuccess ||
+                (varGuided_ && hipMemset(momCarried_, 0, frame + px * sizeof(float)) != hipSuccess) ||
+                hipDeviceSynchronize() != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: history reset failed");
         } else if (carry_) { /* a new accumulation begins: carry the kept frame into it */
             rt_.reproject(hist_, hist_ + 4 * px, histFeat, histCam_, feat_, carried_, carried_ + 4 * px, width_, height_,
                           temporalParams_, true);
+            if (varGuided_) /* the same lengths, features and cameras: the colour's taps and weights */
+                rt_.reproject(momHist_, hist_ + 4 * px, histFeat, histCam_, feat_, momCarried_, momCarried_ + 4 * px, width_,
+                              height_, temporalParams_, true);
         }
         carry_ = false;
         rt_.temporalMerge(carried_, carried_ + 4 * px, dev_, (float)(progression_ > 1 ? progression_ : 1),
                           temporalParams_.max_history, hist_, hist_ + 4 * px, width_, height_, true);
+        if (varGuided_)
+            rt_.temporalMerge(momCarried_, momCarried_ + 4 * px, mom_, (float)(progression_ > 1 ? progression_ : 1),
+                              temporalParams_.max_history, momHist_, momHist_ + 4 * px, width_, height_, true);
         histCam_ = cam;
         haveHist_ = true;
+    }
+    void traceTemporal()
+    {
+        const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
+        if (denoise_) alloc(den_, frame, "denoised framebuffer");
+        mergeTemporal();
         const float *shown = hist_;
         if (denoise_) {
             rt_.denoise(hist_, feat_, den_, width_, height_, denoiseParams_, true);
@@ -229,10 +273,55 @@ private:
         if (hipMemcpy(pbo_.data(), shown, frame, hipMemcpyDeviceToHost) != hipSuccess)
             throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
     }
+    /* before a render that refines the accumulation buffer: its copy, for the frame's own sample */
+    void keepAccumulation()
+    {
+        const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
+        alloc(accPrev_, frame, "accumulation copy");
+        if (progression_ > 1 &&
+            (hipMemcpy(accPrev_, dev_, frame, hipMemcpyDeviceToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+            throw std::runtime_error("ProgressiveViewHIP: accumulation copy failed");
+    }
+    void traceVarianceGuided()
+    {
+        const size_t px = (size_t)width_ * height_, frame = px * 4 * sizeof(float);
+        alloc(mom_, frame, "moments buffer");
+        alloc(var_, px * sizeof(float), "variance buffer");
+        alloc(den_, frame, "denoised framebuffer");
+        /* (without valid moments, after it was switched on in mid-accumulation: start from this frame) */
+        const float n = (float)(progression_ > 1 ? progression_ : 1);
+        rt_.momentsAccumulate(accPrev_, dev_, momValid_ ? n : 1.0f, mom_, mom_, width_, height_, true);
+        momValid_ = true;
+        const float *shown = dev_, *moments = mom_, *len = nullptr;
+        if (temporal_) {
+            mergeTemporal();
+            shown = hist_;
+            moments = momHist_;
+            len = hist_ + 4 * px;
+        } else {
+            alloc(feat_, 2 * frame, "feature buffer");
+            alloc(len_, px * sizeof(float), "history length buffer");
+            if (featDirty_) {
+                rt_.renderFeatures(feat_, width_, height_, kernel_, true);
+                featDirty_ = false;
+            }
+            const std::vector<float> lens(px, n); /* one view, n frames everywhere */
+            if (hipMemcpy(len_, lens.data(), px * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: history length upload failed");
+            len = len_;
+        }
+        rt_.variance(shown, moments, len, feat_, var_, width_, height_, varParams_, true);
+        rt_.denoiseVar(shown, var_, feat_, den_, nullptr, width_, height_, varParams_, true);
+        if (hipMemcpy(pbo_.data(), den_, frame, hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
+    }
     void trace()
     {
+        if (varGuided_) keepAccumulation();
         rt_.rayTrace(dev_, width_, height_, progression_, kernel_, true);
-        if (temporal_) {
+        if (varGuided_) {
+            traceVarianceGuided();
+        } else if (temporal_) {
             traceTemporal();
         } else if (denoise_) {
             const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
@@ -267,6 +356,13 @@ private:
     bool temporal_ = false, haveHist_ = false, carry_ = false;
     rt_reproject_params temporalParams_ = RayTracerHIP::reprojectDefaults();
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
+    /* setVarianceGuided: the accumulation buffer before the frame, the view's moments, with
+       setTemporal their merged and carried histories (moments + length plane, as hist_ / carried_),
+       the variance plane and (without setTemporal) the plane of history lengths */
+    float *accPrev_ = nullptr, *mom_ = nullptr, *momHist_ = nullptr, *momCarried_ = nullptr, *var_ = nullptr,
+          *len_ = nullptr;
+    bool varGuided_ = false, momValid_ = false;
+    rt_denoise_var_params varParams_ = RayTracerHIP::denoiseVarDefaults();
     std::vector<float> pbo_, raw_;
     bool realloc_ = true, rendered_ = false;
     unsigned progression_ = 0, maxProgression_ = 10000;

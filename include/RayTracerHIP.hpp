@@ -274,6 +274,51 @@ public:
         return ms;
     }
 
+    /* ---- variance-guided display filter (pathtracer_rt.h) ---- */
+    static rt_denoise_var_params denoiseVarDefaults()
+    {
+        rt_denoise_var_params p;
+        rt_denoise_var_defaults(&p);
+        return p;
+    }
+    /* Fold the frame between the accumulation buffers prev_rgba (a copy taken before it) and cur_rgba
+       (after it, n_cur = max(progression, 1) frames) into the view's luminance moments; mom_out may
+       be mom_in; n_cur == 1 reads neither prev_rgba nor mom_in. */
+    void momentsAccumulate(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in,
+                           float *mom_out, unsigned width, unsigned height, bool on_device = false)
+    {
+        check(rt_moments_accumulate(ctx_, prev_rgba, cur_rgba, n_cur, mom_in, mom_out, width, height,
+                                    on_device ? RT_OUT_DEVICE : 0),
+              "momentsAccumulate");
+    }
+    /* The variance of the displayed luminance (one plane of W*H floats) from the moments frame, the
+       history lengths and, where those are short, the frame about to be displayed. */
+    void variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
+                  unsigned width, unsigned height, const rt_denoise_var_params &params = denoiseVarDefaults(),
+                  bool on_device = false)
+    {
+        check(rt_variance(ctx_, disp_rgba, mom_rgba, len, feat, out_var, width, height, &params,
+                          on_device ? RT_OUT_DEVICE : 0),
+              "variance");
+    }
+    /* Variance-guided a-trous filter of `in` with its variance plane into `out` (may be `in`) and
+       out_var (may be in_var, or NULL). */
+    void denoiseVar(const float *in, const float *in_var, const float *feat, float *out, float *out_var, unsigned width,
+                    unsigned height, const rt_denoise_var_params &params = denoiseVarDefaults(), bool on_device = false)
+    {
+        check(rt_denoise_var(ctx_, in, in_var, feat, out, out_var, width, height, &params, on_device ? RT_OUT_DEVICE : 0),
+              "denoiseVar");
+    }
+    /* Device time of the last moments kernel (0), variance kernel (1) or rt_denoise_var (2), ms. */
+    float lastVarianceMs(int which = 2) const
+    {
+        float ms = 0.0f;
+        check(rt_last_variance_ms(ctx_, which == 0 ? &ms : nullptr, which == 1 ? &ms : nullptr,
+                                  which == 2 ? &ms : nullptr),
+              "lastVarianceMs");
+        return ms;
+    }
+
     rt_counters counters() const
     {
         rt_counters c;

@@ -370,6 +370,60 @@ int rt_temporal_merge_async(rt_ctx *ctx, const float *hist_rgba, const float *hi
    own), ms; either pointer may be NULL.  RT_ERR_STATE when a kernel asked for has not run. */
 int rt_last_reproject_ms(const rt_ctx *ctx, float *reproject_ms, float *merge_ms);
 
+/* ---- variance-guided display filter driven by temporal luminance moments.  The
+   rules of the calls above hold: display only, no render state is changed, the accumulation buffer
+   is only read, `flags` takes RT_OUT_DEVICE only, the same stream ordering, and arithmetic that a
+   float32 restatement reproduces to the bit.  lum(c) = (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z.
+   A moments frame is an RGBA32F frame holding (mean of lum, mean of lum^2, 0, 0) over the per-frame
+   images of a view.  It is carried across views by rt_reproject and rt_temporal_merge exactly as
+   the displayed colour is (same prev_len, features and cameras: the taps, the weights and the
+   out_len are the colour's); the caller drops it on a reshape or a scene change. ---- */
+typedef struct rt_denoise_var_params {
+    uint32_t iterations; /* 1..8 */
+    float sigma_lum;     /* luminance tolerance in standard deviations; +INFINITY: the term is off */
+    float sigma_normal, sigma_plane; /* as rt_denoise_params */
+    float min_len;       /* history length from which the temporal variance estimate is used, >= 2 */
+} rt_denoise_var_params;
+int rt_denoise_var_defaults(rt_denoise_var_params *p); /* 5, 4.0f, 0.3f, 0.1f, 4.0f */
+/* After every progressive frame: cur_rgba is the accumulation buffer after the frame, prev_rgba a
+   copy of it taken before the frame, n_cur = max(progression, 1).  The frame's own sample is
+   recovered per component as s = prev + (cur - prev) n_cur, negative results to 0; L = lum(s);
+   mom_out.x = m.x + (L - m.x) f, mom_out.y = m.y + (L L - m.y) f with f = 1.0f / n_cur, mom_out.zw = 0.
+   n_cur == 1: s = cur (negative components to 0), mom_out = (L, L L, 0, 0); prev_rgba and mom_in
+   are not read and may be NULL.  mom_out == mom_in is allowed; mom_out may not be prev_rgba or
+   cur_rgba, n_cur < 1 or NaN: RT_ERR_ARG. */
+int rt_moments_accumulate(rt_ctx *ctx, const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in,
+                          float *mom_out, uint32_t width, uint32_t height, int flags);
+int rt_moments_accumulate_async(rt_ctx *ctx, const float *prev_rgba, const float *cur_rgba, float n_cur,
+                                const float *mom_in, float *mom_out, uint32_t width, uint32_t height, int flags,
+                                void *hip_stream);
+/* The variance of the displayed (mean) luminance, out_var: one plane of W*H floats.  Per pixel with
+   l = len[p] (the history length of the moments and of disp_rgba, the frame about to be displayed):
+   l >= min_len: max(m.y - m.x m.x, 0) / (l - 1).  Otherwise a spatial estimate: the 7x7 window at
+   unit distance, tap weights exp(-(|dN|^2/sn^2 + (dP.N)^2/sp^2)) as rt_denoise's feature terms,
+   d = max(sum(w L_q^2)/sum(w) - (sum(w L_q)/sum(w))^2, 0), out = d (min_len / max(l, 1)).
+   Reads sigma_normal, sigma_plane (<= 0 or NaN: RT_ERR_ARG) and min_len (< 2 or NaN: RT_ERR_ARG) of
+   `params`.  out_var apart from every input. */
+int rt_variance(rt_ctx *ctx, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
+                float *out_var, uint32_t width, uint32_t height, const rt_denoise_var_params *params, int flags);
+int rt_variance_async(rt_ctx *ctx, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
+                      float *out_var, uint32_t width, uint32_t height, const rt_denoise_var_params *params, int flags,
+                      void *hip_stream);
+/* rt_denoise's filter with its colour term replaced by |lum(c_q) - lum(c_p)| / (sigma_lum sqrt(g) +
+   1e-8), g the 3x3 Gaussian of the variance plane around p; the variance is filtered along with the
+   colour by the squared weights and feeds the next pass.  in_var: W*H floats >= 0.  out_rgba ==
+   in_rgba and out_var == in_var are allowed (no other overlap); out_var may be NULL.  Reads
+   iterations (outside 1..8: RT_ERR_ARG) and the three sigmas (<= 0 or NaN: RT_ERR_ARG) of `params`. */
+int rt_denoise_var(rt_ctx *ctx, const float *in_rgba, const float *in_var, const float *feat, float *out_rgba,
+                   float *out_var, uint32_t width, uint32_t height, const rt_denoise_var_params *params, int flags);
+int rt_denoise_var_async(rt_ctx *ctx, const float *in_rgba, const float *in_var, const float *feat, float *out_rgba,
+                         float *out_var, uint32_t width, uint32_t height, const rt_denoise_var_params *params, int flags,
+                         void *hip_stream);
+/* Device time of the last moments kernel, the last variance kernel and all passes of the last
+   rt_denoise_var (HIP events of their own), ms; any pointer may be NULL (not all).  RT_ERR_STATE when
+   a kernel asked for has not run. */
+int rt_last_variance_ms(const rt_ctx *ctx, float *moments_ms, float *variance_ms, float *denoise_var_ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

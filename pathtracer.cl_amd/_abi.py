@@ -164,6 +164,11 @@ class RtReprojectParams(ctypes.Structure):
     _fields_ = [("plane_tol", ctypes.c_float), ("normal_min", ctypes.c_float), ("max_history", ctypes.c_float)]
 
 
+class RtDenoiseVarParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("sigma_lum", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_plane", ctypes.c_float), ("min_len", ctypes.c_float)]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -223,6 +228,16 @@ SIGNATURES = {
     "rt_temporal_merge": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32]),
     "rt_temporal_merge_async": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_reproject_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    # variance-guided display filter (csrc/rt_variance.hip)
+    "rt_denoise_var_defaults": (_i32, [ctypes.POINTER(RtDenoiseVarParams)]),
+    "rt_moments_accumulate": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32]),
+    "rt_moments_accumulate_async": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "rt_variance": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseVarParams), _i32]),
+    "rt_variance_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseVarParams), _i32, _vp]),
+    "rt_denoise_var": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseVarParams), _i32]),
+    "rt_denoise_var_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseVarParams), _i32,
+                                    _vp]),
+    "rt_last_variance_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

@@ -345,6 +345,12 @@ struct rt_ctx {
     /* the temporal stage (rt_temporal.hip): its two kernels' events */
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr, ev_m0 = nullptr, ev_m1 = nullptr;
     bool have_reproj_ms = false, have_merge_ms = false;
+    /* the variance-guided filter (rt_variance.hip): the variance planes of its intermediate passes,
+       and the events of its three stages (moments, variance, filter) */
+    float *d_var_tmp[2] = {nullptr, nullptr};
+    size_t var_tmp_bytes[2] = {0, 0};
+    hipEvent_t ev_v[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool have_var_ms[3] = {false, false, false};
     hipStream_t aux_stream = nullptr;
 };
 
@@ -1140,6 +1146,10 @@ try {
     free_dev(c->d_dn_tmp[0]);
     free_dev(c->d_dn_tmp[1]);
     free_dev(c->d_dn_stage);
+    free_dev(c->d_var_tmp[0]);
+    free_dev(c->d_var_tmp[1]);
+    for (hipEvent_t ev : c->ev_v)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {c->ev_f0, c->ev_f1, c->ev_d0, c->ev_d1, c->ev_r0, c->ev_r1, c->ev_m0, c->ev_m1, c->ev_aux})
         if (ev) (void)hipEventDestroy(ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2478,6 +2488,8 @@ int aux_begin(rt_ctx *c, hipStream_t st)
 {
     for (hipEvent_t *ev : {&c->ev_f0, &c->ev_f1, &c->ev_d0, &c->ev_d1, &c->ev_r0, &c->ev_r1, &c->ev_m0, &c->ev_m1})
         if (!*ev) HIPCHK(c, hipEventCreate(ev));
+    for (hipEvent_t &ev : c->ev_v)
+        if (!ev) HIPCHK(c, hipEventCreate(&ev));
     if (!c->ev_aux) HIPCHK(c, hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming));
     if (c->sync_stream && st != c->sync_stream) {
         if (c->sync_stream == c->stream) HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
@@ -2821,6 +2833,203 @@ try {
     if (merge_ms) {
         if (hipEventSynchronize(c->ev_m1) != hipSuccess) return RT_ERR_HIP;
         if (hipEventElapsedTime(merge_ms, c->ev_m0, c->ev_m1) != hipSuccess) return RT_ERR_HIP;
+    }
+    return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+/* ---- variance-guided display filter --------------------- */
+
+int rt_denoise_var_defaults(rt_denoise_var_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->iterations = 5;
+    p->sigma_lum = 4.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    p->min_len = 4.0f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_moments_accumulate_async(rt_ctx *c, const float *prev_rgba, const float *cur_rgba, float n_cur,
+                                const float *mom_in, float *mom_out, uint32_t W, uint32_t H, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_moments_accumulate: n_cur below 1 or NaN");
+    const bool first = n_cur == 1.0f; /* the view's first frame: no history is read */
+    if (!cur_rgba || !mom_out || (!first && (!prev_rgba || !mom_in)))
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_moments_accumulate: flags other than RT_OUT_DEVICE");
+    if (mom_out == prev_rgba || mom_out == cur_rgba)
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate: the output is an accumulation buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t px = (size_t)W * H;
+    const float *d_prev = prev_rgba, *d_cur = cur_rgba, *d_min = mom_in;
+    float *d_mout = mom_out;
+    const bool host = !(flags & RT_OUT_DEVICE);
+    if (host)
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, 12 * px * sizeof(float))) return r;
+    if (const int r = aux_begin(c, st)) return r;
+    if (host) { /* staged: prev, cur, then the moments, accumulated in place there */
+        float *s = c->d_dn_stage;
+        HIPCHK(c, hipMemcpyAsync(s + 4 * px, cur_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        if (!first) {
+            HIPCHK(c, hipMemcpyAsync(s, prev_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(s + 8 * px, mom_in, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        }
+        d_prev = s;
+        d_cur = s + 4 * px;
+        d_min = d_mout = s + 8 * px;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_v[0], st));
+    const int e = rt_launch_moments(d_prev, d_cur, n_cur, d_min, d_mout, W, H, st);
+    if (e) return hip_fail(c, (hipError_t)e, "moments kernel launch");
+    HIPCHK(c, hipEventRecord(c->ev_v[1], st));
+    c->have_var_ms[0] = true;
+    if (host) HIPCHK(c, hipMemcpyAsync(mom_out, d_mout, 4 * px * sizeof(float), hipMemcpyDeviceToHost, st));
+    return aux_end(c, st);
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_moments_accumulate(rt_ctx *c, const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in,
+                          float *mom_out, uint32_t W, uint32_t H, int flags)
+try {
+    const int r = rt_moments_accumulate_async(c, prev_rgba, cur_rgba, n_cur, mom_in, mom_out, W, H, flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_variance_async(rt_ctx *c, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
+                      float *out_var, uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!disp_rgba || !mom_rgba || !len || !feat || !out_var || !prm) return fail(c, RT_ERR_ARG, "rt_variance: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_variance: flags other than RT_OUT_DEVICE");
+    if (!(prm->min_len >= 2.0f)) return fail(c, RT_ERR_ARG, "rt_variance: min_len below 2 or NaN");
+    if (!(prm->sigma_normal > 0.0f) || !(prm->sigma_plane > 0.0f))
+        return fail(c, RT_ERR_ARG, "rt_variance: a sigma is not positive"); /* <= 0 or NaN */
+    const float isn = 1.0f / (prm->sigma_normal * prm->sigma_normal), isp = 1.0f / (prm->sigma_plane * prm->sigma_plane);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t px = (size_t)W * H;
+    const float *d_disp = disp_rgba, *d_mom = mom_rgba, *d_len = len, *d_feat = feat;
+    float *d_out = out_var;
+    const bool host = !(flags & RT_OUT_DEVICE);
+    if (host) /* staged: the float4 streams first (px may be odd), then the two planes */
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, 18 * px * sizeof(float))) return r;
+    if (const int r = aux_begin(c, st)) return r;
+    if (host) {
+        float *s = c->d_dn_stage;
+        HIPCHK(c, hipMemcpyAsync(s, disp_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 4 * px, mom_rgba, 4 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 8 * px, feat, 8 * px * sizeof(float), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 16 * px, len, px * sizeof(float), hipMemcpyHostToDevice, st));
+        d_disp = s;
+        d_mom = s + 4 * px;
+        d_feat = s + 8 * px;
+        d_len = s + 16 * px;
+        d_out = s + 17 * px;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_v[2], st));
+    const int e = rt_launch_variance(d_disp, d_mom, d_len, d_feat, d_out, W, H, isn, isp, prm->min_len, st);
+    if (e) return hip_fail(c, (hipError_t)e, "variance kernel launch");
+    HIPCHK(c, hipEventRecord(c->ev_v[3], st));
+    c->have_var_ms[1] = true;
+    if (host) HIPCHK(c, hipMemcpyAsync(out_var, d_out, px * sizeof(float), hipMemcpyDeviceToHost, st));
+    return aux_end(c, st);
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_variance(rt_ctx *c, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
+                float *out_var, uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags)
+try {
+    const int r = rt_variance_async(c, disp_rgba, mom_rgba, len, feat, out_var, W, H, prm, flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_denoise_var_async(rt_ctx *c, const float *in, const float *in_var, const float *feat, float *out, float *out_var,
+                         uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!in || !in_var || !feat || !out || !prm) return fail(c, RT_ERR_ARG, "rt_denoise_var: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_denoise_var: flags other than RT_OUT_DEVICE");
+    if (prm->iterations < 1 || prm->iterations > 8) return fail(c, RT_ERR_ARG, "rt_denoise_var: iterations outside 1..8");
+    const float sig[3] = {prm->sigma_lum, prm->sigma_normal, prm->sigma_plane};
+    for (float s : sig)
+        if (!(s > 0.0f)) return fail(c, RT_ERR_ARG, "rt_denoise_var: a sigma is not positive"); /* <= 0 or NaN */
+    const float isn = 1.0f / (sig[1] * sig[1]), isp = 1.0f / (sig[2] * sig[2]);
+    const int lum_on = sig[0] < rt_inff(); /* +INFINITY: the luminance term is off (inf * 0 would be a NaN) */
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t px = (size_t)W * H, plane = px * 4 * sizeof(float);
+    const uint32_t n = prm->iterations;
+    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) { /* (three passes and more alternate between two) */
+        if (const int r = ensure_dev(c, c->d_dn_tmp[k], c->dn_tmp_bytes[k], plane)) return r;
+        if (const int r = ensure_dev(c, c->d_var_tmp[k], c->var_tmp_bytes[k], px * sizeof(float))) return r;
+    }
+    const float *din = in, *dvin = in_var, *dfeat = feat;
+    float *dout = out, *dvout = out_var;
+    const bool host = !(flags & RT_OUT_DEVICE);
+    if (host) /* staged: colour, the two feature planes, then the variance plane */
+        if (const int r = ensure_dev(c, c->d_dn_stage, c->dn_stage_bytes, 13 * px * sizeof(float))) return r;
+    if (const int r = aux_begin(c, st)) return r;
+    if (host) {
+        float *s = c->d_dn_stage;
+        HIPCHK(c, hipMemcpyAsync(s, in, plane, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 4 * px, feat, 2 * plane, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(s + 12 * px, in_var, px * sizeof(float), hipMemcpyHostToDevice, st));
+        din = dout = s; /* filtered in place there (the last pass never reads its destination, below) */
+        dfeat = s + 4 * px;
+        dvin = s + 12 * px;
+        if (out_var) dvout = s + 12 * px;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_v[4], st));
+    /* as rt_denoise: pass i reads the previous pass's outputs and writes scratch, the last one the
+       outputs — through scratch and a copy where an output is the buffer the pass reads */
+    const float *src = din, *vsrc = dvin;
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool last = i + 1 == n;
+        float *dst = (last && dout != src) ? dout : c->d_dn_tmp[src == c->d_dn_tmp[0] ? 1 : 0];
+        float *vdst = (last && dvout != vsrc) ? dvout : c->d_var_tmp[vsrc == c->d_var_tmp[0] ? 1 : 0];
+        const int e = rt_launch_atrous_var(src, vsrc, dfeat, dst, vdst, W, H, 1u << i, sig[0], lum_on, isn, isp, st);
+        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
+        src = dst;
+        vsrc = vdst;
+    }
+    if (src != dout) HIPCHK(c, hipMemcpyAsync(dout, src, plane, hipMemcpyDeviceToDevice, st));
+    if (dvout && vsrc != dvout) HIPCHK(c, hipMemcpyAsync(dvout, vsrc, px * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipEventRecord(c->ev_v[5], st));
+    c->have_var_ms[2] = true;
+    if (host) {
+        HIPCHK(c, hipMemcpyAsync(out, dout, plane, hipMemcpyDeviceToHost, st));
+        if (out_var) HIPCHK(c, hipMemcpyAsync(out_var, dvout, px * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    return aux_end(c, st);
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_denoise_var(rt_ctx *c, const float *in, const float *in_var, const float *feat, float *out, float *out_var,
+                   uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags)
+try {
+    const int r = rt_denoise_var_async(c, in, in_var, feat, out, out_var, W, H, prm, flags, nullptr);
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
+
+int rt_last_variance_ms(const rt_ctx *c, float *moments_ms, float *variance_ms, float *denoise_var_ms)
+try {
+    if (!c || (!moments_ms && !variance_ms && !denoise_var_ms)) return RT_ERR_ARG;
+    float *out[3] = {moments_ms, variance_ms, denoise_var_ms};
+    for (int k = 0; k < 3; ++k)
+        if (out[k] && !c->have_var_ms[k]) return RT_ERR_STATE;
+    for (int k = 0; k < 3; ++k) {
+        if (!out[k]) continue;
+        if (hipEventSynchronize(c->ev_v[2 * k + 1]) != hipSuccess) return RT_ERR_HIP;
+        if (hipEventElapsedTime(out[k], c->ev_v[2 * k], c->ev_v[2 * k + 1]) != hipSuccess) return RT_ERR_HIP;
     }
     return RT_OK;
 } RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)

@@ -336,6 +336,16 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
                         float normal_min, float max_history, void *stream);
 int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
                              float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
+/* The variance-guided display filter (rt_variance.hip): device buffers.  The
+   moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in.  One filter
+   pass at tap distance `step`: out / out_var apart from col / var, out_var possibly NULL; lum_on == 0
+   switches the luminance term off. */
+int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
+                      uint32_t W, uint32_t H, void *stream);
+int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
+                       uint32_t W, uint32_t H, float isn, float isp, float min_len, void *stream);
+int rt_launch_atrous_var(const float *col, const float *var, const float *feat, float *out, float *out_var, uint32_t W,
+                         uint32_t H, uint32_t step, float sigma_lum, int lum_on, float isn, float isp, void *stream);
 /* Camera-ray candidate lists for the launch's pixels (writes a.pixel_lists and the list
    records in the triangle buffer at a.list_base); nodes4 = full-precision 4-wide tree,
    q4 = compressed nodes (their normal boxes; may be NULL). */

@@ -21,6 +21,10 @@
  *             [--temporal [MAXHIST]]   (with --events: the view carries its displayed frame across camera
  *              moves (ProgressiveViewHIP::setTemporal, history capped at MAXHIST frames, default 32), with or
  *              without --denoise: --frames-out holds what it shows, --raw-frames-out and --features-out as above)
+ *             [--variance-guided [SIGMA_LUM]]   (with --events: the view displays the variance-guided filter
+ *              (ProgressiveViewHIP::setVarianceGuided, luminance tolerance SIGMA_LUM standard deviations, default 4)
+ *              in place of --denoise's, with or without --temporal: --frames-out holds what it shows,
+ *              --raw-frames-out and --features-out as above)
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -104,7 +108,7 @@ int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
-                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--denoised f] [--denoised-pfm f] [--features-out f] "
+                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
@@ -137,7 +141,8 @@ bool share_comm_id(const std::string &path, int rank, uint8_t id[RT_COMM_ID_BYTE
 int main(int argc, char **argv)
 {
     std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out;
-    bool denoise = false, temporal = false;
+    bool denoise = false, temporal = false, var_guided = false;
+    rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
     rt_denoise_params den_params = RayTracerHIP::denoiseDefaults();
     unsigned W = 512, H = 512, frames = 1, sr = 1, depth = 6, n_tris = 0, max_prog = 10000;
@@ -160,6 +165,11 @@ int main(int argc, char **argv)
         if (a == "--temporal") { /* an optional history cap follows */
             temporal = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') temporal_params.max_history = (float)std::atof(argv[++i]);
+            continue;
+        }
+        if (a == "--variance-guided") { /* an optional luminance tolerance follows */
+            var_guided = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') var_params.sigma_lum = (float)std::atof(argv[++i]);
             continue;
         }
         if (!(v = next())) return usage();
@@ -193,6 +203,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --temporal needs --events (it carries the display across camera moves)\n");
         return 2;
     }
+    if (var_guided && events.empty()) {
+        std::fprintf(stderr, "rt_render: --variance-guided needs --events (it follows a view's progressive frames)\n");
+        return 2;
+    }
     try {
         RayTracerHIP rt(device);
         add_scene(rt, ply);
@@ -219,6 +233,7 @@ int main(int argc, char **argv)
             view.setProgressive(max_prog);
             if (denoise) view.setDenoise(true, den_params);
             if (temporal) view.setTemporal(true, temporal_params);
+            if (var_guided) view.setVarianceGuided(true, var_params);
             FILE *fo = frames_out.empty() ? nullptr : std::fopen(frames_out.c_str(), "wb");
             if (!frames_out.empty() && !fo) return 1;
             FILE *fr = raw_frames_out.empty() ? nullptr : std::fopen(raw_frames_out.c_str(), "wb");

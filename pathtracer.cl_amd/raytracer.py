@@ -376,6 +376,83 @@ class RayTracer:
         self._check(self._lib.rt_last_reproject_ms(self._h, a, b), "rt_last_reproject_ms")
         return ms.value
 
+    # ---- variance-guided display filter (pathtracer_rt.h) ----
+    def denoiseVarDefaults(self) -> dict:
+        prm = _abi.RtDenoiseVarParams()
+        self._check(self._lib.rt_denoise_var_defaults(ctypes.byref(prm)), "rt_denoise_var_defaults")
+        return dict(iterations=prm.iterations, sigma_lum=prm.sigma_lum, sigma_normal=prm.sigma_normal,
+                    sigma_plane=prm.sigma_plane, min_len=prm.min_len)
+
+    def _aux_call(self, name: str, args: tuple, stream, sync: bool) -> None:
+        if sync and stream is None:
+            self._check(getattr(self._lib, name)(*args), name)
+        else:
+            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
+            self._check(getattr(self._lib, name + "_async")(*args, sp), name + "_async")
+            if sync:
+                self.synchronize()
+
+    def momentsAccumulate(self, prev_rgba, cur_rgba, n_cur: float, mom_in, mom_out, width: int, height: int,
+                          stream=None, sync: bool = True) -> None:
+        """After a progressive frame: fold the frame's own luminance (recovered from the accumulation
+        buffer after it, `cur_rgba`, and a copy taken before it, `prev_rgba`; `n_cur` =
+        max(progression, 1)) into the view's moments frame `mom_in` -> `mom_out` (may be the same
+        buffer).  With n_cur == 1 `prev_rgba` and `mom_in` are not read and may be None.  All numpy
+        arrays or all torch CUDA tensors; the accumulation buffers are only read."""
+        px = int(width) * int(height)
+        need = [(prev_rgba, "previous accumulation"), (cur_rgba, "current accumulation"), (mom_in, "moments"),
+                (mom_out, "destination moments")]
+        flags = [self._frame_buffer(b, px * 4, what) for b, what in need if b is not None]
+        if len(set(flags)) != 1:
+            raise ValueError("momentsAccumulate: the buffers must all be host arrays or all device tensors")
+        args = (self._h, _abi.ptr(prev_rgba), _abi.ptr(cur_rgba), float(n_cur), _abi.ptr(mom_in), _abi.ptr(mom_out),
+                int(width), int(height), flags[0])
+        self._aux_call("rt_moments_accumulate", args, stream, sync)
+
+    def variance(self, disp_rgba, mom_rgba, length, feat, out_var, width: int, height: int, sigma_normal: float = 0.3,
+                 sigma_plane: float = 0.1, min_len: float = 4.0, stream=None, sync: bool = True) -> None:
+        """The variance of the displayed luminance into `out_var` (W*H floats): from the moments frame
+        `mom_rgba` where the history length `length` (W*H floats) reaches `min_len`, else from a 7x7
+        feature-weighted window of `disp_rgba`, the frame about to be displayed.  All numpy arrays or
+        all torch CUDA tensors; the inputs are only read."""
+        px = int(width) * int(height)
+        need = [(disp_rgba, 4, "displayed frame"), (mom_rgba, 4, "moments"), (length, 1, "history lengths"),
+                (feat, 8, "feature buffer"), (out_var, 1, "destination variance")]
+        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
+        if len(set(flags)) != 1:
+            raise ValueError("variance: the buffers must all be host arrays or all device tensors")
+        prm = _abi.RtDenoiseVarParams(5, 4.0, float(sigma_normal), float(sigma_plane), float(min_len))
+        args = (self._h, _abi.ptr(disp_rgba), _abi.ptr(mom_rgba), _abi.ptr(length), _abi.ptr(feat), _abi.ptr(out_var),
+                int(width), int(height), ctypes.byref(prm), flags[0])
+        self._aux_call("rt_variance", args, stream, sync)
+
+    def denoiseVar(self, src, var, feat, dst, dst_var, width: int, height: int, iterations: int = 5,
+                   sigma_lum: float = 4.0, sigma_normal: float = 0.3, sigma_plane: float = 0.1, stream=None,
+                   sync: bool = True) -> None:
+        """Variance-guided a-trous filter of the RGBA32F frame `src` with its variance plane `var`
+        (W*H floats, `variance`) guided by `feat` into `dst` (may be `src`) and `dst_var` (may be
+        `var`, or None); all numpy arrays or all torch CUDA tensors."""
+        px = int(width) * int(height)
+        need = [(src, 4, "source frame"), (var, 1, "variance"), (feat, 8, "feature buffer"), (dst, 4, "destination frame"),
+                (dst_var, 1, "destination variance")]
+        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need if b is not None]
+        if len(set(flags)) != 1:
+            raise ValueError("denoiseVar: the buffers must all be host arrays or all device tensors")
+        prm = _abi.RtDenoiseVarParams(int(iterations), float(sigma_lum), float(sigma_normal), float(sigma_plane), 4.0)
+        args = (self._h, _abi.ptr(src), _abi.ptr(var), _abi.ptr(feat), _abi.ptr(dst), _abi.ptr(dst_var), int(width),
+                int(height), ctypes.byref(prm), flags[0])
+        self._aux_call("rt_denoise_var", args, stream, sync)
+
+    def lastVarianceMs(self, which: str = "denoise_var") -> float:
+        """Device time of the last `moments` kernel, `variance` kernel, or of all passes of the last
+        `denoise_var`, ms."""
+        k = ("moments", "variance", "denoise_var").index(which)
+        ms = ctypes.c_float()
+        a = [None, None, None]
+        a[k] = ctypes.byref(ms)
+        self._check(self._lib.rt_last_variance_ms(self._h, *a), "rt_last_variance_ms")
+        return ms.value
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
