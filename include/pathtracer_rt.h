@@ -266,6 +266,20 @@ int rt_last_long_chains(rt_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n);
    list (its camera rays take the tree).  Copies min(cap, *n) entries; *n = the render's pixels, 0
    when it used no lists.  Diagnostics and parity tests. */
 int rt_last_list_counts(rt_ctx *ctx, uint16_t *out, uint32_t cap, uint32_t *n);
+/* The current mesh's trees as the kernels read them, copied from the device: the full-precision
+   4-wide nodes of the closest-hit tree (32 floats each), the compressed nodes of both trees (16
+   dwords each, the shadow tree's from shadow_root on, links and record slots already offset) and
+   the triangle records the trees' leaves refer to (12 floats each).  A NULL array is not copied;
+   *layout is always filled.  RT_ERR_NO_MESH without a mesh, RT_ERR_STATE when nodes4q is asked
+   for and the mesh has no compressed nodes.  Diagnostics and tests (tests/tree_ref.py). */
+typedef struct rt_tree_layout {
+    uint32_t n_nodes4;        /* closest-hit tree */
+    uint32_t n_nodes4_shadow; /* 0: one tree */
+    uint32_t shadow_root;     /* index of the shadow tree's root in the compressed array */
+    uint32_t n_records;       /* triangle records the trees refer to */
+    uint32_t compressed;      /* 1: compressed nodes exist */
+} rt_tree_layout;
+int rt_mesh_tree(rt_ctx *ctx, rt_tree_layout *layout, float *nodes4, uint32_t *nodes4q, float *tris);
 
 /* ---- ray queries for hit-index parity (rtcommon.h:39-52 / :59-68 semantics).
    Host arrays; any_hit=0: out_idx = closest triangle (-1 none), out_t = its t;

@@ -112,6 +112,11 @@ class RtMeshStats(ctypes.Structure):
                 ("n_nodes4_shadow", ctypes.c_uint32)]
 
 
+class RtTreeLayout(ctypes.Structure):
+    _fields_ = [("n_nodes4", ctypes.c_uint32), ("n_nodes4_shadow", ctypes.c_uint32), ("shadow_root", ctypes.c_uint32),
+                ("n_records", ctypes.c_uint32), ("compressed", ctypes.c_uint32)]
+
+
 class RtCounters(ctypes.Structure):
     _fields_ = [
         ("rays_closest", ctypes.c_uint64),
@@ -209,6 +214,7 @@ SIGNATURES = {
     "rt_last_render_info": (_i32, [_vp, ctypes.POINTER(RtRenderInfo)]),
     "rt_last_long_chains": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
     "rt_last_list_counts": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
+    "rt_mesh_tree": (_i32, [_vp, ctypes.POINTER(RtTreeLayout), _vp, _vp, _vp]),
     "rt_trace_rays": (_i32, [_vp, _vp, _u32, _i32, _vp, _vp]),
     # first-hit feature buffers and the display denoiser (csrc/rt_denoise.hip)
     "rt_get_camera": (_i32, [_vp, _u32, _vp]),

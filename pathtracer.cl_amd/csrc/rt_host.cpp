@@ -2366,6 +2366,29 @@ try {
     return RT_OK;
 } RT_CATCH(c ? &c->err : nullptr)
 
+int rt_mesh_tree(rt_ctx *c, rt_tree_layout *layout, float *nodes4, uint32_t *nodes4q, float *tris)
+try {
+    if (!c || !layout) return RT_ERR_ARG;
+    if (!c->n_tris || !c->d_nodes4 || !c->d_tris) return RT_ERR_NO_MESH;
+    layout->n_nodes4 = c->bvh.n_nodes4;
+    layout->n_nodes4_shadow = c->n_nodes4_shadow;
+    layout->shadow_root = c->shadow_root;
+    layout->n_records = (uint32_t)c->tree_recs;
+    layout->compressed = c->d_nodes4q ? 1u : 0u;
+    if (nodes4q && !c->d_nodes4q) return fail(c, RT_ERR_STATE, "the mesh has no compressed nodes");
+    if (!nodes4 && !nodes4q && !tris) return RT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nodes4)
+        HIPCHK(c, hipMemcpy(nodes4, c->d_nodes4, (size_t)c->bvh.n_nodes4 * 32 * sizeof(float), hipMemcpyDeviceToHost));
+    if (nodes4q)
+        HIPCHK(c, hipMemcpy(nodes4q, c->d_nodes4q,
+                            ((size_t)c->bvh.n_nodes4 + c->n_nodes4_shadow) * RT_QNODE_DWORDS * sizeof(uint32_t),
+                            hipMemcpyDeviceToHost));
+    if (tris) HIPCHK(c, hipMemcpy(tris, c->d_tris, c->tree_recs * 12 * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+} RT_CATCH(c ? &c->err : nullptr)
+
 int rt_get_counters(const rt_ctx *c, rt_counters *out)
 try {
     if (!c || !out) return RT_ERR_ARG;

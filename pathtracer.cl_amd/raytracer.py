@@ -539,6 +539,21 @@ class RayTracer:
                         "rt_last_list_counts")
         return out
 
+    def meshTree(self) -> dict:
+        """rt_mesh_tree: the current mesh's trees as the kernels read them.  The layout's fields, and
+        `nodes4` (n_nodes4 x 32 float32, the closest-hit tree), `nodes4q` ((n_nodes4 + n_nodes4_shadow)
+        x 16 uint32, None without compressed nodes), `tris` (n_records x 12 float32)."""
+        lay = _abi.RtTreeLayout()
+        self._check(self._lib.rt_mesh_tree(self._h, ctypes.byref(lay), None, None, None), "rt_mesh_tree")
+        nodes4 = np.empty((lay.n_nodes4, 32), np.float32)
+        nodes4q = np.empty((lay.n_nodes4 + lay.n_nodes4_shadow, 16), np.uint32) if lay.compressed else None
+        tris = np.empty((lay.n_records, 12), np.float32)
+        self._check(self._lib.rt_mesh_tree(self._h, ctypes.byref(lay), _abi.ptr(nodes4), _abi.ptr(nodes4q),
+                                           _abi.ptr(tris)), "rt_mesh_tree")
+        out = {f: getattr(lay, f) for f, _ in _abi.RtTreeLayout._fields_}
+        out.update(nodes4=nodes4, nodes4q=nodes4q, tris=tris)
+        return out
+
     def traceRays(self, rays: np.ndarray, any_hit: bool = False) -> tuple[np.ndarray, np.ndarray]:
         r = np.ascontiguousarray(rays, _abi.RAY_DTYPE)
         idx = np.empty(r.size, np.int32)
