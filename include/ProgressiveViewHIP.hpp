@@ -133,6 +133,21 @@ public:
         return post;
     }
 
+    /* The mesh moves (RayTracerHIP::updateMesh): the features are rendered again, and what the
+       display stages keep of earlier frames — the temporal history and the luminance moments —
+       is dropped, not carried: it shows the old geometry (there are no motion vectors).
+       Progression back to 0; returns restart()'s answer. */
+    bool updateMesh(const float *verts_xyz, uint32_t n_verts, int flags = 0)
+    {
+        rt_.updateMesh(verts_xyz, n_verts, flags);
+        featDirty_ = true;
+        haveHist_ = false;
+        momValid_ = false;
+        const bool post = restart();
+        carry_ = false;
+        return post;
+    }
+
     void setDenoise(bool on, const rt_denoise_params &params = RayTracerHIP::denoiseDefaults())
     {
         if (on && !denoise_) featDirty_ = true;

@@ -151,6 +151,21 @@ public:
         flushScene();
         check(rt_set_mesh(ctx_, verts_xyz, n_verts, idx, n_tris), "setMesh");
     }
+    /* New positions for the vertices of the last setMesh (rt_update_mesh: a refit of both trees on
+       the device, or a rebuild where a refit cannot stand for a build; lastMeshUpdate() says which).
+       flags: RT_MESH_VERTS_DEVICE when verts_xyz is device memory. */
+    void updateMesh(const float *verts_xyz, uint32_t n_verts, int flags = 0)
+    {
+        check(rt_update_mesh(ctx_, verts_xyz, n_verts, flags), "updateMesh");
+    }
+    /* The next host-built setMesh keeps every triangle, so that every later updateMesh refits. */
+    void setMeshDynamic(bool on) { check(rt_set_mesh_dynamic(ctx_, on ? 1 : 0), "setMeshDynamic"); }
+    rt_mesh_update_info lastMeshUpdate() const
+    {
+        rt_mesh_update_info i;
+        check(rt_last_mesh_update(ctx_, &i), "lastMeshUpdate");
+        return i;
+    }
     void setTraversal(int traversal) { check(rt_set_traversal(ctx_, traversal), "setTraversal"); }
     /* BVH builder for the next setMesh: RT_BUILD_HOST (binned SAH) or RT_BUILD_GPU (LBVH). */
     void setBuilder(int builder) { check(rt_set_builder(ctx_, builder), "setBuilder"); }

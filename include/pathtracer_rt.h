@@ -135,6 +135,34 @@ enum { RT_BUILD_HOST = 0, RT_BUILD_GPU = 1 };
 int rt_set_builder(rt_ctx *ctx, int builder);
 int rt_mesh_info(const rt_ctx *ctx, rt_mesh_stats *out);
 
+/* ---- a moving mesh: new positions for the vertices of the last rt_set_mesh (same count, same
+   indices), by a refit of both trees on the device — the records, the boxes, the compressed
+   planes and the normal boxes recomputed from the trees' own links; no build, no upload of
+   nodes.  Synchronous.  Every result afterwards is bit for bit what a fresh rt_set_mesh with the
+   new vertices gives; rt_mesh_info's numbers stay those of the build.  Errors (RT_ERR_NO_MESH;
+   RT_ERR_ARG for another vertex count or a non-finite coordinate) leave the previous mesh as it
+   was.  The call rebuilds instead, as rt_set_mesh with the kept indices and the mesh's own
+   builder, when a triangle the host builder left out of the tree (no unit ray could hit it) can
+   now be hit, or when the compressed form stops / starts holding every node.
+   rt_set_mesh_dynamic(ctx, 1) makes the next host build keep every triangle, so that later
+   updates always refit (the tree then holds the never-hit triangles too).  area_ratio tells how
+   far the refitted boxes have grown since the build: the sign to call rt_set_mesh again. ---- */
+enum { RT_MESH_VERTS_DEVICE = 1 }; /* flags: verts_xyz is a device pointer */
+enum { RT_MESH_UPDATE_REFIT = 1, RT_MESH_UPDATE_REBUILT = 2 };
+enum { RT_REFIT_OK = 0, RT_REFIT_NEWLY_HITTABLE = 1, RT_REFIT_ENCODING = 2 };
+typedef struct rt_mesh_update_info {
+    uint32_t action;         /* REFIT or REBUILT */
+    uint32_t reason;         /* why rebuilt, else RT_REFIT_OK */
+    uint32_t newly_hittable; /* triangles left out of the tree that a unit ray can now hit */
+    uint32_t now_unhittable; /* triangles in the tree that a unit ray could hit when it was built and none can
+                                now (they stay) */
+    float area_ratio;        /* closest-hit tree: sum of child-box half-areas now / at its build */
+    float ms;                /* device time of the refit kernels (HIP events); 0 when rebuilt */
+} rt_mesh_update_info;
+int rt_update_mesh(rt_ctx *ctx, const float *verts_xyz, uint32_t n_verts, int flags);
+int rt_last_mesh_update(const rt_ctx *ctx, rt_mesh_update_info *out);
+int rt_set_mesh_dynamic(rt_ctx *ctx, int on); /* for the next rt_set_mesh */
+
 /* ---- camera: RayTracer::setCameraMatrix / setCameraSpherical / setFoVAngle
    (RayTracer.h:56-60, RayTracer.cpp:24-47); the Camera struct is derived per
    frame width exactly as RayTracerCL::updateCLCamera (RayTracerCL.cpp:178-215). ---- */

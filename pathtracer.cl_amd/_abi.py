@@ -40,6 +40,13 @@ RT_TRAVERSAL_BVH4F = 4
 RT_BUILD_HOST = 0
 RT_BUILD_GPU = 1
 
+RT_MESH_VERTS_DEVICE = 1
+RT_MESH_UPDATE_REFIT = 1
+RT_MESH_UPDATE_REBUILT = 2
+RT_REFIT_OK = 0
+RT_REFIT_NEWLY_HITTABLE = 1
+RT_REFIT_ENCODING = 2
+
 RT_OUT_DEVICE = 1
 RT_SEEDS_HALO = 2
 
@@ -110,6 +117,11 @@ class RtMeshStats(ctypes.Structure):
                 ("n_nodes4", ctypes.c_uint32), ("depth4", ctypes.c_uint32), ("stack4", ctypes.c_uint32),
                 ("build_seconds", ctypes.c_double), ("builder", ctypes.c_uint32), ("n_tris_tree", ctypes.c_uint32),
                 ("n_nodes4_shadow", ctypes.c_uint32)]
+
+
+class RtMeshUpdateInfo(ctypes.Structure):
+    _fields_ = [("action", ctypes.c_uint32), ("reason", ctypes.c_uint32), ("newly_hittable", ctypes.c_uint32),
+                ("now_unhittable", ctypes.c_uint32), ("area_ratio", ctypes.c_float), ("ms", ctypes.c_float)]
 
 
 class RtTreeLayout(ctypes.Structure):
@@ -184,6 +196,9 @@ SIGNATURES = {
     "rt_set_spheres": (_i32, [_vp, _vp, _u32]),
     "rt_set_mesh": (_i32, [_vp, _vp, _u32, _vp, _u32]),
     "rt_mesh_info": (_i32, [_vp, ctypes.POINTER(RtMeshStats)]),
+    "rt_update_mesh": (_i32, [_vp, _vp, _u32, _i32]),
+    "rt_last_mesh_update": (_i32, [_vp, ctypes.POINTER(RtMeshUpdateInfo)]),
+    "rt_set_mesh_dynamic": (_i32, [_vp, _i32]),
     "rt_set_view_matrix": (_i32, [_vp, _vp]),
     "rt_set_camera_spherical": (_i32, [_vp, _f32, _f32, _f32, _f32, _f32, _f32]),
     "rt_set_fov": (_i32, [_vp, _f32]),

@@ -270,6 +270,35 @@ struct rt_ctx {
     int builder = RT_BUILD_HOST;      /* builder for the next rt_set_mesh */
     int mesh_builder = RT_BUILD_HOST; /* builder of the current mesh */
     uint64_t mesh_serial = 0;
+    /* the moving mesh (rt_update_mesh, rt_refit.hip): the indices of the last rt_set_mesh, on the
+       host for a rebuild and on the device for the refit; how that mesh was built; the refit's
+       workspace, allocated at the first update (at rt_set_mesh in dynamic mode) and kept until the
+       next rt_set_mesh */
+    std::vector<int32_t> h_idx;
+    int32_t *d_idx = nullptr;
+    uint32_t n_verts = 0;
+    bool dynamic = false;       /* the next host build keeps every triangle */
+    bool mesh_dynamic = false;  /* the current mesh was built so */
+    bool mesh_det_cull = true;  /* ... with normal boxes in its compressed nodes */
+    struct Refit {
+        bool ready = false;
+        float *d_verts = nullptr;          /* the update's vertices */
+        float *d_tbox = nullptr;           /* padded box per record slot */
+        uint8_t *d_hit0 = nullptr;         /* per tree slot: hittable when the tree was built (set by the first update) */
+        bool have_hit0 = false;
+        float *d_shadow_full = nullptr;    /* the shadow tree's full-precision nodes */
+        uint32_t *d_qscratch = nullptr;    /* compressed nodes of a tree that has none: the encodability test */
+        void *d_nbox = nullptr;            /* binary64 normal-box bounds per node */
+        uint32_t *d_res = nullptr;         /* RT_REFIT_RES_WORDS */
+        double *d_part = nullptr;          /* RT_REFIT_AREA_BLOCKS partial area sums */
+        RtRefitStep *d_steps = nullptr;
+        std::vector<RtRefitStep> steps;    /* deepest level first */
+        double area0 = 0.0;                /* the build's own area sum */
+        bool have_area0 = false;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    } refit;
+    rt_mesh_update_info last_update = {};
+    bool have_update = false;
     size_t spill_entries = 0;
     /* owner-map tiles (rt_tile.stripe_owner): the tile's frame stripes in order, on the device, and a
        serial that changes with them (in the view / schedule keys) */
@@ -376,6 +405,24 @@ int hip_fail(rt_ctx *c, hipError_t e, const char *what)
 void free_dev(void *p)
 {
     if (p) (void)hipFree(p);
+}
+
+/* the refit's workspace (rt_update_mesh): gone with the mesh it was sized for */
+void refit_free(rt_ctx *c)
+{
+    rt_ctx::Refit &r = c->refit;
+    free_dev(r.d_verts);
+    free_dev(r.d_tbox);
+    free_dev(r.d_hit0);
+    free_dev(r.d_shadow_full);
+    free_dev(r.d_qscratch);
+    free_dev(r.d_nbox);
+    free_dev(r.d_res);
+    free_dev(r.d_part);
+    free_dev(r.d_steps);
+    if (r.ev0) (void)hipEventDestroy(r.ev0);
+    if (r.ev1) (void)hipEventDestroy(r.ev1);
+    r = rt_ctx::Refit();
 }
 
 /* RayTracer::setCameraSpherical (RayTracer.cpp:33-47): gmtl EulerAngle<ZYX>
@@ -1103,6 +1150,8 @@ try {
     free_dev(c->d_lights);
     free_dev(c->d_nodes4);
     free_dev(c->d_nodes4q);
+    refit_free(c);
+    free_dev(c->d_idx);
     free_dev(c->d_spill);
     free_dev(c->d_order);
     free_dev(c->d_flags);
@@ -1216,13 +1265,14 @@ static bool mesh_bounds(const float *verts, const int32_t *idx, uint32_t n_tris,
     return true;
 }
 
-int rt_set_mesh(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris)
-try {
-    if (!c || !verts || !idx || !n_verts || !n_tris) return fail(c, RT_ERR_ARG, "empty mesh");
-    HIPCHK(c, hipSetDevice(c->device));
+/* The build and the upload of rt_set_mesh (and of rt_update_mesh's rebuild): `builder` and
+   `dynamic` are the context's choices for the next mesh, or the current mesh's own. */
+static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
+                          int builder, bool dynamic)
+{
     std::string err;
     c->mesh_bounds_ok = false;
-    if (c->builder == RT_BUILD_GPU) {
+    if (builder == RT_BUILD_GPU) {
         if (!rt_validate_mesh(verts, n_verts, idx, n_tris, err)) return fail(c, RT_ERR_ARG, err);
         free_dev(c->d_nodes4);
         free_dev(c->d_nodes4q);
@@ -1261,6 +1311,8 @@ try {
         }
         c->mesh_builder = RT_BUILD_GPU;
         c->mesh_bounds_ok = mesh_bounds(verts, idx, n_tris, c->mesh_lo, c->mesh_hi);
+        c->mesh_det_cull = det_cull;
+        c->mesh_dynamic = dynamic;
         return RT_OK;
     }
     /* Two host trees over the same triangles: the closest-hit queries (camera rays, bounces, the
@@ -1274,6 +1326,7 @@ try {
        the same hits. */
     RtBvh b;
     if (const char *v = getenv("RT_CULL_UNHITTABLE")) b.cull_unhittable = atoi(v) != 0; /* A/B knob */
+    if (dynamic) b.cull_unhittable = false; /* rt_set_mesh_dynamic: every later update can refit */
     if (const char *v = getenv("RT_DET_CULL")) b.det_cull = atoi(v) != 0; /* A/B knob */
     RtBvh sb;
     sb.cull_unhittable = b.cull_unhittable;
@@ -1359,6 +1412,209 @@ try {
     c->bvh.build_seconds = b.build_seconds;
     c->bvh.n_hit = b.n_hit;
     c->mesh_bounds_ok = mesh_bounds(verts, idx, n_tris, c->mesh_lo, c->mesh_hi);
+    c->mesh_det_cull = b.det_cull;
+    c->mesh_dynamic = dynamic;
+    return RT_OK;
+}
+
+/* The refit's workspace for the current mesh: the levels of both trees read off their links
+   (deepest first: the steps of k_refit_levels), and every array an update writes.  Nothing is
+   allocated in an update after this. */
+static int refit_prepare(rt_ctx *c)
+{
+    rt_ctx::Refit &r = c->refit;
+    const uint32_t n_a = c->bvh.n_nodes4, n_s = c->n_nodes4_shadow, n_all = n_a + n_s;
+    std::vector<uint32_t> q((size_t)RT_QNODE_DWORDS * n_all, 0u);
+    if (c->d_nodes4q) {
+        HIPCHK(c, hipMemcpy(q.data(), c->d_nodes4q, q.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    } else { /* full-precision nodes only: their links in the compressed nodes' place */
+        std::vector<float> f(32ull * n_a);
+        HIPCHK(c, hipMemcpy(f.data(), c->d_nodes4, f.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n_a; ++i) memcpy(&q[(size_t)i * RT_QNODE_DWORDS + 12], &f[32ull * i + 24], 16);
+    }
+    const auto la = tree_levels(q.data(), n_all, 0u);
+    const auto ls = n_s ? tree_levels(q.data(), n_all, c->shadow_root) : std::vector<std::pair<uint32_t, uint32_t>>();
+    uint64_t seen_a = 0, seen_s = 0;
+    for (const auto &l : la) seen_a += l.second - l.first;
+    for (const auto &l : ls) seen_s += l.second - l.first;
+    if (seen_a != n_a || seen_s != n_s || (!la.empty() && la.back().second != n_a) ||
+        (!ls.empty() && (ls.front().first != n_a || ls.back().second != n_all)))
+        return fail(c, RT_ERR_STATE, "the tree's levels are not index ranges: no refit");
+    r.steps.clear();
+    for (size_t d = std::max(la.size(), ls.size()); d-- > 0;) {
+        RtRefitStep s = {0u, 0u, 0u, 0u};
+        if (d < la.size()) s.a_first = la[d].first, s.a_count = la[d].second - la[d].first;
+        if (d < ls.size()) s.s_first = ls[d].first, s.s_count = ls[d].second - ls[d].first;
+        r.steps.push_back(s);
+    }
+    HIPCHK(c, hipMalloc(&r.d_steps, r.steps.size() * sizeof(RtRefitStep)));
+    HIPCHK(c, hipMemcpy(r.d_steps, r.steps.data(), r.steps.size() * sizeof(RtRefitStep), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMalloc(&r.d_verts, 12ull * c->n_verts));
+    HIPCHK(c, hipMalloc(&r.d_tbox, 24ull * c->tree_recs));
+    HIPCHK(c, hipMalloc(&r.d_hit0, c->bvh.n_hit));
+    if (n_s) HIPCHK(c, hipMalloc(&r.d_shadow_full, 128ull * n_s));
+    if (!c->d_nodes4q) HIPCHK(c, hipMalloc(&r.d_qscratch, 4ull * RT_QNODE_DWORDS * n_all));
+    HIPCHK(c, hipMalloc(&r.d_nbox, rt_refit_nbox_bytes() * n_all));
+    HIPCHK(c, hipMalloc(&r.d_res, RT_REFIT_RES_WORDS * sizeof(uint32_t)));
+    HIPCHK(c, hipMalloc(&r.d_part, RT_REFIT_AREA_BLOCKS * sizeof(double)));
+    HIPCHK(c, hipEventCreate(&r.ev0));
+    HIPCHK(c, hipEventCreate(&r.ev1));
+    r.ready = true;
+    return RT_OK;
+}
+
+/* rt_set_mesh, and rt_update_mesh's rebuild: the build, then what a later update needs of this
+   mesh — its indices on the host and on the device. */
+static int set_mesh_keep(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
+                         int builder, bool dynamic)
+{
+    refit_free(c);
+    c->have_update = false;
+    const int st = set_mesh_build(c, verts, n_verts, idx, n_tris, builder, dynamic);
+    if (st != RT_OK) return st;
+    if (idx != c->h_idx.data()) c->h_idx.assign(idx, idx + 3ull * n_tris);
+    c->n_verts = n_verts;
+    free_dev(c->d_idx);
+    c->d_idx = nullptr;
+    HIPCHK(c, hipMalloc(&c->d_idx, 12ull * n_tris));
+    HIPCHK(c, hipMemcpy(c->d_idx, idx, 12ull * n_tris, hipMemcpyHostToDevice));
+    return dynamic ? refit_prepare(c) : RT_OK;
+}
+
+int rt_set_mesh(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris)
+try {
+    if (!c || !verts || !idx || !n_verts || !n_tris) return fail(c, RT_ERR_ARG, "empty mesh");
+    HIPCHK(c, hipSetDevice(c->device));
+    return set_mesh_keep(c, verts, n_verts, idx, n_tris, c->builder, c->dynamic);
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_set_mesh_dynamic(rt_ctx *c, int on)
+try {
+    if (!c) return RT_ERR_ARG;
+    c->dynamic = on != 0;
+    return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+int rt_last_mesh_update(const rt_ctx *c, rt_mesh_update_info *out)
+try {
+    if (!c || !out) return RT_ERR_ARG;
+    if (!c->n_tris) return RT_ERR_NO_MESH;
+    if (!c->have_update) return RT_ERR_STATE;
+    *out = c->last_update;
+    return RT_OK;
+} RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
+
+/* rt_update_mesh's other way: the mesh built again from the kept indices, as it was built */
+static int update_rebuild(rt_ctx *c, const float *verts, int flags, uint32_t reason, uint32_t newly)
+{
+    std::vector<float> hv;
+    if (flags & RT_MESH_VERTS_DEVICE) {
+        hv.resize(3ull * c->n_verts);
+        HIPCHK(c, hipMemcpy(hv.data(), c->refit.d_verts, hv.size() * sizeof(float), hipMemcpyDeviceToHost));
+        verts = hv.data();
+    }
+    const std::vector<int32_t> idx = std::move(c->h_idx);
+    c->h_idx.clear();
+    const int st = set_mesh_keep(c, verts, c->n_verts, idx.data(), c->n_tris, c->mesh_builder, c->mesh_dynamic);
+    if (st != RT_OK) return st;
+    c->last_update = {RT_MESH_UPDATE_REBUILT, reason, newly, 0u, 1.0f, 0.0f};
+    c->have_update = true;
+    return RT_OK;
+}
+
+int rt_update_mesh(rt_ctx *c, const float *verts, uint32_t n_verts, int flags)
+try {
+    if (!c || !verts) return fail(c, RT_ERR_ARG, "rt_update_mesh: null argument");
+    if (!c->n_tris || !c->d_nodes4 || !c->d_tris || !c->d_idx) return fail(c, RT_ERR_NO_MESH, "no mesh to update");
+    if (n_verts != c->n_verts) return fail(c, RT_ERR_ARG, "rt_update_mesh: the vertex count differs from the mesh's");
+    HIPCHK(c, hipSetDevice(c->device));
+    rt_ctx::Refit &r = c->refit;
+    if (!r.ready) {
+        const int st = refit_prepare(c);
+        if (st != RT_OK) {
+            refit_free(c);
+            return st;
+        }
+    }
+    hipStream_t st = c->stream;
+    const uint32_t n_tris = c->n_tris, n_hit = c->bvh.n_hit, n_a = c->bvh.n_nodes4;
+    uint32_t res[RT_REFIT_RES_WORDS] = {0u, 0u, 0u, 0u, ~0u, ~0u, ~0u, 0u, 0u, 0u};
+    HIPCHK(c, hipMemcpyAsync(r.d_verts, verts, 12ull * n_verts,
+                             (flags & RT_MESH_VERTS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(r.d_res, res, sizeof(res), hipMemcpyHostToDevice, st));
+    /* look first: nothing of the mesh is written before the host has decided */
+    if (int e = rt_launch_refit_check(r.d_verts, n_verts, c->d_idx, n_tris, c->d_tris, n_hit, r.d_res, st))
+        return hip_fail(c, (hipError_t)e, "k_refit_check");
+    HIPCHK(c, hipMemcpyAsync(res, r.d_res, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (res[RT_REFIT_RES_BAD] & 1u) return fail(c, RT_ERR_ARG, "non-finite or out-of-range vertex coordinate");
+    if (res[RT_REFIT_RES_BAD]) return fail(c, RT_ERR_STATE, "rt_update_mesh: a record's triangle index is out of range");
+    if (res[RT_REFIT_RES_NEWLY])
+        return update_rebuild(c, verts, flags, RT_REFIT_NEWLY_HITTABLE, res[RT_REFIT_RES_NEWLY]);
+    double part[RT_REFIT_AREA_BLOCKS];
+    if (!r.have_area0) { /* the build's own sum, before the first overwrite */
+        if (int e = rt_launch_refit_area(c->d_nodes4, n_a, r.d_part, st))
+            return hip_fail(c, (hipError_t)e, "k_refit_area");
+        HIPCHK(c, hipMemcpyAsync(part, r.d_part, sizeof(part), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        r.area0 = 0.0;
+        for (double p : part) r.area0 += p;
+        r.have_area0 = true;
+    }
+    RtRefitLaunch a;
+    a.nodes4 = c->d_nodes4;
+    a.nodes4_shadow = r.d_shadow_full;
+    a.nodes4q = c->d_nodes4q ? c->d_nodes4q : r.d_qscratch;
+    a.nbox = r.d_nbox;
+    a.tris = c->d_tris;
+    a.tbox = r.d_tbox;
+    a.n_nodes4 = n_a;
+    a.n_nodes4_shadow = c->n_nodes4_shadow;
+    a.n_recs = (uint32_t)c->tree_recs;
+    a.det_cull = c->mesh_det_cull;
+    a.res = r.d_res;
+    HIPCHK(c, hipEventRecord(r.ev0, st));
+    if (int e = rt_launch_refit_records(r.d_verts, c->d_idx, n_tris, n_hit, a.n_recs, c->d_tris, r.d_tbox, r.d_hit0,
+                                        !r.have_hit0, r.d_res, st))
+        return hip_fail(c, (hipError_t)e, "k_refit_records");
+    r.have_hit0 = true;
+    if (int e = rt_launch_refit_levels(a, r.d_steps, r.steps.data(), (uint32_t)r.steps.size(), st))
+        return hip_fail(c, (hipError_t)e, "k_refit_levels");
+    double now = 0.0;
+    if (int e = rt_launch_refit_area(c->d_nodes4, n_a, r.d_part, st))
+        return hip_fail(c, (hipError_t)e, "k_refit_area");
+    HIPCHK(c, hipEventRecord(r.ev1, st));
+    HIPCHK(c, hipMemcpyAsync(res, r.d_res, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(part, r.d_part, sizeof(part), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->mesh_serial++; /* the records have changed: the schedule, the lists and the pilot are the old mesh's */
+    if (res[RT_REFIT_RES_BAD]) return fail(c, RT_ERR_STATE, "rt_update_mesh: a link of the tree is out of range");
+    /* the compressed form holds every node, or none: a change either way is a rebuild (the
+       half-written nodes are replaced with everything else) */
+    const bool had_q = c->d_nodes4q != nullptr;
+    if (had_q ? res[RT_REFIT_RES_QFAIL] != 0u : res[RT_REFIT_RES_QFAIL] == 0u)
+        return update_rebuild(c, verts, flags, RT_REFIT_ENCODING, 0u);
+    for (double p : part) now += p;
+    /* the off-mesh bounds by mesh_bounds' rule */
+    float ext = 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        auto unkey = [](uint32_t key) { return (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key; }; /* k_prep's f2key */
+        const uint32_t ul = unkey(res[RT_REFIT_RES_LO + k]), uh = unkey(res[RT_REFIT_RES_HI + k]);
+        memcpy(&c->mesh_lo[k], &ul, 4);
+        memcpy(&c->mesh_hi[k], &uh, 4);
+        ext = std::max(ext, c->mesh_hi[k] - c->mesh_lo[k]);
+    }
+    const float pad = 1e-3f * ext + 1e-4f;
+    for (int k = 0; k < 3; ++k) {
+        c->mesh_lo[k] -= pad;
+        c->mesh_hi[k] += pad;
+    }
+    c->mesh_bounds_ok = true;
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, r.ev0, r.ev1));
+    c->last_update = {RT_MESH_UPDATE_REFIT, RT_REFIT_OK, 0u, res[RT_REFIT_RES_UNHIT],
+                      r.area0 > 0.0 ? (float)(now / r.area0) : 1.0f, ms};
+    c->have_update = true;
     return RT_OK;
 } RT_CATCH(c ? &const_cast<rt_ctx *>(c)->err : nullptr)
 

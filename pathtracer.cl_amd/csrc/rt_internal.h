@@ -129,6 +129,52 @@ int rt_build_bvh_gpu(const float *verts, uint32_t n_verts, const int32_t *idx, u
 /* Input checks shared by both builders (finite coordinates, indices in range, size limit). */
 bool rt_validate_mesh(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, std::string &err);
 
+/* ---- refit of both trees to new vertex positions (rt_refit.hip) ----
+   All pointers are device memory; every launcher returns a hipError_t as int. */
+/* the result words the refit kernels write (zeroed before k_refit_check, the bounds' keys set to
+   ~0 / 0): a defect mask (1: a non-finite coordinate, 2 / 4: a record or a link out of range),
+   left-out triangles a unit ray can now hit, tree triangles none can hit any more, nodes the
+   compressed form cannot hold, then the ordered-integer keys of the referenced vertices' bounds */
+enum {
+    RT_REFIT_RES_BAD = 0,
+    RT_REFIT_RES_NEWLY = 1,
+    RT_REFIT_RES_UNHIT = 2,
+    RT_REFIT_RES_QFAIL = 3,
+    RT_REFIT_RES_LO = 4,
+    RT_REFIT_RES_HI = 7,
+    RT_REFIT_RES_WORDS = 10
+};
+#define RT_REFIT_AREA_BLOCKS 256 /* partial sums of k_refit_area */
+/* the nodes of one depth of both trees (index ranges in the compressed nodes' numbering) */
+struct RtRefitStep {
+    uint32_t a_first, a_count; /* closest-hit tree */
+    uint32_t s_first, s_count; /* shadow tree (count 0: none, or no such level) */
+};
+struct RtRefitLaunch {
+    float *nodes4;        /* closest-hit tree, rewritten in place */
+    float *nodes4_shadow; /* workspace: the shadow tree's full-precision nodes (NULL without one) */
+    uint32_t *nodes4q;    /* both trees' compressed nodes (a scratch array for a tree without them) */
+    void *nbox;           /* workspace: rt_refit_nbox_bytes() per node of both trees */
+    const float *tris;    /* the records k_refit_records wrote */
+    const float *tbox;    /* their padded boxes, 6 floats per slot */
+    uint32_t n_nodes4, n_nodes4_shadow, n_recs;
+    bool det_cull;
+    uint32_t *res;
+};
+int rt_launch_refit_check(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, const float *tris,
+                          uint32_t n_hit, uint32_t *res, void *stream);
+/* hit0: one byte per tree slot of the closest-hit tree's half (n_hit), written when init: the
+   triangle could be hit when the tree was built (now_unhittable counts those that cannot now) */
+int rt_launch_refit_records(const float *verts, const int32_t *idx, uint32_t n_tris, uint32_t n_hit, uint32_t n_recs,
+                            float *tris, float *tbox, uint8_t *hit0, bool init, uint32_t *res, void *stream);
+/* steps: deepest level first, the same array on the device and on the host (the host's sizes
+   choose the launches: levels that fit one block are folded into one single-block launch) */
+int rt_launch_refit_levels(const RtRefitLaunch &a, const RtRefitStep *steps_dev, const RtRefitStep *steps_host,
+                           uint32_t n_steps, void *stream);
+/* part: RT_REFIT_AREA_BLOCKS doubles, to be added in index order */
+int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, void *stream);
+size_t rt_refit_nbox_bytes(void);
+
 /* ---- kernel launchers (rt_kernels.hip) ---- */
 #ifndef RT_QHEADS
 #define RT_QHEADS 8 /* heads of the multi-head pixel queue (k_tris mq_take) */

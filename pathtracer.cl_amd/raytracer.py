@@ -150,6 +150,30 @@ class RayTracer:
         self._check(self._lib.rt_set_mesh(self._h, _abi.ptr(v), v.shape[0], _abi.ptr(i), i.shape[0]), "rt_set_mesh")
         self._mesh = (v.shape[0], i.shape[0])
 
+    def setMeshDynamic(self, on: bool) -> None:
+        """The next host-built setMesh keeps every triangle in the tree (also those no ray can hit),
+        so that every later updateMesh refits and none has to rebuild."""
+        self._check(self._lib.rt_set_mesh_dynamic(self._h, int(bool(on))), "rt_set_mesh_dynamic")
+
+    def updateMesh(self, verts, device: bool = False) -> dict:
+        """New positions for the vertices of the last setMesh (same count, same indices): both trees
+        are refitted on the device, or rebuilt where a refit cannot stand for a build (the returned
+        rt_mesh_update_info says which, and why).  device=True: `verts` is device memory (a torch
+        tensor, or an address with the mesh's vertex count)."""
+        if device:
+            v, n = verts, (verts.numel() // 3 if hasattr(verts, "numel") else (self._mesh or (0, 0))[0])
+        else:
+            v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+            n = v.shape[0]
+        self._check(self._lib.rt_update_mesh(self._h, _abi.ptr(v), n, _abi.RT_MESH_VERTS_DEVICE if device else 0),
+                    "rt_update_mesh")
+        return self.lastMeshUpdate()
+
+    def lastMeshUpdate(self) -> dict:
+        i = _abi.RtMeshUpdateInfo()
+        self._check(self._lib.rt_last_mesh_update(self._h, ctypes.byref(i)), "rt_last_mesh_update")
+        return {f: getattr(i, f) for f, _ in _abi.RtMeshUpdateInfo._fields_}
+
     def meshInfo(self) -> dict:
         st = _abi.RtMeshStats()
         self._check(self._lib.rt_mesh_info(self._h, ctypes.byref(st)), "rt_mesh_info")
