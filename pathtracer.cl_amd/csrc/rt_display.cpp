@@ -1,0 +1,469 @@
+/*
+ * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
+ * features and the edge-avoiding denoiser (rt_denoise.hip), temporal reprojection
+ * and merge (rt_temporal.hip, §4.10), luminance moments, variance and the variance-guided filter
+ * (rt_variance.hip, §4.11), with their kernel times.  Every call runs through one driver (AuxCall).
+ */
+#include <cmath>
+
+#include "rt_ctx.h"
+#include "rt_math.h"
+
+namespace {
+
+/* A feature / denoise call on `st` begins: its events exist, and it is ordered after the context's
+   pending render the way a render on another stream is (ev_done), and after an earlier such call. */
+int aux_begin(rt_ctx *c, hipStream_t st)
+{
+    for (rt_ctx::StageTime &t : c->stage_time) {
+        HIPCHK(c, t.e0.create());
+        HIPCHK(c, t.e1.create());
+    }
+    HIPCHK(c, c->ev_aux.create(hipEventDisableTiming));
+    if (const int r = wait_last_render(c, st)) return r;
+    return wait_aux(c, st);
+}
+
+/* ... and ends: the next render (rt_render_async) orders itself after ev_aux */
+int aux_end(rt_ctx *c, hipStream_t st)
+{
+    HIPCHK(c, hipEventRecord(c->ev_aux, st));
+    c->aux_stream = st;
+    return RT_OK;
+}
+
+/* growing a display-side buffer: a pending call may still use it */
+int ensure_dev(rt_ctx *c, DevBuf<float> &buf, size_t floats)
+{
+    if (floats <= buf.cap) return RT_OK;
+    if (c->aux_stream) HIPCHK(c, hipEventSynchronize(c->ev_aux));
+    HIPCHK(c, buf.reserve(floats));
+    return RT_OK;
+}
+
+bool frame_ok(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H < (1ull << 28); }
+
+/* One plane of a call's staging area (host buffers only): `floats` floats at `off`, uploaded from
+   `up` before the kernels and downloaded to `down` after them (either may be null). */
+struct Plane {
+    const float *up;
+    float *down;
+    size_t off, floats;
+};
+
+/* The driver of a display-side call: open (device, stream), begin (the staging area for host
+   buffers, aux_begin, the uploads, the stage's first event), the caller's launches, end (the
+   second event, the downloads, aux_end). */
+struct AuxCall {
+    rt_ctx *c;
+    RtStage stage;
+    hipStream_t st = nullptr;
+    bool host = false;
+    const Plane *planes = nullptr;
+    int n_planes = 0;
+
+    int open(void *stream, int flags)
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        st = stream ? (hipStream_t)stream : c->stream;
+        host = !(flags & RT_OUT_DEVICE);
+        return RT_OK;
+    }
+    /* plane i on the device (after begin): in the staging area, or the caller's own buffer */
+    float *at(int i, const float *dev) const { return host ? c->d_dn_stage + planes[i].off : const_cast<float *>(dev); }
+    int begin(const Plane *pl, int n, size_t floats)
+    {
+        planes = pl;
+        n_planes = n;
+        if (host)
+            if (const int r = ensure_dev(c, c->d_dn_stage, floats)) return r;
+        if (const int r = aux_begin(c, st)) return r;
+        if (host)
+            for (int i = 0; i < n_planes; ++i)
+                if (planes[i].up)
+                    HIPCHK(c, hipMemcpyAsync(c->d_dn_stage + planes[i].off, planes[i].up, planes[i].floats * sizeof(float),
+                                             hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipEventRecord(c->stage_time[stage].e0, st));
+        return RT_OK;
+    }
+    int end()
+    {
+        HIPCHK(c, hipEventRecord(c->stage_time[stage].e1, st));
+        c->stage_time[stage].have = true;
+        if (host)
+            for (int i = 0; i < n_planes; ++i)
+                if (planes[i].down)
+                    HIPCHK(c, hipMemcpyAsync(planes[i].down, c->d_dn_stage + planes[i].off, planes[i].floats * sizeof(float),
+                                             hipMemcpyDeviceToHost, st));
+        return aux_end(c, st);
+    }
+};
+
+/* the sync twin of an _async call: its status, then the context's stream drained */
+int finish_sync(rt_ctx *c, int r)
+{
+    if (r != RT_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+/* a stage's kernel time, once it has run */
+int stage_ms(const rt_ctx *c, RtStage s, float *ms)
+{
+    const rt_ctx::StageTime &t = c->stage_time[s];
+    if (hipEventSynchronize(t.e1) != hipSuccess) return RT_ERR_HIP;
+    return hipEventElapsedTime(ms, t.e0, t.e1) == hipSuccess ? RT_OK : RT_ERR_HIP;
+}
+
+/* The a-trous passes' ping-pong: pass i reads the previous pass's output (pass 0: the input) and
+   writes a scratch buffer, the last one the output — through scratch (and the caller's copy
+   afterwards) when that is the buffer it reads (one pass in place). */
+float *pass_dst(bool last, float *out, const float *src, DevBuf<float> tmp[2])
+{
+    return (last && out != src) ? out : tmp[src == tmp[0] ? 1 : 0].p;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_render_features_async(rt_ctx *c, float *feat, uint32_t W, uint32_t H, int kernel, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!feat) return fail(c, RT_ERR_ARG, "null feature buffer");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (kernel < RT_KERNEL_SPHERES || kernel > RT_KERNEL_TRIS) return fail(c, RT_ERR_ARG, "unknown kernel");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_render_features: flags other than RT_OUT_DEVICE");
+    if (kernel == RT_KERNEL_TRIS && c->n_tris == 0) return fail(c, RT_ERR_NO_MESH, "no mesh set");
+    if (kernel != RT_KERNEL_TRIS && c->spheres.empty()) return fail(c, RT_ERR_NO_SCENE, "no spheres set");
+    AuxCall x = {c, RT_ST_FEATURES};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    const Plane pl[] = {{nullptr, feat, 0, 8 * px}};
+    RtFeatLaunch a{};
+    a.cam = frame_camera(c, W);
+    a.W = W;
+    a.H = H;
+    int trav = 0;
+    if (kernel == RT_KERNEL_TRIS) {
+        trav = trav_kind(c);
+        a.nodes = trav_nodes(c);
+        a.tris = c->d_tris;
+        a.n_tris = c->n_tris;
+        a.spill_cap = spill_cap(c);
+        if (a.spill_cap) {
+            const size_t blocks = ((size_t)W * H + RT_BLOCK - 1) / RT_BLOCK;
+            /* (growing it frees the old area: hipFree waits for whatever still runs on it) */
+            if (const int r = ensure_spill(c, blocks * RT_BLOCK * a.spill_cap)) return r;
+        }
+        a.spill = c->d_spill;
+    } else {
+        a.spheres = c->d_spheres;
+        a.n_spheres = (uint32_t)c->spheres.size();
+    }
+    if (const int r = x.begin(pl, 1, 8 * px)) return r;
+    a.feat = x.at(0, feat);
+    const int e = rt_launch_features(a, trav, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "feature kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_render_features(rt_ctx *c, float *feat, uint32_t W, uint32_t H, int kernel, int flags)
+try {
+    return finish_sync(c, rt_render_features_async(c, feat, W, H, kernel, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_denoise_defaults(rt_denoise_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->iterations = 5;
+    p->sigma_color = 2.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_denoise_async(rt_ctx *c, const float *in, const float *feat, float *out, uint32_t W, uint32_t H,
+                     const rt_denoise_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!in || !feat || !out || !prm) return fail(c, RT_ERR_ARG, "rt_denoise: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_denoise: flags other than RT_OUT_DEVICE");
+    if (prm->iterations < 1 || prm->iterations > 8) return fail(c, RT_ERR_ARG, "rt_denoise: iterations outside 1..8");
+    const float sig[3] = {prm->sigma_color, prm->sigma_normal, prm->sigma_plane};
+    for (float s : sig)
+        if (!(s > 0.0f)) return fail(c, RT_ERR_ARG, "rt_denoise: a sigma is not positive"); /* <= 0 or NaN */
+    /* the inverse variances, in float (+INFINITY: 0, the term is off) */
+    const float isn = 1.0f / (sig[1] * sig[1]), isp = 1.0f / (sig[2] * sig[2]);
+    AuxCall x = {c, RT_ST_DENOISE};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    const uint32_t n = prm->iterations;
+    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) /* (three passes and more alternate between two) */
+        if (const int r = ensure_dev(c, c->d_dn_tmp[k], 4 * px)) return r;
+    /* staged: colour (filtered in place there: the last pass never reads its destination), then the
+       two feature planes */
+    const Plane pl[] = {{in, out, 0, 4 * px}, {feat, nullptr, 4 * px, 8 * px}};
+    if (const int r = x.begin(pl, 2, 12 * px)) return r;
+    const float *dfeat = x.at(1, feat);
+    float *dout = x.at(0, out);
+    const float *src = x.at(0, in);
+    for (uint32_t i = 0; i < n; ++i) {
+        const float sc = ldexpf(prm->sigma_color, -(int)i); /* the colour tolerance halves every pass */
+        const float isc = 1.0f / (sc * sc);
+        float *dst = pass_dst(i + 1 == n, dout, src, c->d_dn_tmp);
+        const int e = rt_launch_atrous(src, dfeat, dst, W, H, 1u << i, isc, isn, isp, x.st);
+        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
+        src = dst;
+    }
+    if (src != dout) HIPCHK(c, hipMemcpyAsync(dout, src, 4 * px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_denoise(rt_ctx *c, const float *in, const float *feat, float *out, uint32_t W, uint32_t H,
+               const rt_denoise_params *prm, int flags)
+try {
+    return finish_sync(c, rt_denoise_async(c, in, feat, out, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_features_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->stage_time[RT_ST_FEATURES].have) return RT_ERR_STATE;
+    return stage_ms(c, RT_ST_FEATURES, ms);
+} RT_CATCH(err_of(c))
+
+int rt_last_denoise_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->stage_time[RT_ST_DENOISE].have) return RT_ERR_STATE;
+    return stage_ms(c, RT_ST_DENOISE, ms);
+} RT_CATCH(err_of(c))
+
+/* ---- temporal reprojection of the displayed frame ------- */
+
+int rt_reproject_defaults(rt_reproject_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->plane_tol = 0.01f;
+    p->normal_min = 0.9f;
+    p->max_history = 32.0f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_reproject_async(rt_ctx *c, const float *prev_rgba, const float *prev_len, const float *prev_feat,
+                       const rt_camera *prev_cam, const float *cur_feat, float *out_rgba, float *out_len, uint32_t W,
+                       uint32_t H, const rt_reproject_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!prev_rgba || !prev_len || !prev_feat || !prev_cam || !cur_feat || !out_rgba || !out_len || !prm)
+        return fail(c, RT_ERR_ARG, "rt_reproject: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_reproject: flags other than RT_OUT_DEVICE");
+    if (!(prm->plane_tol >= 0.0f)) return fail(c, RT_ERR_ARG, "rt_reproject: plane_tol negative or NaN");
+    if (prm->normal_min != prm->normal_min) return fail(c, RT_ERR_ARG, "rt_reproject: normal_min is NaN");
+    if (!(prm->max_history >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_reproject: max_history below 1 or NaN");
+    if (out_rgba == prev_rgba || out_len == prev_len)
+        return fail(c, RT_ERR_ARG, "rt_reproject: an output is the previous frame's buffer");
+    AuxCall x = {c, RT_ST_REPROJECT};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged: the float4 streams first (px may be odd), then the two length planes */
+    const Plane pl[] = {{prev_rgba, nullptr, 0, 4 * px},      {prev_feat, nullptr, 4 * px, 8 * px},
+                        {cur_feat, nullptr, 12 * px, 8 * px}, {prev_len, nullptr, 24 * px, px},
+                        {nullptr, out_rgba, 20 * px, 4 * px}, {nullptr, out_len, 25 * px, px}};
+    if (const int r = x.begin(pl, 6, 26 * px)) return r;
+    const int e = rt_launch_reproject(x.at(0, prev_rgba), x.at(3, prev_len), x.at(1, prev_feat), *prev_cam, x.at(2, cur_feat),
+                                      x.at(4, out_rgba), x.at(5, out_len), W, H, prm->plane_tol, prm->normal_min,
+                                      prm->max_history, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "reprojection kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_reproject(rt_ctx *c, const float *prev_rgba, const float *prev_len, const float *prev_feat,
+                 const rt_camera *prev_cam, const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H,
+                 const rt_reproject_params *prm, int flags)
+try {
+    return finish_sync(c, rt_reproject_async(c, prev_rgba, prev_len, prev_feat, prev_cam, cur_feat, out_rgba, out_len, W, H,
+                                             prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_temporal_merge_async(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                            float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags,
+                            void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!hist_rgba || !hist_len || !cur_rgba || !out_rgba || !out_len)
+        return fail(c, RT_ERR_ARG, "rt_temporal_merge: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_temporal_merge: flags other than RT_OUT_DEVICE");
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_temporal_merge: n_cur below 1 or NaN");
+    if (!(max_history >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_temporal_merge: max_history below 1 or NaN");
+    if (out_rgba == cur_rgba) return fail(c, RT_ERR_ARG, "rt_temporal_merge: the output is the current frame's buffer");
+    AuxCall x = {c, RT_ST_MERGE};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged, and merged in place there */
+    const Plane pl[] = {{hist_rgba, out_rgba, 0, 4 * px}, {cur_rgba, nullptr, 4 * px, 4 * px}, {hist_len, out_len, 8 * px, px}};
+    if (const int r = x.begin(pl, 3, 9 * px)) return r;
+    const int e = rt_launch_temporal_merge(x.at(0, hist_rgba), x.at(2, hist_len), x.at(1, cur_rgba), n_cur, max_history,
+                                           x.at(0, out_rgba), x.at(2, out_len), W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "temporal merge kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_temporal_merge(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                      float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_temporal_merge_async(c, hist_rgba, hist_len, cur_rgba, n_cur, max_history, out_rgba, out_len, W,
+                                                  H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_reproject_ms(const rt_ctx *c, float *reproject_ms, float *merge_ms)
+try {
+    if (!c || (!reproject_ms && !merge_ms)) return RT_ERR_ARG;
+    if ((reproject_ms && !c->stage_time[RT_ST_REPROJECT].have) || (merge_ms && !c->stage_time[RT_ST_MERGE].have))
+        return RT_ERR_STATE;
+    if (reproject_ms)
+        if (const int r = stage_ms(c, RT_ST_REPROJECT, reproject_ms)) return r;
+    return merge_ms ? stage_ms(c, RT_ST_MERGE, merge_ms) : RT_OK;
+} RT_CATCH(err_of(c))
+
+/* ---- variance-guided display filter --------------------- */
+
+int rt_denoise_var_defaults(rt_denoise_var_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->iterations = 5;
+    p->sigma_lum = 4.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    p->min_len = 4.0f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_moments_accumulate_async(rt_ctx *c, const float *prev_rgba, const float *cur_rgba, float n_cur,
+                                const float *mom_in, float *mom_out, uint32_t W, uint32_t H, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_moments_accumulate: n_cur below 1 or NaN");
+    const bool first = n_cur == 1.0f; /* the view's first frame: no history is read */
+    if (!cur_rgba || !mom_out || (!first && (!prev_rgba || !mom_in)))
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_moments_accumulate: flags other than RT_OUT_DEVICE");
+    if (mom_out == prev_rgba || mom_out == cur_rgba)
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate: the output is an accumulation buffer");
+    AuxCall x = {c, RT_ST_MOMENTS};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged: prev, cur, then the moments, accumulated in place there */
+    const Plane pl[] = {{cur_rgba, nullptr, 4 * px, 4 * px},
+                        {first ? nullptr : prev_rgba, nullptr, 0, 4 * px},
+                        {first ? nullptr : mom_in, mom_out, 8 * px, 4 * px}};
+    if (const int r = x.begin(pl, 3, 12 * px)) return r;
+    const int e = rt_launch_moments(x.at(1, prev_rgba), x.at(0, cur_rgba), n_cur, x.at(2, mom_in), x.at(2, mom_out), W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "moments kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_moments_accumulate(rt_ctx *c, const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in,
+                          float *mom_out, uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_moments_accumulate_async(c, prev_rgba, cur_rgba, n_cur, mom_in, mom_out, W, H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_variance_async(rt_ctx *c, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
+                      float *out_var, uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!disp_rgba || !mom_rgba || !len || !feat || !out_var || !prm) return fail(c, RT_ERR_ARG, "rt_variance: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_variance: flags other than RT_OUT_DEVICE");
+    if (!(prm->min_len >= 2.0f)) return fail(c, RT_ERR_ARG, "rt_variance: min_len below 2 or NaN");
+    if (!(prm->sigma_normal > 0.0f) || !(prm->sigma_plane > 0.0f))
+        return fail(c, RT_ERR_ARG, "rt_variance: a sigma is not positive"); /* <= 0 or NaN */
+    const float isn = 1.0f / (prm->sigma_normal * prm->sigma_normal), isp = 1.0f / (prm->sigma_plane * prm->sigma_plane);
+    AuxCall x = {c, RT_ST_VARIANCE};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged: the float4 streams first (px may be odd), then the two planes */
+    const Plane pl[] = {{disp_rgba, nullptr, 0, 4 * px}, {mom_rgba, nullptr, 4 * px, 4 * px}, {feat, nullptr, 8 * px, 8 * px},
+                        {len, nullptr, 16 * px, px},     {nullptr, out_var, 17 * px, px}};
+    if (const int r = x.begin(pl, 5, 18 * px)) return r;
+    const int e = rt_launch_variance(x.at(0, disp_rgba), x.at(1, mom_rgba), x.at(3, len), x.at(2, feat), x.at(4, out_var), W, H,
+                                     isn, isp, prm->min_len, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "variance kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_variance(rt_ctx *c, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
+                float *out_var, uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags)
+try {
+    return finish_sync(c, rt_variance_async(c, disp_rgba, mom_rgba, len, feat, out_var, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_denoise_var_async(rt_ctx *c, const float *in, const float *in_var, const float *feat, float *out, float *out_var,
+                         uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!in || !in_var || !feat || !out || !prm) return fail(c, RT_ERR_ARG, "rt_denoise_var: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_denoise_var: flags other than RT_OUT_DEVICE");
+    if (prm->iterations < 1 || prm->iterations > 8) return fail(c, RT_ERR_ARG, "rt_denoise_var: iterations outside 1..8");
+    const float sig[3] = {prm->sigma_lum, prm->sigma_normal, prm->sigma_plane};
+    for (float s : sig)
+        if (!(s > 0.0f)) return fail(c, RT_ERR_ARG, "rt_denoise_var: a sigma is not positive"); /* <= 0 or NaN */
+    const float isn = 1.0f / (sig[1] * sig[1]), isp = 1.0f / (sig[2] * sig[2]);
+    const int lum_on = sig[0] < rt_inff(); /* +INFINITY: the luminance term is off (inf * 0 would be a NaN) */
+    AuxCall x = {c, RT_ST_DENOISE_VAR};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    const uint32_t n = prm->iterations;
+    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) { /* (three passes and more alternate between two) */
+        if (const int r = ensure_dev(c, c->d_dn_tmp[k], 4 * px)) return r;
+        if (const int r = ensure_dev(c, c->d_var_tmp[k], px)) return r;
+    }
+    /* staged: colour, the two feature planes, then the variance plane; filtered in place there
+       (the last pass never reads its destination) */
+    const Plane pl[] = {{in, out, 0, 4 * px}, {feat, nullptr, 4 * px, 8 * px}, {in_var, out_var, 12 * px, px}};
+    if (const int r = x.begin(pl, 3, 13 * px)) return r;
+    const float *dfeat = x.at(1, feat);
+    float *dout = x.at(0, out), *dvout = x.host && !out_var ? nullptr : x.at(2, out_var);
+    /* as rt_denoise, the colour and the variance side by side */
+    const float *src = x.at(0, in), *vsrc = x.at(2, in_var);
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool last = i + 1 == n;
+        float *dst = pass_dst(last, dout, src, c->d_dn_tmp);
+        float *vdst = pass_dst(last, dvout, vsrc, c->d_var_tmp);
+        const int e = rt_launch_atrous_var(src, vsrc, dfeat, dst, vdst, W, H, 1u << i, sig[0], lum_on, isn, isp, x.st);
+        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
+        src = dst;
+        vsrc = vdst;
+    }
+    if (src != dout) HIPCHK(c, hipMemcpyAsync(dout, src, 4 * px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    if (dvout && vsrc != dvout) HIPCHK(c, hipMemcpyAsync(dvout, vsrc, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_denoise_var(rt_ctx *c, const float *in, const float *in_var, const float *feat, float *out, float *out_var,
+                   uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags)
+try {
+    return finish_sync(c, rt_denoise_var_async(c, in, in_var, feat, out, out_var, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_variance_ms(const rt_ctx *c, float *moments_ms, float *variance_ms, float *denoise_var_ms)
+try {
+    if (!c || (!moments_ms && !variance_ms && !denoise_var_ms)) return RT_ERR_ARG;
+    float *out[3] = {moments_ms, variance_ms, denoise_var_ms};
+    const RtStage stage[3] = {RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR};
+    for (int k = 0; k < 3; ++k)
+        if (out[k] && !c->stage_time[stage[k]].have) return RT_ERR_STATE;
+    for (int k = 0; k < 3; ++k)
+        if (out[k])
+            if (const int r = stage_ms(c, stage[k], out[k])) return r;
+    return RT_OK;
+} RT_CATCH(err_of(c))
+
+} /* extern "C" */

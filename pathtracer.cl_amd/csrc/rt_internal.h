@@ -1,6 +1,6 @@
 /*
- * rt_internal.h — host-side interface between the C-ABI layer (rt_host.cpp),
- * the BVH builder (rt_bvh.cpp) and the HIP kernels (rt_kernels.hip).
+ * rt_internal.h — host-side interface between the C-ABI layer (rt_host.cpp, rt_mesh.cpp,
+ * rt_render.cpp, rt_display.cpp), the BVH builder (rt_bvh.cpp) and the HIP kernels (rt_kernels.hip).
  * Not part of the public boundary.
  */
 #ifndef RT_INTERNAL_H
@@ -26,7 +26,7 @@ int rt_exception_status(std::string *err) noexcept;
    with k_tris's other per-lane LDS — pixel sum and throughput, list word, hit normal, the shadow
    cache's 16-bit word: 31,744 B per block in all — keeps 5 blocks per CU; one block more of LDS
    measured 3.5 % slower: profiles/r03z, r03zb); deeper entries go to a per-lane global spill tail sized from the tree
-   (rt_host.cpp spill_cap). */
+   (rt_ctx.h spill_cap). */
 #ifndef RT_STACK_DEPTH
 #define RT_STACK_DEPTH 20
 #endif
@@ -278,7 +278,7 @@ struct RtTriLaunch {
        recorded) */
     uint32_t *pixel_iter;
     uint32_t take_exact; /* k_tris: queue takes of exactly the idle lanes' items, no wave-private batch */
-    /* the mesh's bounds padded by 1e-3 of its extent (rt_host.cpp mesh_bounds): a box-path query
+    /* the mesh's bounds padded by 1e-3 of its extent (rt_mesh.cpp mesh_bounds): a box-path query
        (a bounce off the box or a shadow ray leaving it) whose segment misses them meets no
        triangle and is answered in the path advance, without a traversal (0: not used) */
     uint32_t mesh_bounds;

@@ -201,7 +201,7 @@ __device__ __forceinline__ uint32_t global_row(const L &a, uint32_t yl)
 /* A pixel's camera-ray candidate list (k_pixel_lists) packed in one word, read when the lane takes
    the pixel instead of before every sample's camera query (one dependent load less per sample):
    (first slot / 8) << RT_LIST_BITS | (count - 1) — lists start on 8-record multiples and slots stay
-   below 2^28 (rt_host.cpp list_cap), so the word stays below RT_LPACK_EMPTY. */
+   below 2^28 (rt_render.cpp list_cap), so the word stays below RT_LPACK_EMPTY. */
 constexpr uint32_t RT_LPACK_NONE = 0xffffffffu, RT_LPACK_EMPTY = 0xfffffffeu;
 __device__ __forceinline__ uint32_t list_pack(const RtTriLaunch &a, uint32_t x, uint32_t yl, uint32_t tiles_x)
 {
@@ -287,7 +287,7 @@ __device__ __forceinline__ void coop_begin(CoopQuery &q, V3 o, V3 d, float tmax)
    tested, the latest in list order.  The group's whole query is on its stack (q.sp entries: the
    root, or the list blocks, pushed at the start); the item assignment is computed alike in the
    4 lanes.  Above `multi_sp` entries a round takes ONE item: 4 nodes add at most 12 entries, and
-   a one-item depth-first walk from there at most the tree's worst stack (rt_host.cpp), so the
+   a one-item depth-first walk from there at most the tree's worst stack (rt_render.cpp), so the
    stack stays inside the group's RT_COOP_STACK words. */
 __device__ __forceinline__ bool coop_round(const float4 *__restrict__ nodes, const float4 *__restrict__ tris,
                                            CoopQuery &q, const CoopStack &gst, V3 o, V3 d, float tmin,
@@ -396,7 +396,7 @@ __device__ __forceinline__ bool coop_round(const float4 *__restrict__ nodes, con
     const int total = quad_dpp<0x00>(nh) + h1 + h2 + h3;
     const int above = (sub < 1 ? h1 : 0) + (sub < 2 ? h2 : 0) + (sub < 3 ? h3 : 0);
     const int sp = q.sp - nfull;
-    if (sp + total > CoopStack::kCap) { /* cannot happen (multi_sp bound, rt_host.cpp): reported, not clamped */
+    if (sp + total > CoopStack::kCap) { /* cannot happen (multi_sp bound, rt_render.cpp): reported, not clamped */
         if (sub == 0) atomicOr(guard, (unsigned long long)RT_GUARD_STACK);
         return true;
     }
@@ -2165,7 +2165,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_trace_rays(const float4 *__restric
     }
 }
 
-/* Cost probe for the LPT pixel queue (rt_host.cpp tile_order): per pixel, an n x n grid
+/* Cost probe for the LPT pixel queue (rt_render.cpp tile_order): per pixel, an n x n grid
    (probe_n, default 2) of camera rays (the pixel's samples are stratified over its area, so silhouette pixels mix
    mesh and box paths) — each ray's closest-hit query and, when it hits the mesh, one shadow
    query per light from the hit point toward the light's centre — with the per-lane

@@ -88,7 +88,7 @@ __global__ void k_refit_check(const float *__restrict__ verts, uint32_t n_verts,
         const float *p2 = verts + 3ull * (uint32_t)idx[3ull * t + 2];
         if (!never_hit(a, p1, p2)) ++newly;
     }
-    /* bounds of the vertices the triangles use (rt_host.cpp mesh_bounds) */
+    /* bounds of the vertices the triangles use (rt_mesh.cpp mesh_bounds) */
     uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
     for (uint64_t i = t0; i < 3ull * n_tris; i += stride) {
         const float *v = verts + 3ull * (uint32_t)idx[i];

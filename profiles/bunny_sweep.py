@@ -1,6 +1,6 @@
 """Sweep k_tris's stepping knobs on one context (GPU box): for each setting the frame's kernel
 time (median of --reps renders) with RTMI_FETCH_K / RTMI_FETCH_FRAC / RTMI_GRID_BLOCKS set
-(rt_host.cpp reads them at every render).  Settings alternate round after round.
+(rt_render.cpp reads them at every render).  Settings alternate round after round.
 
     python profiles/bunny_sweep.py [--config bunny] [--reps 5] [--rounds 3] [--lib build.so] 24:24:0 16:24:0 ...
     (K:FRAC:GRID; GRID 0 = the host's grid)

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pathtracer_rt.h"
+#include "rt_ctx.h"
 #include "rt_internal.h"
 
 extern "C" {
@@ -191,6 +192,11 @@ int run_host()
     check(st != RT_OK ? c == nullptr : c != nullptr, "rt_create status");
     if (c) rt_destroy(c);
     check(rt_create(0, nullptr) == RT_ERR_ARG, "rt_create null");
+    if (st != RT_OK) { /* no device: a buffer that cannot be allocated stays empty, and says so */
+        DevBuf<float> buf;
+        check(buf.reserve(16) != hipSuccess && buf.p == nullptr && buf.cap == 0, "DevBuf::reserve without a device");
+        (void)hipGetLastError();
+    }
     check(rt_render(nullptr, nullptr, 1, 1, 0, RT_KERNEL_TRIS, nullptr, 0) == RT_ERR_ARG, "render null ctx");
     std::printf("host ok\n");
     return g_fail;

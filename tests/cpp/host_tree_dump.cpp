@@ -4,7 +4,7 @@
  *
  *   host_tree_dump verts.f32 idx.i32 out.bin [lights.f32 [light_weight]]
  *
- * The two trees are built and laid out as rt_set_mesh does (rt_host.cpp): the closest-hit tree
+ * The two trees are built and laid out as rt_set_mesh does (rt_mesh.cpp): the closest-hit tree
  * with cost weight 0; with lights, a second tree with the context's weight (RtBvh's default
  * unless given), its compressed nodes after the first tree's, inner links offset by the first
  * tree's node count and leaf slots by n_tris, its triangle records after the first tree's.

@@ -1,4 +1,4 @@
-"""The padded mesh bounds behind k_tris's off-mesh box paths (rt_host.cpp `mesh_bounds`, DESIGN.md
+"""The padded mesh bounds behind k_tris's off-mesh box paths (rt_mesh.cpp `mesh_bounds`, DESIGN.md
 §4.7) — CPU only.
 
 A short frame answers a box-path query (a bounce off the box, or a shadow ray leaving it) without a
@@ -17,7 +17,7 @@ RT_SMALL_F = np.float32(1e-4)
 
 
 def padded_bounds(verts, idx):
-    """rt_host.cpp mesh_bounds: the used vertices' box, grown by 1e-3 of its extent + 1e-4 (float32)."""
+    """rt_mesh.cpp mesh_bounds: the used vertices' box, grown by 1e-3 of its extent + 1e-4 (float32)."""
     v = verts[np.unique(idx.reshape(-1))]
     lo, hi = v.min(axis=0).astype(np.float32), v.max(axis=0).astype(np.float32)
     pad = np.float32(1e-3) * np.float32((hi - lo).max()) + np.float32(1e-4)

@@ -1,5 +1,5 @@
 """The arithmetic behind the speculated mesh pixels' chunk seeds (rt_kernels.hip
-`mwc_jump`, rt_host.cpp `spec_setup`): each of frand's two MWC generators (rng.h:9-47,
+`mwc_jump`, rt_render.cpp `spec_setup`): each of frand's two MWC generators (rng.h:9-47,
 x <- A (x & 0xffff) + (x >> 16)) is x <- A x mod M, M = A 2^16 - 1, on the states below M, so k
 draws are one multiplication by A^k mod M; states at or above M reach that range within 2 steps
 (M itself is a fixed point), and A^-1 = 2^16 mod M undoes the canonicalising steps.  CPU-only:
