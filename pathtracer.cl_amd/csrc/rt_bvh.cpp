@@ -278,7 +278,7 @@ bool rt_validate_mesh(const float *verts, uint32_t n_verts, const int32_t *idx, 
 }
 
 /* True when no ray of the kernel can ever accept this triangle.  Moller-Trumbore
-   (geometryFuncs.h:167, rt_kernels.hip mt_test) rejects |det| < 1e-4 with
+   (geometryFuncs.h:167, rt_traverse.h mt_test) rejects |det| < 1e-4 with
    det = dot(cross(d, e2), e1) evaluated in float.  Exactly, |det| <= |d| |e2 x e1|, and
    every query direction is unit length (camera rays, light samples, Lambert bounces:
    |d| <= 1.001 covers their rounding).  The float evaluation adds at most

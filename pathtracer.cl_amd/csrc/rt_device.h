@@ -7,7 +7,7 @@
  * -ffp-contract=off; HIP's f32 division and sqrt are correctly rounded).
  * Data layout and control flow are the MI355X design:
  * vectors live in registers as V3, scene records are read through scalar
- * loads, and the path state machine lives in rt_kernels.hip.
+ * loads, and the path state machine lives in rt_tris.hip (k_tris).
  */
 #ifndef RT_DEVICE_H
 #define RT_DEVICE_H

@@ -1,6 +1,7 @@
 /*
  * rt_internal.h — host-side interface between the C-ABI layer (rt_host.cpp, rt_mesh.cpp,
- * rt_render.cpp, rt_display.cpp), the BVH builder (rt_bvh.cpp) and the HIP kernels (rt_kernels.hip).
+ * rt_render.cpp, rt_display.cpp), the BVH builder (rt_bvh.cpp) and the HIP kernels (the .hip files:
+ * each launcher's prototype below names the file that defines it).
  * Not part of the public boundary.
  */
 #ifndef RT_INTERNAL_H
@@ -175,7 +176,8 @@ int rt_launch_refit_levels(const RtRefitLaunch &a, const RtRefitStep *steps_dev,
 int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, void *stream);
 size_t rt_refit_nbox_bytes(void);
 
-/* ---- kernel launchers (rt_kernels.hip) ---- */
+/* ---- the render kernels' launch structs and launchers (rt_tris.hip, rt_split.hip, rt_spheres.hip,
+   rt_lists.hip, rt_sched.hip, rt_denoise.hip, rt_temporal.hip, rt_variance.hip) ---- */
 #ifndef RT_QHEADS
 #define RT_QHEADS 8 /* heads of the multi-head pixel queue (k_tris mq_take) */
 #endif
@@ -341,71 +343,45 @@ struct RtSphLaunch {
 /* traversal kinds (kernel template parameter) */
 enum { RT_TRAV_LINEAR = 0, RT_TRAV_BVH4 = 2, RT_TRAV_BVH4Q = 4 };
 
+/* -- rt_tris.hip -- */
 int rt_launch_tris(const RtTriLaunch &a, int trav, bool count, int grid_blocks, void *stream);
+/* Persistent-grid size for the triangle kernel on this device; form: RT_FORM_*. */
+enum { RT_FORM_PLAIN = 0, RT_FORM_SPLIT = 1 };
+int rt_tris_grid_blocks(int device, int trav, bool count, int form, int *blocks);
 /* a render's counters into the host's mapped pinned copy, then the counters and queue cursors
    zeroed for the next render (n_zero 64-bit words from dev) */
 int rt_launch_counters_out(unsigned long long *dev, unsigned long long *host_mapped, unsigned long long *totals,
                            uint32_t n_cnt, uint32_t n_zero, void *stream);
+/* -- rt_split.hip -- */
 /* Sample-split renders: the seed pass (grid a.split_seed_blocks, cursor a.split_counter reset
    first) and the in-order sums; rt_launch_tris runs the chunk tasks (a.split_chunks > 0). */
 int rt_launch_split_seeds(const RtTriLaunch &a, void *stream);
 int rt_launch_split_finish(const RtTriLaunch &a, void *stream);
+/* -- rt_spheres.hip -- */
 int rt_launch_spheres(const RtSphLaunch &a, bool single_sample, void *stream);
 int rt_launch_trace_rays(const float *nodes, const float *tris, uint32_t n_tris, const rt_ray *rays, uint32_t n,
                          int any_hit, int trav, int32_t *spill, uint32_t spill_cap, int32_t *out_idx, float *out_t,
                          unsigned long long *counters, void *stream); /* counters: NULL, or counting (queries, nodes, tests, leaves) */
-/* First-hit feature buffers and the display filter (rt_denoise.hip).  feat: 2 planes of W x H
-   float4 on the device, (P, t) then (N, surface id bits).  spheres != NULL: the sphere kernels'
-   scene (trav ignored); else the mesh through traversal kind `trav`, spill indexed by block
-   (ceil(W H / RT_BLOCK) blocks of RT_BLOCK lanes, spill_cap entries each). */
-struct RtFeatLaunch {
-    float *feat;
-    const float *nodes;
-    const float *tris;
-    uint32_t n_tris;
-    const rt_sphere *spheres;
-    uint32_t n_spheres;
-    rt_camera cam;
-    uint32_t W, H;
-    int32_t *spill;
-    uint32_t spill_cap;
-};
-int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
-/* One a-trous pass at tap distance `step` with the inverse variances of its colour, normal and
-   plane terms; col, feat and out are device buffers, out apart from col. */
-int rt_launch_atrous(const float *col, const float *feat, float *out, uint32_t W, uint32_t H, uint32_t step, float isc,
-                     float isn, float isp, void *stream);
-/* Temporal reprojection of the displayed frame (rt_temporal.hip): device buffers;
-   the outputs of the reprojection apart from its inputs, those of the merge possibly its history. */
-int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &prev_cam,
-                        const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H, float plane_tol,
-                        float normal_min, float max_history, void *stream);
-int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
-                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
-/* The variance-guided display filter (rt_variance.hip): device buffers.  The
-   moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in.  One filter
-   pass at tap distance `step`: out / out_var apart from col / var, out_var possibly NULL; lum_on == 0
-   switches the luminance term off. */
-int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
-                      uint32_t W, uint32_t H, void *stream);
-int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
-                       uint32_t W, uint32_t H, float isn, float isp, float min_len, void *stream);
-int rt_launch_atrous_var(const float *col, const float *var, const float *feat, float *out, float *out_var, uint32_t W,
-                         uint32_t H, uint32_t step, float sigma_lum, int lum_on, float isn, float isp, void *stream);
+/* Seed-row halo: copy whole rows (both planes) of the seed layout to / from a packed
+   buffer [plane][i][x] of 2 * n * wpad words (rows: device array of n row indices). */
+int rt_launch_seed_rows(uint32_t *seeds, uint32_t wpad, uint32_t hpad, const uint32_t *rows, uint32_t n,
+                        uint32_t *buf, bool unpack, void *stream);
+/* -- rt_lists.hip -- */
 /* Camera-ray candidate lists for the launch's pixels (writes a.pixel_lists and the list
    records in the triangle buffer at a.list_base); nodes4 = full-precision 4-wide tree,
    q4 = compressed nodes (their normal boxes; may be NULL). */
 int rt_launch_pixel_lists(const RtTriLaunch &a, const float *nodes4, const uint32_t *q4, uint16_t *codes,
                           uint32_t *tile_base, void *stream);
+/* -- rt_sched.hip -- */
 /* Scheduling probe: per pixel the mesh hits of a grid of probe rays and the traversal steps of
-   their queries (rt_kernels.hip). */
+   their queries. */
 int rt_launch_probe_cost(const RtTriLaunch &a, int grid_blocks, uint32_t *out, void *stream);
 /* Per stripe of stripe_rows rows of a W x H probe (rt_launch_probe_cost over the whole frame, pn2 rays
    per pixel): out[2 s] = pixels with a probe ray that missed the mesh, out[2 s + 1] = the probe steps
    of the others (rt_partition_stripes) */
 int rt_launch_stripe_costs(const uint32_t *probe, uint32_t W, uint32_t H, uint32_t stripe_rows, uint32_t pn2,
                            unsigned long long *out, void *stream);
-/* The pixel-queue schedule from the probe, on the device (rt_sched.hip): LPT tile order, box
+/* The pixel-queue schedule from the probe, on the device: LPT tile order, box
    flags and their exclusive scan, pixel classes with the long chains' slots. */
 struct RtSchedScratch {
     void *tmp = nullptr; /* hipCUB temporary storage */
@@ -430,12 +406,46 @@ int rt_sched_box_scan(RtSchedScratch &s, const uint32_t *flags, uint32_t npx, ui
                       uint32_t row, void *stream);
 int rt_sched_classify(const RtSchedScratch &s, uint32_t npx, uint32_t slots, int32_t *cls, uint32_t *slot_pixel,
                       void *stream);
-/* Seed-row halo: copy whole rows (both planes) of the seed layout to / from a packed
-   buffer [plane][i][x] of 2 * n * wpad words (rows: device array of n row indices). */
-int rt_launch_seed_rows(uint32_t *seeds, uint32_t wpad, uint32_t hpad, const uint32_t *rows, uint32_t n,
-                        uint32_t *buf, bool unpack, void *stream);
-/* Persistent-grid size for the triangle kernel on this device; form: RT_FORM_*. */
-enum { RT_FORM_PLAIN = 0, RT_FORM_SPLIT = 1 };
-int rt_tris_grid_blocks(int device, int trav, bool count, int form, int *blocks);
+/* -- rt_denoise.hip -- */
+/* First-hit feature buffers and the display filter.  feat: 2 planes of W x H
+   float4 on the device, (P, t) then (N, surface id bits).  spheres != NULL: the sphere kernels'
+   scene (trav ignored); else the mesh through traversal kind `trav`, spill indexed by block
+   (ceil(W H / RT_BLOCK) blocks of RT_BLOCK lanes, spill_cap entries each). */
+struct RtFeatLaunch {
+    float *feat;
+    const float *nodes;
+    const float *tris;
+    uint32_t n_tris;
+    const rt_sphere *spheres;
+    uint32_t n_spheres;
+    rt_camera cam;
+    uint32_t W, H;
+    int32_t *spill;
+    uint32_t spill_cap;
+};
+int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
+/* One a-trous pass at tap distance `step` with the inverse variances of its colour, normal and
+   plane terms; col, feat and out are device buffers, out apart from col. */
+int rt_launch_atrous(const float *col, const float *feat, float *out, uint32_t W, uint32_t H, uint32_t step, float isc,
+                     float isn, float isp, void *stream);
+/* -- rt_temporal.hip -- */
+/* Temporal reprojection of the displayed frame: device buffers;
+   the outputs of the reprojection apart from its inputs, those of the merge possibly its history. */
+int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &prev_cam,
+                        const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H, float plane_tol,
+                        float normal_min, float max_history, void *stream);
+int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
+/* -- rt_variance.hip -- */
+/* The variance-guided display filter: device buffers.  The
+   moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in.  One filter
+   pass at tap distance `step`: out / out_var apart from col / var, out_var possibly NULL; lum_on == 0
+   switches the luminance term off. */
+int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
+                      uint32_t W, uint32_t H, void *stream);
+int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
+                       uint32_t W, uint32_t H, float isn, float isp, float min_len, void *stream);
+int rt_launch_atrous_var(const float *col, const float *var, const float *feat, float *out, float *out_var, uint32_t W,
+                         uint32_t H, uint32_t step, float sigma_lum, int lum_on, float isn, float isp, void *stream);
 
 #endif /* RT_INTERNAL_H */

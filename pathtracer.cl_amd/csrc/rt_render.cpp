@@ -1,8 +1,9 @@
 /*
  * rt_render.cpp — the renders of a context (librtmi.so host runtime): the schedule of the
  * triangle kernel's launch (grid, tile order, sample split, speculation, pilot, candidate lists),
- * the launches of the kernels in rt_kernels.hip, the stripe partition, the counters, the render
- * info and the kernel times, the seed-row halo, rt_read and rt_trace_rays.
+ * the launches of the render kernels (rt_tris.hip, rt_split.hip, rt_lists.hip, rt_sched.hip,
+ * rt_spheres.hip), the stripe partition, the counters, the render info and the kernel times, the
+ * seed-row halo, rt_read and rt_trace_rays.
  */
 #include <chrono>
 #include <cmath>

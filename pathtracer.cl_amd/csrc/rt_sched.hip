@@ -4,9 +4,9 @@
  * The reference launches one work-item per pixel and lets the runtime order them
  * (raytracer.cl:184-243); a pixel's sampleRate^2 samples are one serial chain, so the
  * persistent k_tris takes 8 x 8 pixel tiles from a queue, and the order of that queue
- * sets how long the launch's tail is.  From the cost probe (k_probe_cost: per pixel the
- * mesh hits of a grid of probe rays and the traversal steps of their queries) this file
- * computes, without a host round trip:
+ * sets how long the launch's tail is.  The cost probe is here too (k_probe_cost: per pixel the
+ * mesh hits of a grid of probe rays and the traversal steps of their queries, with k_tris's own
+ * per-lane traversal, rt_traverse.h), and from it this file computes, without a host round trip:
  *   1. the frame's mean steps per probed query (k_probe_sums),
  *   2. each tile's estimated cost (k_tile_cost: a blend of its costliest pixel — the
  *      tile's last lane finishes with it — and its mean; a probe ray that misses the mesh
@@ -15,7 +15,8 @@
  *   4. the pixel classes (k_classify): mesh pixel -1; box pixel (some probe ray missed,
  *      or — for a sample-split render — a mesh pixel whose probe took over 96 steps per ray)
  *      with a slot >= 0 in pixel order up to the slot budget (an exclusive scan of the box
- *      flags), -2 beyond it; a sample-split render runs the slotted long chains apart.
+ *      flags), -2 beyond it; a sample-split render runs the slotted long chains apart;
+ *   5. for a multi-GPU frame's stripe partition, the probe summed per stripe (k_stripe_costs).
  * Scheduling only: no pixel's result depends on when or where it is rendered.  This
  * replaced an 8 MB device-to-host copy, a host loop and a host sort per camera change
  * (every arrow key or drag of GlutCLWindow.cpp:229-279 restarts the refinement).
@@ -26,9 +27,73 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "rt_device.h"
 #include "rt_internal.h"
+#include "rt_quant.h"
+#include "rt_traverse.h"
+#include "rt_kernel_util.h"
+
+#pragma clang fp contract(off)
 
 namespace {
+
+/* Cost probe for the LPT pixel queue (rt_render.cpp tile_order): per pixel, an n x n grid
+   (probe_n, default 2) of camera rays (the pixel's samples are stratified over its area, so silhouette pixels mix
+   mesh and box paths) — each ray's closest-hit query and, when it hits the mesh, one shadow
+   query per light from the hit point toward the light's centre — with the per-lane
+   compressed traversal of the real kernel, counting its steps.
+   out[p] = (mesh hits, 0..n^2) << RT_PROBE_HIT_SHIFT | steps of all those queries.  A persistent grid (the
+   main kernel's) with grid-stride pixels, so the main kernel's traversal spill area serves
+   it.  Scheduling only: no result depends on it. */
+__global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_probe_cost(RtTriLaunch a, uint32_t *__restrict__ out)
+{
+    __shared__ int s_stack[RT_STACK_DEPTH * RT_BLOCK];
+    Stack stk;
+    stk.init(s_stack, a.spill, a.spill_cap);
+    const float4 *__restrict__ nodes = reinterpret_cast<const float4 *>(a.nodes);
+    const float4 *__restrict__ tris = reinterpret_cast<const float4 *>(a.tris);
+    const uint32_t npx = a.W * a.Hl;
+    const uint32_t stride = gridDim.x * RT_BLOCK;
+    const uint32_t rounds = (npx + stride - 1) / stride; /* uniform trip count: whole waves iterate together */
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t p = r * stride + blockIdx.x * RT_BLOCK + threadIdx.x;
+        const bool valid = p < npx;
+        const uint32_t x = valid ? p % a.W : 0u, yl = valid ? p / a.W : 0u;
+        const uint32_t y = global_row(a, yl);
+        const V3 o = v3(a.cam.position.x, a.cam.position.y, a.cam.position.z);
+        uint32_t steps = 0, hits = 0;
+        const uint32_t pn = a.probe_n;
+        const float step = 1.0f / (float)pn;
+        for (uint32_t k = 0; k < pn * pn; ++k) {
+            const float fx = (float)x + ((float)(k % pn) + 0.5f) * step, fy = (float)y + ((float)(k / pn) + 0.5f) * step;
+            const V3 d = camera_dir(a.cam, fx - ((float)a.W) / 2.0f, fy - ((float)a.H) / 2.0f);
+            TravCounts tc = {0u, 0u, 0u};
+            float t = kInf;
+            const int hit = traverse<RT_TRAV_BVH4Q, true>(nodes, tris, a.n_tris, o, d, RT_SMALL_F, t, false, stk, tc);
+            steps += tc.nodes + tc.leaves;
+            if (hit < 0) continue;
+            ++hits;
+            const float4 e1 = tris[3 * hit + 1], e2 = tris[3 * hit + 2];
+            const V3 hn = cross3(v3(e2.x, e2.y, e2.z), v3(e1.x, e1.y, e1.z));
+            const V3 so = v3(o.x + d.x * t + hn.x * RT_SMALL_F, o.y + d.y * t + hn.y * RT_SMALL_F,
+                             o.z + d.z * t + hn.z * RT_SMALL_F);
+            for (uint32_t l = 0; l < a.n_lights; ++l) {
+                const rt_sphere &L = a.lights[l];
+                const V3 lc = v3(L.center.x, L.center.y, L.center.z);
+                V3 sd = v3(lc.x - so.x, lc.y - so.y, lc.z - so.z);
+                const float il = rt_rsqrtf(sd.x * sd.x + sd.y * sd.y + sd.z * sd.z);
+                sd = v3(sd.x * il, sd.y * il, sd.z * il);
+                float st = intersect_sphere(so, sd, RT_SMALL_F, lc, L.radius) - RT_SMALL_F;
+                if (st > RT_SMALL_F && sd.x * hn.x + sd.y * hn.y + sd.z * hn.z > 0.0f) {
+                    TravCounts ts = {0u, 0u, 0u};
+                    (void)traverse<RT_TRAV_BVH4Q, true>(nodes, tris, a.n_tris, so, sd, RT_SMALL_F, st, true, stk, ts);
+                    steps += ts.nodes + ts.leaves;
+                }
+            }
+        }
+        if (valid) out[p] = (hits << RT_PROBE_HIT_SHIFT) | (steps < RT_PROBE_STEP_MASK ? steps : RT_PROBE_STEP_MASK);
+    }
+}
 
 /* the probe-cost model's constants (measured on the dragon frame, DESIGN.md §5: a box-path
    query costs 1.4x the mean probed query; the tile key weighs its costliest pixel 0.75) */
@@ -170,6 +235,51 @@ __global__ __launch_bounds__(256) void k_classify(const uint32_t *__restrict__ b
 }
 
 } // namespace
+
+int rt_launch_probe_cost(const RtTriLaunch &a, int grid_blocks, uint32_t *out, void *stream)
+{
+    hipLaunchKernelGGL(k_probe_cost, dim3((unsigned)grid_blocks), dim3(RT_BLOCK), 0, (hipStream_t)stream, a, out);
+    return (int)hipGetLastError();
+}
+
+/* Per stripe of a whole-frame probe (rt_partition_stripes): one block per stripe, its pixels'
+   box flags and mesh-pixel steps summed over the block (integer sums: the same on every GPU). */
+__global__ __launch_bounds__(256) void k_stripe_costs(const uint32_t *__restrict__ probe, uint32_t W, uint32_t H,
+                                                      uint32_t stripe_rows, uint32_t pn2,
+                                                      unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long s_box[256], s_steps[256];
+    const uint32_t s = blockIdx.x;
+    const uint32_t y0 = s * stripe_rows, y1 = min(H, y0 + stripe_rows);
+    unsigned long long box = 0, steps = 0;
+    for (uint32_t p = y0 * W + threadIdx.x; p < y1 * W; p += 256u) {
+        const uint32_t w = probe[p];
+        if ((w >> RT_PROBE_HIT_SHIFT) < pn2) ++box;
+        else steps += w & RT_PROBE_STEP_MASK;
+    }
+    s_box[threadIdx.x] = box;
+    s_steps[threadIdx.x] = steps;
+    __syncthreads();
+    for (uint32_t k = 128; k > 0; k >>= 1) {
+        if (threadIdx.x < k) {
+            s_box[threadIdx.x] += s_box[threadIdx.x + k];
+            s_steps[threadIdx.x] += s_steps[threadIdx.x + k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[2 * s] = s_box[0];
+        out[2 * s + 1] = s_steps[0];
+    }
+}
+
+int rt_launch_stripe_costs(const uint32_t *probe, uint32_t W, uint32_t H, uint32_t stripe_rows, uint32_t pn2,
+                           unsigned long long *out, void *stream)
+{
+    const uint32_t ns = (H + stripe_rows - 1u) / stripe_rows;
+    hipLaunchKernelGGL(k_stripe_costs, dim3(ns), dim3(256), 0, (hipStream_t)stream, probe, W, H, stripe_rows, pn2, out);
+    return (int)hipGetLastError();
+}
 
 void rt_sched_free(RtSchedScratch &s)
 {

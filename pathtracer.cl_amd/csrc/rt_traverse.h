@@ -2,9 +2,10 @@
  * rt_traverse.h — the per-lane ray queries of the gfx950 kernels: the reference's
  * ray/triangle test, the LDS traversal stack with its global spill tail, and the
  * resumable traversal of the 4-wide trees (full-precision and compressed nodes) with
- * the linear loop beside them.  Shared by rt_kernels.hip (the render kernels, the
- * batch ray queries) and rt_denoise.hip (the first-hit feature kernel); everything
- * here has internal linkage.
+ * the linear loop beside them.  Shared by rt_tris.hip and rt_split.hip (the render
+ * kernels), rt_spheres.hip (the batch ray queries), rt_sched.hip (the cost probe),
+ * rt_lists.hip and rt_denoise.hip (the first-hit feature kernel); everything here has
+ * internal linkage.
  */
 #ifndef RT_TRAVERSE_H
 #define RT_TRAVERSE_H

@@ -136,7 +136,7 @@ static long query(V o, V d, float tmax, bool any, float &t_hit, int &hit, int st
             ++steps;
             ++g_node_steps;
             if ((g_det_cull == 4 || g_det_cull == 5) && !det_possible(&g_nbox[6 * it.c], d)) continue; /* own box */
-            if (g_det_cull == 7) { /* the kernel's formula on the encoded box (rt_kernels.hip trav_step_q) */
+            if (g_det_cull == 7) { /* the kernel's formula on the encoded box (rt_traverse.h trav_step_q) */
                 const uint32_t *q = g_q4 + 16ull * it.c;
                 auto sx = [](uint32_t w, int off) { return (int)((w >> off) & 0xff) - 128; };
                 const float nsc = std::ldexp(1.0f, (int)(q[10] >> 24) - 128);

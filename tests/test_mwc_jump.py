@@ -1,4 +1,4 @@
-"""The arithmetic behind the speculated mesh pixels' chunk seeds (rt_kernels.hip
+"""The arithmetic behind the speculated mesh pixels' chunk seeds (rt_kernel_util.h
 `mwc_jump`, rt_render.cpp `spec_setup`): each of frand's two MWC generators (rng.h:9-47,
 x <- A (x & 0xffff) + (x >> 16)) is x <- A x mod M, M = A 2^16 - 1, on the states below M, so k
 draws are one multiplication by A^k mod M; states at or above M reach that range within 2 steps
@@ -53,7 +53,7 @@ def test_states_below_m_stay_and_others_arrive_within_two_steps(a):
     assert a * 65536 % m == 1  # a^-1 = 2^16 mod M
     # states above M (the only ones that need canonicalising: the 2^20 just above M and just
     # below 2^32, and a random 2^22 between), and a random sample below M: the step keeps states
-    # below M, and the others are below M or at the fixed point within 2 steps (rt_kernels.hip's
+    # below M, and the others are below M or at the fixed point within 2 steps (mwc_jump's
     # loop bound; every 32-bit state was checked once)
     rng = np.random.default_rng(a)
     above = np.concatenate([np.arange(m + 1, m + 1 + 2**20, dtype=np.uint64),
