@@ -231,7 +231,7 @@ SIGNATURES = {
     "rt_last_list_counts": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
     "rt_mesh_tree": (_i32, [_vp, ctypes.POINTER(RtTreeLayout), _vp, _vp, _vp]),
     "rt_trace_rays": (_i32, [_vp, _vp, _u32, _i32, _vp, _vp]),
-    # first-hit feature buffers and the display denoiser (csrc/rt_denoise.hip)
+    # first-hit feature buffers and the display denoiser (csrc/rt_features.hip, csrc/rt_filter.hip)
     "rt_get_camera": (_i32, [_vp, _u32, _vp]),
     "rt_primary_rays": (_i32, [_vp, _u32, _u32, _vp]),
     "rt_render_features": (_i32, [_vp, _vp, _u32, _u32, _i32, _i32]),
@@ -249,7 +249,7 @@ SIGNATURES = {
     "rt_temporal_merge": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32]),
     "rt_temporal_merge_async": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_reproject_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
-    # variance-guided display filter (csrc/rt_variance.hip)
+    # variance-guided display filter (csrc/rt_filter.hip)
     "rt_denoise_var_defaults": (_i32, [ctypes.POINTER(RtDenoiseVarParams)]),
     "rt_moments_accumulate": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32]),
     "rt_moments_accumulate_async": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),

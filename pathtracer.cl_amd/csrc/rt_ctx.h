@@ -282,7 +282,7 @@ struct rt_ctx {
     /* persistent-grid size per (traversal kind, counting, kernel form): index (trav * 2 + count) * 3 + form */
     int grid_cache[6 * (RT_TRAV_BVH4Q + 1)] = {};
     /* first-hit features, the display denoiser, the temporal stage and the variance-guided filter
-       (rt_denoise.hip, rt_temporal.hip, rt_variance.hip): scratch and events of their own.
+       (rt_features.hip, rt_temporal.hip, rt_filter.hip): scratch and events of their own.
        aux_stream: the stream of the last such call not yet followed by a render (ev_aux: its end) —
        the next render, ray query or probe on another stream waits for it (the spill area, the
        framebuffer the filter reads) */

@@ -1,8 +1,9 @@
 /*
  * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
- * features and the edge-avoiding denoiser (rt_denoise.hip), temporal reprojection
- * and merge (rt_temporal.hip, §4.10), luminance moments, variance and the variance-guided filter
- * (rt_variance.hip, §4.11), with their kernel times.  Every call runs through one driver (AuxCall).
+ * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
+ * §4.10), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
+ * (rt_filter.hip, §4.9 and §4.11), with their kernel times.  Every call runs through one driver
+ * (AuxCall).
  */
 #include <cmath>
 
@@ -123,6 +124,43 @@ float *pass_dst(bool last, float *out, const float *src, DevBuf<float> tmp[2])
     return (last && out != src) ? out : tmp[src == tmp[0] ? 1 : 0].p;
 }
 
+/* The passes of rt_denoise (in_var null) and of rt_denoise_var, from the scratch buffers to the
+   call's end.  pl: the call's planes — colour (filtered in place in the staging area: the last pass
+   never reads its destination), the two feature planes, then with in_var the variance plane —
+   `floats` in all.  sigma: sigma_color, its tolerance halving every pass, or sigma_lum. */
+int atrous_passes(AuxCall &x, const Plane *pl, size_t floats, const float *in, const float *in_var, const float *feat,
+                  float *out, float *out_var, uint32_t W, uint32_t H, uint32_t n, float sigma, int lum_on, float isn,
+                  float isp)
+{
+    rt_ctx *c = x.c;
+    const size_t px = (size_t)W * H;
+    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) { /* (three passes and more alternate between two) */
+        if (const int r = ensure_dev(c, c->d_dn_tmp[k], 4 * px)) return r;
+        if (in_var)
+            if (const int r = ensure_dev(c, c->d_var_tmp[k], px)) return r;
+    }
+    if (const int r = x.begin(pl, in_var ? 3 : 2, floats)) return r;
+    float *dout = x.at(0, out), *dvout = !in_var || (x.host && !out_var) ? nullptr : x.at(2, out_var);
+    /* each pass reads the one before it (col, var) and sets its own outputs, step and colour parameter */
+    RtAtrousLaunch a = {x.at(0, in), in_var ? x.at(2, in_var) : nullptr, x.at(1, feat), nullptr, nullptr, W, H, 0, 0.0f,
+                        lum_on, isn, isp};
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool last = i + 1 == n;
+        a.out = pass_dst(last, dout, a.col, c->d_dn_tmp);
+        a.out_var = in_var ? pass_dst(last, dvout, a.var, c->d_var_tmp) : nullptr;
+        a.step = 1u << i;
+        const float sc = ldexpf(sigma, -(int)i);
+        a.colour = in_var ? sigma : 1.0f / (sc * sc);
+        const int e = rt_launch_atrous(a, x.st);
+        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
+        a.col = a.out;
+        a.var = a.out_var;
+    }
+    if (a.col != dout) HIPCHK(c, hipMemcpyAsync(dout, a.col, 4 * px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    if (dvout && a.var != dvout) HIPCHK(c, hipMemcpyAsync(dvout, a.var, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    return x.end();
+}
+
 } // namespace
 
 extern "C" {
@@ -199,26 +237,10 @@ try {
     AuxCall x = {c, RT_ST_DENOISE};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    const uint32_t n = prm->iterations;
-    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) /* (three passes and more alternate between two) */
-        if (const int r = ensure_dev(c, c->d_dn_tmp[k], 4 * px)) return r;
     /* staged: colour (filtered in place there: the last pass never reads its destination), then the
        two feature planes */
     const Plane pl[] = {{in, out, 0, 4 * px}, {feat, nullptr, 4 * px, 8 * px}};
-    if (const int r = x.begin(pl, 2, 12 * px)) return r;
-    const float *dfeat = x.at(1, feat);
-    float *dout = x.at(0, out);
-    const float *src = x.at(0, in);
-    for (uint32_t i = 0; i < n; ++i) {
-        const float sc = ldexpf(prm->sigma_color, -(int)i); /* the colour tolerance halves every pass */
-        const float isc = 1.0f / (sc * sc);
-        float *dst = pass_dst(i + 1 == n, dout, src, c->d_dn_tmp);
-        const int e = rt_launch_atrous(src, dfeat, dst, W, H, 1u << i, isc, isn, isp, x.st);
-        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
-        src = dst;
-    }
-    if (src != dout) HIPCHK(c, hipMemcpyAsync(dout, src, 4 * px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
-    return x.end();
+    return atrous_passes(x, pl, 12 * px, in, nullptr, feat, out, nullptr, W, H, prm->iterations, sig[0], 0, isn, isp);
 } RT_CATCH(err_of(c))
 
 int rt_denoise(rt_ctx *c, const float *in, const float *feat, float *out, uint32_t W, uint32_t H,
@@ -420,31 +442,10 @@ try {
     AuxCall x = {c, RT_ST_DENOISE_VAR};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    const uint32_t n = prm->iterations;
-    for (uint32_t k = 0; k < (n > 2 ? 2u : 1u); ++k) { /* (three passes and more alternate between two) */
-        if (const int r = ensure_dev(c, c->d_dn_tmp[k], 4 * px)) return r;
-        if (const int r = ensure_dev(c, c->d_var_tmp[k], px)) return r;
-    }
     /* staged: colour, the two feature planes, then the variance plane; filtered in place there
        (the last pass never reads its destination) */
     const Plane pl[] = {{in, out, 0, 4 * px}, {feat, nullptr, 4 * px, 8 * px}, {in_var, out_var, 12 * px, px}};
-    if (const int r = x.begin(pl, 3, 13 * px)) return r;
-    const float *dfeat = x.at(1, feat);
-    float *dout = x.at(0, out), *dvout = x.host && !out_var ? nullptr : x.at(2, out_var);
-    /* as rt_denoise, the colour and the variance side by side */
-    const float *src = x.at(0, in), *vsrc = x.at(2, in_var);
-    for (uint32_t i = 0; i < n; ++i) {
-        const bool last = i + 1 == n;
-        float *dst = pass_dst(last, dout, src, c->d_dn_tmp);
-        float *vdst = pass_dst(last, dvout, vsrc, c->d_var_tmp);
-        const int e = rt_launch_atrous_var(src, vsrc, dfeat, dst, vdst, W, H, 1u << i, sig[0], lum_on, isn, isp, x.st);
-        if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
-        src = dst;
-        vsrc = vdst;
-    }
-    if (src != dout) HIPCHK(c, hipMemcpyAsync(dout, src, 4 * px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
-    if (dvout && vsrc != dvout) HIPCHK(c, hipMemcpyAsync(dvout, vsrc, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
-    return x.end();
+    return atrous_passes(x, pl, 13 * px, in, in_var, feat, out, out_var, W, H, prm->iterations, sig[0], lum_on, isn, isp);
 } RT_CATCH(err_of(c))
 
 int rt_denoise_var(rt_ctx *c, const float *in, const float *in_var, const float *feat, float *out, float *out_var,

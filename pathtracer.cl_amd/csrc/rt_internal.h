@@ -177,7 +177,7 @@ int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, v
 size_t rt_refit_nbox_bytes(void);
 
 /* ---- the render kernels' launch structs and launchers (rt_tris.hip, rt_split.hip, rt_spheres.hip,
-   rt_lists.hip, rt_sched.hip, rt_denoise.hip, rt_temporal.hip, rt_variance.hip) ---- */
+   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_filter.hip) ---- */
 #ifndef RT_QHEADS
 #define RT_QHEADS 8 /* heads of the multi-head pixel queue (k_tris mq_take) */
 #endif
@@ -406,8 +406,8 @@ int rt_sched_box_scan(RtSchedScratch &s, const uint32_t *flags, uint32_t npx, ui
                       uint32_t row, void *stream);
 int rt_sched_classify(const RtSchedScratch &s, uint32_t npx, uint32_t slots, int32_t *cls, uint32_t *slot_pixel,
                       void *stream);
-/* -- rt_denoise.hip -- */
-/* First-hit feature buffers and the display filter.  feat: 2 planes of W x H
+/* -- rt_features.hip -- */
+/* First-hit feature buffers.  feat: 2 planes of W x H
    float4 on the device, (P, t) then (N, surface id bits).  spheres != NULL: the sphere kernels'
    scene (trav ignored); else the mesh through traversal kind `trav`, spill indexed by block
    (ceil(W H / RT_BLOCK) blocks of RT_BLOCK lanes, spill_cap entries each). */
@@ -424,10 +424,11 @@ struct RtFeatLaunch {
     uint32_t spill_cap;
 };
 int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
-/* One a-trous pass at tap distance `step` with the inverse variances of its colour, normal and
-   plane terms; col, feat and out are device buffers, out apart from col. */
-int rt_launch_atrous(const float *col, const float *feat, float *out, uint32_t W, uint32_t H, uint32_t step, float isc,
-                     float isn, float isp, void *stream);
+/* The pixel tile of a block of the display-side kernels that run one lane per pixel of a 2-D grid
+   (the a-trous passes, k_variance, k_reproject): a wave covers two rows of 32 (512-B row segments
+   per float4 stream). */
+#define RT_TILE_BX 32
+#define RT_TILE_BY 8
 /* -- rt_temporal.hip -- */
 /* Temporal reprojection of the displayed frame: device buffers;
    the outputs of the reprojection apart from its inputs, those of the merge possibly its history. */
@@ -436,16 +437,25 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
                         float normal_min, float max_history, void *stream);
 int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
                              float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
-/* -- rt_variance.hip -- */
-/* The variance-guided display filter: device buffers.  The
-   moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in.  One filter
-   pass at tap distance `step`: out / out_var apart from col / var, out_var possibly NULL; lum_on == 0
-   switches the luminance term off. */
+/* -- rt_filter.hip -- */
+/* The display filters: device buffers.  The
+   moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in. */
 int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
                       uint32_t W, uint32_t H, void *stream);
 int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
                        uint32_t W, uint32_t H, float isn, float isp, float min_len, void *stream);
-int rt_launch_atrous_var(const float *col, const float *var, const float *feat, float *out, float *out_var, uint32_t W,
-                         uint32_t H, uint32_t step, float sigma_lum, int lum_on, float isn, float isp, void *stream);
+/* One a-trous pass at tap distance `step` with the inverse variances of its normal and plane terms.
+   var == NULL: rt_denoise's filter, `colour` the inverse variance of its colour term.  Else
+   rt_denoise_var's: the variance plane filtered along, `colour` = sigma_lum, lum_on == 0 switches the
+   luminance term off, out_var possibly NULL.  out / out_var apart from col / var. */
+struct RtAtrousLaunch {
+    const float *col, *var, *feat;
+    float *out, *out_var;
+    uint32_t W, H, step;
+    float colour;
+    int lum_on;
+    float isn, isp;
+};
+int rt_launch_atrous(const RtAtrousLaunch &a, void *stream);
 
 #endif /* RT_INTERNAL_H */

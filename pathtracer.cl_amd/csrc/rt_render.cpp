@@ -595,7 +595,7 @@ int order_streams(rt_ctx *c, Frame &f)
     /* a render on another stream than the last one's: ordered after that render's counter hand-back
        (which reads and zeroes the counters and queue cursors this render uses) */
     if (const int r = wait_last_render(c, f.st)) return r;
-    if (c->aux_stream) { /* and after a feature / denoise call enqueued since (rt_denoise.hip) */
+    if (c->aux_stream) { /* and after a feature / denoise call enqueued since (rt_display.cpp) */
         if (const int r = wait_aux(c, f.st)) return r;
         c->aux_stream = nullptr;
     }

@@ -21,11 +21,6 @@
 
 namespace {
 
-/* One lane per pixel; a block covers 32 x 8 pixels as the a-trous kernels', a wave two rows of 32
-   (512-B row segments per float4 stream). */
-#define RT_TEMPORAL_BX 32
-#define RT_TEMPORAL_BY 8
-
 struct ReprojArgs {
     const float4 *prev_col;
     const float *prev_len;
@@ -41,13 +36,14 @@ struct ReprojArgs {
     float plane_tol, normal_min, max_history;
 };
 
-/* The taps are gathered straight from global memory: for the small camera moves this stage exists
-   for, neighbouring lanes project onto neighbouring pixels of the previous frame, so a wave's taps
-   share cache lines (vector L1 / L2). */
-__global__ __launch_bounds__(RT_TEMPORAL_BX *RT_TEMPORAL_BY) void k_reproject(ReprojArgs a)
+/* One lane per pixel of the block's RT_TILE_BX x RT_TILE_BY tile.  The taps are gathered straight
+   from global memory: for the small camera moves this stage exists for, neighbouring lanes project
+   onto neighbouring pixels of the previous frame, so a wave's taps share cache lines (vector L1 /
+   L2). */
+__global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_reproject(ReprojArgs a)
 {
-    const int x = (int)(blockIdx.x * RT_TEMPORAL_BX + threadIdx.x);
-    const int y = (int)(blockIdx.y * RT_TEMPORAL_BY + threadIdx.y);
+    const int x = (int)(blockIdx.x * RT_TILE_BX + threadIdx.x);
+    const int y = (int)(blockIdx.y * RT_TILE_BY + threadIdx.y);
     const int W = (int)a.W, H = (int)a.H;
     if (x >= W || y >= H) return;
     const size_t npx = (size_t)a.W * a.H, p = (size_t)y * a.W + x;
@@ -171,8 +167,8 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
     a.plane_tol = plane_tol;
     a.normal_min = normal_min;
     a.max_history = max_history;
-    const dim3 grid((W + RT_TEMPORAL_BX - 1) / RT_TEMPORAL_BX, (H + RT_TEMPORAL_BY - 1) / RT_TEMPORAL_BY);
-    const dim3 block(RT_TEMPORAL_BX, RT_TEMPORAL_BY);
+    const dim3 grid((W + RT_TILE_BX - 1) / RT_TILE_BX, (H + RT_TILE_BY - 1) / RT_TILE_BY);
+    const dim3 block(RT_TILE_BX, RT_TILE_BY);
     hipLaunchKernelGGL(k_reproject, grid, block, 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -4,7 +4,7 @@
  * resumable traversal of the 4-wide trees (full-precision and compressed nodes) with
  * the linear loop beside them.  Shared by rt_tris.hip and rt_split.hip (the render
  * kernels), rt_spheres.hip (the batch ray queries), rt_sched.hip (the cost probe),
- * rt_lists.hip and rt_denoise.hip (the first-hit feature kernel); everything here has
+ * rt_lists.hip and rt_features.hip (the first-hit feature kernel); everything here has
  * internal linkage.
  */
 #ifndef RT_TRAVERSE_H

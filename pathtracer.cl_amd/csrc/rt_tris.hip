@@ -15,7 +15,7 @@
  * ([depth][lane] stride 256: conflict-free), BVH nodes and triangles are
  * 16-B-aligned float4 records read with dwordx4 loads.  See DESIGN.md.
  * The per-lane ray queries themselves (triangle test, stack, traversal steps) are in
- * rt_traverse.h, shared with rt_denoise.hip; the queue takes, the counters and the camera ray
+ * rt_traverse.h, shared with rt_features.hip; the queue takes, the counters and the camera ray
  * in rt_kernel_util.h, shared with the sample-split seed passes (rt_split.hip).
  */
 #include <hip/hip_runtime.h>
