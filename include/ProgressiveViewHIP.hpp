@@ -52,6 +52,13 @@
  *                    rt_denoise_var's output.  Features are rendered as with setDenoise; rawPixels()
  *                    is unchanged; a reshape drops the moments.  Switched on in mid-accumulation,
  *                    the moments start from the accumulated frame.  Off (the default), nothing changes.
+ *   setMotionCarry(on, max_history)  (no counterpart in the reference) with setTemporal, carry the
+ *                    displayed frame (and setVarianceGuided's moments) across updateMesh as well
+ *                    (DESIGN.md §4.13): the view keeps the pose the last frame was displayed in, and the
+ *                    first display after the update reprojects the history through the new features
+ *                    warped into that pose (rt_warp_features), its length capped at max_history.  The
+ *                    denoisers read the unwarped features.  Off (the default), updateMesh drops the
+ *                    history as before.
  */
 #ifndef PROGRESSIVE_VIEW_HIP_HPP
 #define PROGRESSIVE_VIEW_HIP_HPP
@@ -135,18 +142,46 @@ public:
 
     /* The mesh moves (RayTracerHIP::updateMesh): the features are rendered again, and what the
        display stages keep of earlier frames — the temporal history and the luminance moments —
-       is dropped, not carried: it shows the old geometry (there are no motion vectors).
-       Progression back to 0; returns restart()'s answer. */
+       is dropped, not carried: it shows the old geometry.  With setMotionCarry (and setTemporal, and
+       a kept frame) it is carried instead: the pose the kept frame was displayed in is snapshotted
+       before the tracer is updated — only if no snapshot is pending, so several updates between two
+       displays keep the oldest — and the next display warps its features into that pose
+       (mergeTemporal).  Progression back to 0; returns restart()'s answer. */
     bool updateMesh(const float *verts_xyz, uint32_t n_verts, int flags = 0)
     {
+        const bool carryMotion = motionCarry_ && temporal_ && haveHist_ && !realloc_;
+        if (carryMotion && !(posePending_ && poseVerts_ == n_verts)) {
+            if (poseVerts_ != n_verts) {
+                if (posePrev_) (void)hipFree(posePrev_);
+                posePrev_ = nullptr;
+                poseVerts_ = n_verts;
+            }
+            alloc(posePrev_, (size_t)n_verts * 3 * sizeof(float), "pose snapshot");
+            rt_.meshPose(posePrev_, n_verts, true);
+            posePending_ = true;
+        }
         rt_.updateMesh(verts_xyz, n_verts, flags);
         featDirty_ = true;
-        haveHist_ = false;
-        momValid_ = false;
+        if (!carryMotion) {
+            haveHist_ = false;
+            momValid_ = false;
+            posePending_ = false;
+        }
         const bool post = restart();
-        carry_ = false;
+        if (!carryMotion) carry_ = false;
         return post;
     }
+    /* (no counterpart in the reference) carry the displayed frame across updateMesh (DESIGN.md
+       §4.13).  max_history caps the history length of that carry alone (with setTemporal's own cap):
+       the carried radiance is the old pose's, and the cap bounds how long its shading lags.  Needs
+       setTemporal; off (the default), updateMesh drops the history as before. */
+    void setMotionCarry(bool on, float max_history = 8.0f)
+    {
+        motionCarry_ = on;
+        motionMaxHistory_ = max_history;
+        if (!on) posePending_ = false;
+    }
+    bool motionCarry() const { return motionCarry_; }
 
     void setDenoise(bool on, const rt_denoise_params &params = RayTracerHIP::denoiseDefaults())
     {
@@ -160,6 +195,7 @@ public:
         if (on && !temporal_) {
             featDirty_ = true;
             haveHist_ = false;
+            posePending_ = false;
         }
         temporal_ = on;
         temporalParams_ = params;
@@ -171,6 +207,7 @@ public:
             featDirty_ = true;
             haveHist_ = false;
             momValid_ = false;
+            posePending_ = false;
         }
         varGuided_ = on;
         varParams_ = params;
@@ -212,6 +249,7 @@ private:
         featDirty_ = true;
         haveHist_ = false;
         momValid_ = false;
+        posePending_ = false;
     }
     void release()
     {
@@ -221,10 +259,11 @@ private:
         if (featPrev_) (void)hipFree(featPrev_);
         if (hist_) (void)hipFree(hist_);
         if (carried_) (void)hipFree(carried_);
-        for (float *b : {accPrev_, mom_, momHist_, momCarried_, var_, len_})
+        for (float *b : {accPrev_, mom_, momHist_, momCarried_, var_, len_, featWarp_, posePrev_})
             if (b) (void)hipFree(b);
         dev_ = den_ = feat_ = featPrev_ = hist_ = carried_ = nullptr;
-        accPrev_ = mom_ = momHist_ = momCarried_ = var_ = len_ = nullptr;
+        accPrev_ = mom_ = momHist_ = momCarried_ = var_ = len_ = featWarp_ = posePrev_ = nullptr;
+        poseVerts_ = 0;
     }
     void alloc(float *&buf, size_t bytes, const char *what)
     {
@@ -260,12 +299,21 @@ private:
                 hipDeviceSynchronize() != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: history reset failed");
         } else if (carry_) { /* a new accumulation begins: carry the kept frame into it */
-            rt_.reproject(hist_, hist_ + 4 * px, histFeat, histCam_, feat_, carried_, carried_ + 4 * px, width_, height_,
-                          temporalParams_, true);
+            const float *curFeat = feat_;
+            rt_reproject_params prm = temporalParams_;
+            if (posePending_) { /* the mesh has moved since: the taps are sought where the material was */
+                alloc(featWarp_, 2 * frame, "feature buffer");
+                rt_.warpFeatures(feat_, posePrev_, poseVerts_, featWarp_, width_, height_, true);
+                curFeat = featWarp_;
+                prm.max_history = std::fmin(temporalParams_.max_history, motionMaxHistory_);
+            }
+            rt_.reproject(hist_, hist_ + 4 * px, histFeat, histCam_, curFeat, carried_, carried_ + 4 * px, width_, height_, prm,
+                          true);
             if (varGuided_) /* the same lengths, features and cameras: the colour's taps and weights */
-                rt_.reproject(momHist_, hist_ + 4 * px, histFeat, histCam_, feat_, momCarried_, momCarried_ + 4 * px, width_,
-                              height_, temporalParams_, true);
+                rt_.reproject(momHist_, hist_ + 4 * px, histFeat, histCam_, curFeat, momCarried_, momCarried_ + 4 * px, width_,
+                              height_, prm, true);
         }
+        posePending_ = false;
         carry_ = false;
         rt_.temporalMerge(carried_, carried_ + 4 * px, dev_, (float)(progression_ > 1 ? progression_ : 1),
                           temporalParams_.max_history, hist_, hist_ + 4 * px, width_, height_, true);
@@ -369,6 +417,12 @@ private:
     float *hist_ = nullptr, *featPrev_ = nullptr, *carried_ = nullptr;
     rt_camera histCam_{};
     bool temporal_ = false, haveHist_ = false, carry_ = false;
+    /* setMotionCarry: the pose the kept frame was displayed in (a device copy taken at the first
+       updateMesh after a display), and the current features warped into it */
+    float *posePrev_ = nullptr, *featWarp_ = nullptr;
+    uint32_t poseVerts_ = 0;
+    bool motionCarry_ = false, posePending_ = false;
+    float motionMaxHistory_ = 8.0f;
     rt_reproject_params temporalParams_ = RayTracerHIP::reprojectDefaults();
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
     /* setVarianceGuided: the accumulation buffer before the frame, the view's moments, with

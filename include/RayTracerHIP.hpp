@@ -289,6 +289,27 @@ public:
         return ms;
     }
 
+    /* ---- carrying the displayed frame across updateMesh (pathtracer_rt.h) ---- */
+    /* The vertices of the current mesh as the trees hold them (the last successful setMesh / updateMesh). */
+    void meshPose(float *out_verts_xyz, uint32_t n_verts, bool on_device = false) const
+    {
+        check(rt_mesh_pose(ctx_, out_verts_xyz, n_verts, on_device ? RT_OUT_DEVICE : 0), "meshPose");
+    }
+    /* cur_feat rewritten into the earlier pose prev_verts_xyz of the same mesh: out_feat (may be cur_feat),
+       reproject's cur_feat across an updateMesh. */
+    void warpFeatures(const float *cur_feat, const float *prev_verts_xyz, uint32_t n_verts, float *out_feat, unsigned width,
+                      unsigned height, bool on_device = false)
+    {
+        check(rt_warp_features(ctx_, cur_feat, prev_verts_xyz, n_verts, out_feat, width, height, on_device ? RT_OUT_DEVICE : 0),
+              "warpFeatures");
+    }
+    float lastWarpMs() const
+    {
+        float ms = 0.0f;
+        check(rt_last_warp_ms(ctx_, &ms), "lastWarpMs");
+        return ms;
+    }
+
     /* ---- variance-guided display filter (pathtracer_rt.h) ---- */
     static rt_denoise_var_params denoiseVarDefaults()
     {

@@ -162,6 +162,10 @@ typedef struct rt_mesh_update_info {
 int rt_update_mesh(rt_ctx *ctx, const float *verts_xyz, uint32_t n_verts, int flags);
 int rt_last_mesh_update(const rt_ctx *ctx, rt_mesh_update_info *out);
 int rt_set_mesh_dynamic(rt_ctx *ctx, int on); /* for the next rt_set_mesh */
+/* The vertices of the current mesh as the trees hold them: those of the last successful
+   rt_set_mesh / rt_update_mesh.  3 * n_verts floats; flags: RT_OUT_DEVICE = out is a device pointer.
+   RT_ERR_NO_MESH without a mesh; RT_ERR_ARG for a null pointer or another vertex count. */
+int rt_mesh_pose(rt_ctx *ctx, float *out_verts_xyz, uint32_t n_verts, int flags);
 
 /* ---- camera: RayTracer::setCameraMatrix / setCameraSpherical / setFoVAngle
    (RayTracer.h:56-60, RayTracer.cpp:24-47); the Camera struct is derived per
@@ -411,6 +415,27 @@ int rt_temporal_merge_async(rt_ctx *ctx, const float *hist_rgba, const float *hi
 /* Device time of the last reprojection kernel and of the last merge kernel (HIP events of their
    own), ms; either pointer may be NULL.  RT_ERR_STATE when a kernel asked for has not run. */
 int rt_last_reproject_ms(const rt_ctx *ctx, float *reproject_ms, float *merge_ms);
+
+/* ---- carrying the displayed frame across rt_update_mesh: the current features
+   rewritten into an earlier pose of the mesh, for rt_reproject's cur_feat. ---- */
+/* cur_feat as rt_render_features wrote it for the CURRENT pose; prev_verts_xyz: an earlier pose of the
+   same mesh (n_verts as the mesh's).  out_feat: the same two planes with every mesh pixel's P and N
+   replaced by those of the same material point in the earlier pose — the hit point's barycentrics
+   (u, v) in its triangle (id) of the current pose (rt_mesh_pose), unclamped, then P' = (a' + e1' u) +
+   e2' v and N' = normalize(cross(e2', e1')) from the earlier vertices; t and id stay.  Pixels of the
+   box, a sphere or nothing (id < 0) are copied bit for bit.  A mesh pixel becomes "no surface" (P = N
+   = 0, t = INFINITY, id RT_FEAT_NONE: rt_reproject gives it no history) when its id is not below the
+   triangle count, an index of its triangle is outside [0, n_verts), either triangle is degenerate, or
+   P' / N' is not finite.  Display only: the rules of the feature / denoise / reproject calls (no
+   render state changed, flags takes RT_OUT_DEVICE only and then every buffer incl. prev_verts_xyz is
+   a device pointer, the same stream ordering).  out_feat == cur_feat is allowed (no other overlap).
+   RT_ERR_NO_MESH without a mesh; RT_ERR_ARG for null pointers, an empty frame or another n_verts. */
+int rt_warp_features(rt_ctx *ctx, const float *cur_feat, const float *prev_verts_xyz, uint32_t n_verts,
+                     float *out_feat, uint32_t width, uint32_t height, int flags);
+int rt_warp_features_async(rt_ctx *ctx, const float *cur_feat, const float *prev_verts_xyz, uint32_t n_verts,
+                           float *out_feat, uint32_t width, uint32_t height, int flags, void *hip_stream);
+/* Device time of the last warp kernel (HIP events of its own), ms; RT_ERR_STATE before a first run. */
+int rt_last_warp_ms(const rt_ctx *ctx, float *ms);
 
 /* ---- variance-guided display filter driven by temporal luminance moments.  The
    rules of the calls above hold: display only, no render state is changed, the accumulation buffer

@@ -199,6 +199,7 @@ SIGNATURES = {
     "rt_update_mesh": (_i32, [_vp, _vp, _u32, _i32]),
     "rt_last_mesh_update": (_i32, [_vp, ctypes.POINTER(RtMeshUpdateInfo)]),
     "rt_set_mesh_dynamic": (_i32, [_vp, _i32]),
+    "rt_mesh_pose": (_i32, [_vp, _vp, _u32, _i32]),
     "rt_set_view_matrix": (_i32, [_vp, _vp]),
     "rt_set_camera_spherical": (_i32, [_vp, _f32, _f32, _f32, _f32, _f32, _f32]),
     "rt_set_fov": (_i32, [_vp, _f32]),
@@ -249,6 +250,10 @@ SIGNATURES = {
     "rt_temporal_merge": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32]),
     "rt_temporal_merge_async": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_reproject_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    # the features of a moving mesh in an earlier pose (csrc/rt_motion.hip)
+    "rt_warp_features": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32]),
+    "rt_warp_features_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32, _vp]),
+    "rt_last_warp_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
     # variance-guided display filter (csrc/rt_filter.hip)
     "rt_denoise_var_defaults": (_i32, [ctypes.POINTER(RtDenoiseVarParams)]),
     "rt_moments_accumulate": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32]),

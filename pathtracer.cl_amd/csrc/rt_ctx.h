@@ -101,7 +101,7 @@ static_assert((kCounterBytes + kWorkWords * sizeof(uint32_t)) % sizeof(unsigned 
 #endif
 
 /* the display-side stages with a kernel time of their own (rt_display.cpp) */
-enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_COUNT };
+enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_COUNT };
 
 struct rt_ctx {
     int device = 0;
@@ -201,6 +201,8 @@ struct rt_ctx {
        next rt_set_mesh */
     std::vector<int32_t> h_idx;
     DevBuf<int32_t> d_idx;
+    DevBuf<float> d_pose; /* the vertices the trees hold: those of the last successful rt_set_mesh /
+                             rt_update_mesh, 3 per vertex (rt_mesh_pose, rt_warp_features) */
     uint32_t n_verts = 0;
     bool dynamic = false;       /* the next host build keeps every triangle */
     bool mesh_dynamic = false;  /* the current mesh was built so */

@@ -1,7 +1,7 @@
 /*
  * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
  * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
- * §4.10), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
+ * §4.10), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
  * (rt_filter.hip, §4.9 and §4.11), with their kernel times.  Every call runs through one driver
  * (AuxCall).
  */
@@ -350,6 +350,42 @@ try {
     if (reproject_ms)
         if (const int r = stage_ms(c, RT_ST_REPROJECT, reproject_ms)) return r;
     return merge_ms ? stage_ms(c, RT_ST_MERGE, merge_ms) : RT_OK;
+} RT_CATCH(err_of(c))
+
+/* ---- the features of a moving mesh in an earlier pose ---- */
+
+int rt_warp_features_async(rt_ctx *c, const float *cur_feat, const float *prev_verts, uint32_t n_verts, float *out_feat,
+                           uint32_t W, uint32_t H, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!c->n_tris || !c->d_idx || !c->d_pose) return fail(c, RT_ERR_NO_MESH, "no mesh set");
+    if (!cur_feat || !prev_verts || !out_feat) return fail(c, RT_ERR_ARG, "rt_warp_features: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (n_verts != c->n_verts) return fail(c, RT_ERR_ARG, "rt_warp_features: the vertex count differs from the mesh's");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_warp_features: flags other than RT_OUT_DEVICE");
+    AuxCall x = {c, RT_ST_WARP};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged: the two feature planes, warped in place there, then the earlier pose */
+    const Plane pl[] = {{cur_feat, out_feat, 0, 8 * px}, {prev_verts, nullptr, 8 * px, 3ull * n_verts}};
+    if (const int r = x.begin(pl, 2, 8 * px + 3ull * n_verts)) return r;
+    const int e = rt_launch_warp_features(x.at(0, cur_feat), c->d_idx, c->d_pose, x.at(1, prev_verts), c->n_tris, n_verts,
+                                          x.at(0, out_feat), W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "feature warp kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_warp_features(rt_ctx *c, const float *cur_feat, const float *prev_verts, uint32_t n_verts, float *out_feat,
+                     uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_warp_features_async(c, cur_feat, prev_verts, n_verts, out_feat, W, H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_warp_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->stage_time[RT_ST_WARP].have) return RT_ERR_STATE;
+    return stage_ms(c, RT_ST_WARP, ms);
 } RT_CATCH(err_of(c))
 
 /* ---- variance-guided display filter --------------------- */

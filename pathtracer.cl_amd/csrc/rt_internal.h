@@ -177,7 +177,7 @@ int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, v
 size_t rt_refit_nbox_bytes(void);
 
 /* ---- the render kernels' launch structs and launchers (rt_tris.hip, rt_split.hip, rt_spheres.hip,
-   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_filter.hip) ---- */
+   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_motion.hip, rt_filter.hip) ---- */
 #ifndef RT_QHEADS
 #define RT_QHEADS 8 /* heads of the multi-head pixel queue (k_tris mq_take) */
 #endif
@@ -437,6 +437,12 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
                         float normal_min, float max_history, void *stream);
 int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
                              float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
+/* -- rt_motion.hip -- */
+/* The features of a moving mesh in an earlier pose: device buffers; idx the mesh's
+   indices (3 n_tris), pose / prev_verts its current and the earlier vertices (3 n_verts floats each).
+   out_feat may be cur_feat. */
+int rt_launch_warp_features(const float *cur_feat, const int32_t *idx, const float *pose, const float *prev_verts,
+                            uint32_t n_tris, uint32_t n_verts, float *out_feat, uint32_t W, uint32_t H, void *stream);
 /* -- rt_filter.hip -- */
 /* The display filters: device buffers.  The
    moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in. */

@@ -293,6 +293,9 @@ static int set_mesh_keep(rt_ctx *c, const float *verts, uint32_t n_verts, const 
     c->d_idx.reset();
     HIPCHK(c, c->d_idx.reserve(3ull * n_tris));
     HIPCHK(c, hipMemcpy(c->d_idx, idx, 12ull * n_tris, hipMemcpyHostToDevice));
+    c->d_pose.reset(); /* the pose the trees now hold (rt_mesh_pose) */
+    HIPCHK(c, c->d_pose.reserve(3ull * n_verts));
+    HIPCHK(c, hipMemcpy(c->d_pose, verts, 12ull * n_verts, hipMemcpyHostToDevice));
     return dynamic ? refit_prepare(c) : RT_OK;
 }
 
@@ -425,11 +428,29 @@ try {
         c->mesh_hi[k] += pad;
     }
     c->mesh_bounds_ok = true;
+    /* the update stands: its vertices are the mesh's pose (after a display-side call that still reads the old one) */
+    if (const int w = wait_aux(c, st)) return w;
+    HIPCHK(c, hipMemcpyAsync(c->d_pose, r.d_verts, 12ull * n_verts, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     float ms = 0.0f;
     HIPCHK(c, hipEventElapsedTime(&ms, r.ev0, r.ev1));
     c->last_update = {RT_MESH_UPDATE_REFIT, RT_REFIT_OK, 0u, res[RT_REFIT_RES_UNHIT],
                       r.area0 > 0.0 ? (float)(now / r.area0) : 1.0f, ms};
     c->have_update = true;
+    return RT_OK;
+} RT_CATCH(err_of(c))
+
+int rt_mesh_pose(rt_ctx *c, float *out, uint32_t n_verts, int flags)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!c->n_tris || !c->d_pose) return fail(c, RT_ERR_NO_MESH, "no mesh set");
+    if (!out) return fail(c, RT_ERR_ARG, "rt_mesh_pose: null argument");
+    if (n_verts != c->n_verts) return fail(c, RT_ERR_ARG, "rt_mesh_pose: the vertex count differs from the mesh's");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_mesh_pose: flags other than RT_OUT_DEVICE");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(out, c->d_pose, 12ull * n_verts,
+                        (flags & RT_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    HIPCHK(c, hipStreamSynchronize(nullptr)); /* (a device-to-device copy may return before it is done) */
     return RT_OK;
 } RT_CATCH(err_of(c))
 

@@ -25,6 +25,12 @@
  *              (ProgressiveViewHIP::setVarianceGuided, luminance tolerance SIGMA_LUM standard deviations, default 4)
  *              in place of --denoise's, with or without --temporal: --frames-out holds what it shows,
  *              --raw-frames-out and --features-out as above)
+ *             [--poses FILE]   (with --events and --mesh / --ply: raw float32, K poses of 3 * n_verts floats
+ *              each, of the mesh's vertices; the event p:K calls ProgressiveViewHIP::updateMesh(pose K), its
+ *              JSON line names what the tracer did: "mesh_update": "refit" | "rebuilt")
+ *             [--motion-carry [MAXHIST]]   (with --temporal: the view carries its displayed frame across the
+ *              p events too (ProgressiveViewHIP::setMotionCarry, that carry's history capped at MAXHIST frames,
+ *              default 8))
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -108,7 +114,7 @@ int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
-                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--denoised f] [--denoised-pfm f] [--features-out f] "
+                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
@@ -140,8 +146,9 @@ bool share_comm_id(const std::string &path, int rank, uint8_t id[RT_COMM_ID_BYTE
 
 int main(int argc, char **argv)
 {
-    std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out;
-    bool denoise = false, temporal = false, var_guided = false;
+    std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out, poses_path;
+    bool denoise = false, temporal = false, var_guided = false, motion_carry = false;
+    float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
     rt_denoise_params den_params = RayTracerHIP::denoiseDefaults();
@@ -167,6 +174,11 @@ int main(int argc, char **argv)
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') temporal_params.max_history = (float)std::atof(argv[++i]);
             continue;
         }
+        if (a == "--motion-carry") { /* an optional history cap follows */
+            motion_carry = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') motion_max_history = (float)std::atof(argv[++i]);
+            continue;
+        }
         if (a == "--variance-guided") { /* an optional luminance tolerance follows */
             var_guided = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') var_params.sigma_lum = (float)std::atof(argv[++i]);
@@ -186,6 +198,7 @@ int main(int argc, char **argv)
         else if (a == "--mesh") n_tris = (unsigned)std::atoi(v);
         else if (a == "--ply") ply_path = v;
         else if (a == "--events") events = v;
+        else if (a == "--poses") poses_path = v;
         else if (a == "--max-progression") max_prog = (unsigned)std::atoi(v);
         else if (a == "--frames-out") frames_out = v;
         else if (a == "--raw") raw = v;
@@ -203,6 +216,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --temporal needs --events (it carries the display across camera moves)\n");
         return 2;
     }
+    if (motion_carry && !temporal) {
+        std::fprintf(stderr, "rt_render: --motion-carry needs --temporal (without it there is nothing to carry)\n");
+        return 2;
+    }
     if (var_guided && events.empty()) {
         std::fprintf(stderr, "rt_render: --variance-guided needs --events (it follows a view's progressive frames)\n");
         return 2;
@@ -216,8 +233,12 @@ int main(int argc, char **argv)
         if (ply) rt.setCameraSpherical(target, 40.0f, 105.0f, 5.0f); /* plymain.cpp:115-117 */
         else rt.setCameraSpherical(target, 14.0f, 118.0f, 5.0f);     /* main.cpp:127-128 */
         int kernel = RT_KERNEL_SPHERES;
+        uint32_t n_verts = 0; /* of the mesh (--poses) */
         if (!ply_path.empty()) { /* plymain.cpp:121, with the mesh actually handed to the tracer */
             rt.setMeshFromPly(ply_path.c_str());
+            rt_ply *hdr = nullptr;
+            uint32_t nt = 0;
+            if (rt_ply_open(ply_path.c_str(), &hdr, &n_verts, &nt) == RT_OK) rt_ply_close(hdr);
             rt.setTraversal(linear ? RT_TRAVERSAL_LINEAR : RT_TRAVERSAL_BVH);
             kernel = RT_KERNEL_TRIS;
         } else if (n_tris) {
@@ -225,6 +246,7 @@ int main(int argc, char **argv)
             std::vector<int> idx(3ull * n_tris);
             if (rt_make_mesh(n_tris, 0.0f, -2.2f, 0.0f, 2.5f, v.data(), idx.data()) != RT_OK) return 1;
             rt.setMesh(v.data(), (unsigned)(v.size() / 3), idx.data(), n_tris);
+            n_verts = (uint32_t)(v.size() / 3);
             rt.setTraversal(linear ? RT_TRAVERSAL_LINEAR : RT_TRAVERSAL_BVH);
             kernel = RT_KERNEL_TRIS;
         }
@@ -234,6 +256,19 @@ int main(int argc, char **argv)
             if (denoise) view.setDenoise(true, den_params);
             if (temporal) view.setTemporal(true, temporal_params);
             if (var_guided) view.setVarianceGuided(true, var_params);
+            if (motion_carry) view.setMotionCarry(true, motion_max_history);
+            std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
+            if (!poses_path.empty()) {
+                std::ifstream pf(poses_path, std::ios::binary | std::ios::ate);
+                const std::streamoff bytes = pf ? (std::streamoff)pf.tellg() : -1;
+                if (!n_verts || bytes <= 0 || bytes % (12 * (std::streamoff)n_verts)) {
+                    std::fprintf(stderr, "rt_render: --poses needs a mesh and a file of whole poses (3 * %u floats each)\n", n_verts);
+                    return 2;
+                }
+                poses.resize((size_t)bytes / 4);
+                pf.seekg(0);
+                if (!pf.read(reinterpret_cast<char *>(poses.data()), bytes)) return 1;
+            }
             FILE *fo = frames_out.empty() ? nullptr : std::fopen(frames_out.c_str(), "wb");
             if (!frames_out.empty() && !fo) return 1;
             FILE *fr = raw_frames_out.empty() ? nullptr : std::fopen(raw_frames_out.c_str(), "wb");
@@ -246,6 +281,7 @@ int main(int argc, char **argv)
                 pos = end + 1;
                 if (ev.empty()) continue;
                 bool post = false, traced = false;
+                const char *mesh_update = nullptr; /* a p event: what the tracer did */
                 if (ev == "d") {
                     post = view.display();
                     traced = view.rendered();
@@ -271,11 +307,22 @@ int main(int argc, char **argv)
                     if (std::sscanf(ev.c_str() + 1, ":%d:%d", &a1, &a2) != 2) return usage();
                     if (ev[0] == 'm') post = view.motion(a1, a2);
                     else view.reshape((unsigned)a1, (unsigned)a2);
+                } else if (ev[0] == 'p') {
+                    unsigned k = 0;
+                    if (std::sscanf(ev.c_str() + 1, ":%u", &k) != 1) return usage();
+                    if (!n_verts || (size_t)(k + 1ull) * 3 * n_verts > poses.size()) {
+                        std::fprintf(stderr, "rt_render: event %s: --poses holds no pose %u\n", ev.c_str(), k);
+                        return 2;
+                    }
+                    post = view.updateMesh(poses.data() + (size_t)k * 3 * n_verts, n_verts);
+                    mesh_update = rt.lastMeshUpdate().action == RT_MESH_UPDATE_REFIT ? "refit" : "rebuilt";
                 } else return usage();
                 std::printf("{\"event\": \"%s\", \"rendered\": %s, \"redisplay\": %s, \"progression\": %u, "
-                            "\"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, \"height\": %u}\n",
+                            "\"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, \"height\": %u",
                             ev.c_str(), traced ? "true" : "false", post ? "true" : "false", view.progression(),
                             view.azimuth(), view.elevation(), view.width(), view.height());
+                if (mesh_update) std::printf(", \"mesh_update\": \"%s\"", mesh_update);
+                std::printf("}\n");
             }
             if (fo) std::fclose(fo);
             if (fr) std::fclose(fr);

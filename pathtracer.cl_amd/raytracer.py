@@ -400,6 +400,48 @@ class RayTracer:
         self._check(self._lib.rt_last_reproject_ms(self._h, a, b), "rt_last_reproject_ms")
         return ms.value
 
+    # ---- carrying the displayed frame across updateMesh (pathtracer_rt.h) ----
+    def meshPose(self, out=None, device: bool = False):
+        """The vertices of the current mesh as the trees hold them (the last successful setMesh /
+        updateMesh), [n_verts, 3] float32: into `out` (a numpy array, or a torch CUDA tensor), else
+        into a new numpy array — or, device=True, a new torch tensor on the tracer's device."""
+        if not self._mesh:
+            raise _abi.RtError(_abi.RT_ERR_NO_MESH, "rt_mesh_pose: no mesh set")
+        n = self._mesh[0]
+        if out is None:
+            if device:
+                import torch
+
+                out = torch.empty((n, 3), dtype=torch.float32, device=f"cuda:{self.device}")
+            else:
+                out = np.empty((n, 3), np.float32)
+        flags = self._frame_buffer(out, 3 * n, "pose buffer")
+        self._check(self._lib.rt_mesh_pose(self._h, _abi.ptr(out), n, flags), "rt_mesh_pose")
+        return out
+
+    def warpFeatures(self, cur_feat, prev_verts, out_feat, width: int, height: int, stream=None, sync: bool = True) -> None:
+        """Rewrite the current pose's features `cur_feat` (renderFeatures) into the earlier pose
+        `prev_verts` of the same mesh ([n_verts, 3]): `out_feat` (may be `cur_feat`) holds, for every
+        mesh pixel, position and normal of the same material point in that pose — reproject's
+        `cur_feat` across an updateMesh.  All numpy arrays or all torch CUDA tensors."""
+        px = int(width) * int(height)
+        n = (self._mesh or (0, 0))[0]
+        if isinstance(prev_verts, np.ndarray):
+            prev_verts = np.ascontiguousarray(prev_verts, np.float32)
+        nv = (prev_verts.size if isinstance(prev_verts, np.ndarray) else prev_verts.numel()) // 3
+        flags = [self._frame_buffer(cur_feat, px * 8, "feature buffer"), self._frame_buffer(prev_verts, 3 * n, "earlier pose"),
+                 self._frame_buffer(out_feat, px * 8, "destination feature buffer")]
+        if len(set(flags)) != 1:
+            raise ValueError("warpFeatures: the buffers must all be host arrays or all device tensors")
+        args = (self._h, _abi.ptr(cur_feat), _abi.ptr(prev_verts), nv, _abi.ptr(out_feat), int(width), int(height), flags[0])
+        self._aux_call("rt_warp_features", args, stream, sync)
+
+    def lastWarpMs(self) -> float:
+        """Device time of the last warpFeatures kernel, ms."""
+        ms = ctypes.c_float()
+        self._check(self._lib.rt_last_warp_ms(self._h, ctypes.byref(ms)), "rt_last_warp_ms")
+        return ms.value
+
     # ---- variance-guided display filter (pathtracer_rt.h, DESIGN.md §4.11) ----
     def denoiseVarDefaults(self) -> dict:
         prm = _abi.RtDenoiseVarParams()
