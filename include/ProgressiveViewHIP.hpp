@@ -59,6 +59,17 @@
  *                    warped into that pose (rt_warp_features), its length capped at max_history.  The
  *                    denoisers read the unwarped features.  Off (the default), updateMesh drops the
  *                    history as before.
+ *   setHistoryTrust(on, params)  (no counterpart in the reference) with setTemporal, judge the carried
+ *                    history afresh at every display: rt_history_trust tests it against
+ *                    the accumulation buffer over each pixel's window and gives the length it still
+ *                    deserves, which both merges (colour and moments) take in place of the carried
+ *                    length.  The carried pair itself is not rewritten.  Off (the default), no call is
+ *                    made and no output bit changes.
+ *   sceneChanged()   (no counterpart in the reference) the caller has changed the spheres (addSphere /
+ *                    clearSpheres — the lights of RT_KERNEL_TRIS among them): the features are rendered
+ *                    again and the progression restarts.  The history and the moments are dropped, as
+ *                    updateMesh drops them without the motion carry — unless setHistoryTrust is on, which
+ *                    keeps them and lets the test shorten them where the shading has changed.
  */
 #ifndef PROGRESSIVE_VIEW_HIP_HPP
 #define PROGRESSIVE_VIEW_HIP_HPP
@@ -183,6 +194,30 @@ public:
     }
     bool motionCarry() const { return motionCarry_; }
 
+    /* (no counterpart in the reference) lag-adaptive trust of the carried history.
+       Needs setTemporal; off (the default), nothing changes. */
+    void setHistoryTrust(bool on, const rt_trust_params &params = RayTracerHIP::trustDefaults())
+    {
+        trust_ = on;
+        trustParams_ = params;
+    }
+    bool historyTrust() const { return trust_; }
+    /* The spheres have changed (the caller's addSphere / clearSpheres).  Without setHistoryTrust the
+       history and the moments show the old lighting and are dropped; with it they are kept and judged.
+       Progression back to 0; returns restart()'s answer. */
+    bool sceneChanged()
+    {
+        featDirty_ = true;
+        if (!trust_) {
+            haveHist_ = false;
+            momValid_ = false;
+            posePending_ = false;
+        }
+        const bool post = restart();
+        if (!trust_) carry_ = false;
+        return post;
+    }
+
     void setDenoise(bool on, const rt_denoise_params &params = RayTracerHIP::denoiseDefaults())
     {
         if (on && !denoise_) featDirty_ = true;
@@ -259,10 +294,10 @@ private:
         if (featPrev_) (void)hipFree(featPrev_);
         if (hist_) (void)hipFree(hist_);
         if (carried_) (void)hipFree(carried_);
-        for (float *b : {accPrev_, mom_, momHist_, momCarried_, var_, len_, featWarp_, posePrev_})
+        for (float *b : {accPrev_, mom_, momHist_, momCarried_, var_, len_, featWarp_, posePrev_, trustLen_})
             if (b) (void)hipFree(b);
         dev_ = den_ = feat_ = featPrev_ = hist_ = carried_ = nullptr;
-        accPrev_ = mom_ = momHist_ = momCarried_ = var_ = len_ = featWarp_ = posePrev_ = nullptr;
+        accPrev_ = mom_ = momHist_ = momCarried_ = var_ = len_ = featWarp_ = posePrev_ = trustLen_ = nullptr;
         poseVerts_ = 0;
     }
     void alloc(float *&buf, size_t bytes, const char *what)
@@ -293,6 +328,7 @@ private:
             featDirty_ = false;
             carry_ = true;
         }
+        const bool judged = trust_ && haveHist_; /* a history exists: it is judged at every display */
         if (!haveHist_) { /* after a (re)allocation: no history anywhere */
             if (hipMemset(carried_, 0, frame + px * sizeof(float)) != hipSuccess ||
                 (varGuided_ && hipMemset(momCarried_, 0, frame + px * sizeof(float)) != hipSuccess) ||
@@ -315,11 +351,19 @@ private:
         }
         posePending_ = false;
         carry_ = false;
-        rt_.temporalMerge(carried_, carried_ + 4 * px, dev_, (float)(progression_ > 1 ? progression_ : 1),
-                          temporalParams_.max_history, hist_, hist_ + 4 * px, width_, height_, true);
+        const float n = (float)(progression_ > 1 ? progression_ : 1);
+        /* the lengths the merges blend by: the carried ones, or with setHistoryTrust what this display's
+           accumulation buffer leaves of them (one plane for colour and moments: they keep one length) */
+        const float *colLen = carried_ + 4 * px, *momLen = varGuided_ ? momCarried_ + 4 * px : nullptr;
+        if (judged) {
+            alloc(trustLen_, px * sizeof(float), "trusted history length buffer");
+            rt_.historyTrust(carried_, carried_ + 4 * px, dev_, n, feat_, trustLen_, width_, height_, trustParams_, true);
+            colLen = momLen = trustLen_;
+        }
+        rt_.temporalMerge(carried_, colLen, dev_, n, temporalParams_.max_history, hist_, hist_ + 4 * px, width_, height_, true);
         if (varGuided_)
-            rt_.temporalMerge(momCarried_, momCarried_ + 4 * px, mom_, (float)(progression_ > 1 ? progression_ : 1),
-                              temporalParams_.max_history, momHist_, momHist_ + 4 * px, width_, height_, true);
+            rt_.temporalMerge(momCarried_, momLen, mom_, n, temporalParams_.max_history, momHist_, momHist_ + 4 * px, width_,
+                              height_, true);
         histCam_ = cam;
         haveHist_ = true;
     }
@@ -423,6 +467,10 @@ private:
     uint32_t poseVerts_ = 0;
     bool motionCarry_ = false, posePending_ = false;
     float motionMaxHistory_ = 8.0f;
+    /* setHistoryTrust: the plane of history lengths the carried history still deserves at this display */
+    float *trustLen_ = nullptr;
+    bool trust_ = false;
+    rt_trust_params trustParams_ = RayTracerHIP::trustDefaults();
     rt_reproject_params temporalParams_ = RayTracerHIP::reprojectDefaults();
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
     /* setVarianceGuided: the accumulation buffer before the frame, the view's moments, with

@@ -289,6 +289,30 @@ public:
         return ms;
     }
 
+    /* ---- lag-adaptive trust of the carried history (pathtracer_rt.h) ---- */
+    static rt_trust_params trustDefaults()
+    {
+        rt_trust_params p;
+        rt_trust_defaults(&p);
+        return p;
+    }
+    /* The history length each pixel of the carried history (hist_rgba, hist_len) still deserves against
+       the accumulation buffer cur_rgba of n_cur frames: out_len (may be hist_len), temporalMerge's hist_len. */
+    void historyTrust(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur, const float *feat,
+                      float *out_len, unsigned width, unsigned height, const rt_trust_params &params = trustDefaults(),
+                      bool on_device = false)
+    {
+        check(rt_history_trust(ctx_, hist_rgba, hist_len, cur_rgba, n_cur, feat, out_len, width, height, &params,
+                               on_device ? RT_OUT_DEVICE : 0),
+              "historyTrust");
+    }
+    float lastTrustMs() const
+    {
+        float ms = 0.0f;
+        check(rt_last_trust_ms(ctx_, &ms), "lastTrustMs");
+        return ms;
+    }
+
     /* ---- carrying the displayed frame across updateMesh (pathtracer_rt.h) ---- */
     /* The vertices of the current mesh as the trees hold them (the last successful setMesh / updateMesh). */
     void meshPose(float *out_verts_xyz, uint32_t n_verts, bool on_device = false) const

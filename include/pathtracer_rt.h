@@ -416,6 +416,37 @@ int rt_temporal_merge_async(rt_ctx *ctx, const float *hist_rgba, const float *hi
    own), ms; either pointer may be NULL.  RT_ERR_STATE when a kernel asked for has not run. */
 int rt_last_reproject_ms(const rt_ctx *ctx, float *reproject_ms, float *merge_ms);
 
+/* ---- lag-adaptive trust of the carried history: per pixel, is the radiance that
+   rt_reproject carried still true?  Display only, under the rules of the calls above. ---- */
+typedef struct rt_trust_params {
+    float tolerance;                 /* standard deviations the window means may differ by; +INFINITY: all is trusted */
+    float sigma_normal, sigma_plane; /* the window's feature weights, as rt_denoise_params */
+} rt_trust_params;
+int rt_trust_defaults(rt_trust_params *p); /* 1.5f, 0.3f, 0.1f */
+/* Every displayed frame of a view that carries history, before rt_temporal_merge: hist_rgba /
+   hist_len the carried history as rt_reproject wrote it for the current view, cur_rgba the
+   accumulation buffer of n_cur = max(progression, 1) frames, feat the current view's features
+   (unwarped).  out_len, one plane of W*H floats: the history length each pixel still deserves, to be
+   passed to rt_temporal_merge as hist_len.  Per pixel p with m = hist_len[p]: !(m > 0): 0; p met
+   nothing: m.  Otherwise over the 7x7 window at unit distance (dy outer, dx inner; a tap counts when
+   it is inside the frame, has hist_len > 0, met a surface, and that surface is of p's class as in
+   rt_reproject), with w = exp(-(|dN|^2/sn^2 + (dP.N)^2/sp^2)), Lc = lum(cur_q), Lh = lum(hist_q):
+   mc, mh the weighted means of Lc, Lh; vc, vh their weighted variances (max(., 0)); ne = sum(w^2) /
+   sum(w)^2.  ne > 0.5 (fewer than two effective taps): m.  v = max(vc, vh max(m, 1) / n_cur);
+   z2 = (mc - mh)^2 / (v ne (1 + n_cur / m) + 1e-12); out = m where !(z2 > tolerance^2), else
+   m tolerance^2 / z2.  (max(a, b) = a > b ? a : b.)  out_len == hist_len is allowed (no other
+   overlap); no other input is written.  tolerance +INFINITY returns hist_len bit for bit.
+   tolerance <= 0 or NaN, a sigma <= 0 or NaN, n_cur < 1 or NaN, null pointers, an empty frame:
+   RT_ERR_ARG. */
+int rt_history_trust(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                     const float *feat, float *out_len, uint32_t width, uint32_t height, const rt_trust_params *params,
+                     int flags);
+int rt_history_trust_async(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                           const float *feat, float *out_len, uint32_t width, uint32_t height,
+                           const rt_trust_params *params, int flags, void *hip_stream);
+/* Device time of the last trust kernel (HIP events of its own), ms; RT_ERR_STATE before a first run. */
+int rt_last_trust_ms(const rt_ctx *ctx, float *ms);
+
 /* ---- carrying the displayed frame across rt_update_mesh: the current features
    rewritten into an earlier pose of the mesh, for rt_reproject's cur_feat. ---- */
 /* cur_feat as rt_render_features wrote it for the CURRENT pose; prev_verts_xyz: an earlier pose of the

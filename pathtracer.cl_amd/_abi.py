@@ -181,6 +181,10 @@ class RtReprojectParams(ctypes.Structure):
     _fields_ = [("plane_tol", ctypes.c_float), ("normal_min", ctypes.c_float), ("max_history", ctypes.c_float)]
 
 
+class RtTrustParams(ctypes.Structure):
+    _fields_ = [("tolerance", ctypes.c_float), ("sigma_normal", ctypes.c_float), ("sigma_plane", ctypes.c_float)]
+
+
 class RtDenoiseVarParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("sigma_lum", ctypes.c_float), ("sigma_normal", ctypes.c_float),
                 ("sigma_plane", ctypes.c_float), ("min_len", ctypes.c_float)]
@@ -250,6 +254,12 @@ SIGNATURES = {
     "rt_temporal_merge": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32]),
     "rt_temporal_merge_async": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_reproject_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    # lag-adaptive trust of the carried history (csrc/rt_temporal.hip)
+    "rt_trust_defaults": (_i32, [ctypes.POINTER(RtTrustParams)]),
+    "rt_history_trust": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTrustParams), _i32]),
+    "rt_history_trust_async": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTrustParams), _i32,
+                                      _vp]),
+    "rt_last_trust_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
     # the features of a moving mesh in an earlier pose (csrc/rt_motion.hip)
     "rt_warp_features": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32]),
     "rt_warp_features_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32, _vp]),

@@ -1,7 +1,7 @@
 /*
  * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
  * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
- * §4.10), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
+ * §4.10), the trust of the carried history (rt_temporal.hip, §4.14), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
  * (rt_filter.hip, §4.9 and §4.11), with their kernel times.  Every call runs through one driver
  * (AuxCall).
  */
@@ -350,6 +350,77 @@ try {
     if (reproject_ms)
         if (const int r = stage_ms(c, RT_ST_REPROJECT, reproject_ms)) return r;
     return merge_ms ? stage_ms(c, RT_ST_MERGE, merge_ms) : RT_OK;
+} RT_CATCH(err_of(c))
+
+/* ---- lag-adaptive trust of the carried history ----------- */
+
+int rt_trust_defaults(rt_trust_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->tolerance = 1.5f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_history_trust_async(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                           const float *feat, float *out_len, uint32_t W, uint32_t H, const rt_trust_params *prm, int flags,
+                           void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!hist_rgba || !hist_len || !cur_rgba || !feat || !out_len || !prm)
+        return fail(c, RT_ERR_ARG, "rt_history_trust: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_history_trust: flags other than RT_OUT_DEVICE");
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_history_trust: n_cur below 1 or NaN");
+    if (!(prm->tolerance > 0.0f)) return fail(c, RT_ERR_ARG, "rt_history_trust: tolerance is not positive"); /* <= 0 or NaN */
+    if (!(prm->sigma_normal > 0.0f) || !(prm->sigma_plane > 0.0f))
+        return fail(c, RT_ERR_ARG, "rt_history_trust: a sigma is not positive"); /* <= 0 or NaN */
+    if (out_len == hist_rgba || out_len == cur_rgba || out_len == feat)
+        return fail(c, RT_ERR_ARG, "rt_history_trust: the output is an input other than hist_len");
+    const float isn = 1.0f / (prm->sigma_normal * prm->sigma_normal), isp = 1.0f / (prm->sigma_plane * prm->sigma_plane);
+    const bool all = prm->tolerance == rt_inff(); /* everything is trusted: hist_len's bits, no kernel */
+    AuxCall x = {c, RT_ST_TRUST};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* the kernel's output lies apart from hist_len, whose neighbours' flags other blocks still read:
+       in the staging area a plane of its own, for device buffers in place a scratch plane */
+    const bool in_place = !x.host && out_len == hist_len;
+    if (in_place && !all)
+        if (const int r = ensure_dev(c, c->d_var_tmp[0], px)) return r;
+    /* staged: the float4 streams first (px may be odd), then the two length planes */
+    const Plane pl[] = {{all ? nullptr : hist_rgba, nullptr, 0, 4 * px},
+                        {all ? nullptr : cur_rgba, nullptr, 4 * px, 4 * px},
+                        {all ? nullptr : feat, nullptr, 8 * px, 8 * px},
+                        {hist_len, nullptr, 16 * px, px},
+                        {nullptr, out_len, 17 * px, px}};
+    if (const int r = x.begin(pl, 5, 18 * px)) return r;
+    const float *dlen = x.at(3, hist_len);
+    float *dout = x.at(4, out_len);
+    if (all) {
+        if (dout != dlen) HIPCHK(c, hipMemcpyAsync(dout, dlen, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+        return x.end();
+    }
+    float *dst = in_place ? c->d_var_tmp[0].p : dout;
+    const int e = rt_launch_history_trust(x.at(0, hist_rgba), dlen, x.at(1, cur_rgba), n_cur, x.at(2, feat), dst, W, H,
+                                          prm->tolerance * prm->tolerance, isn, isp, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "history trust kernel launch");
+    if (in_place) HIPCHK(c, hipMemcpyAsync(dout, dst, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_history_trust(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                     const float *feat, float *out_len, uint32_t W, uint32_t H, const rt_trust_params *prm, int flags)
+try {
+    return finish_sync(c, rt_history_trust_async(c, hist_rgba, hist_len, cur_rgba, n_cur, feat, out_len, W, H, prm, flags,
+                                                 nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_trust_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->stage_time[RT_ST_TRUST].have) return RT_ERR_STATE;
+    return stage_ms(c, RT_ST_TRUST, ms);
 } RT_CATCH(err_of(c))
 
 /* ---- the features of a moving mesh in an earlier pose ---- */

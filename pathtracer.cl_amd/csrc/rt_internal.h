@@ -437,6 +437,12 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
                         float normal_min, float max_history, void *stream);
 int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
                              float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
+/* The history length each pixel of a carried history still deserves: device
+   buffers, out_len apart from every input; k2 the squared tolerance, isn / isp the inverse variances
+   of the window's normal and plane terms. */
+int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                            const float *feat, float *out_len, uint32_t W, uint32_t H, float k2, float isn, float isp,
+                            void *stream);
 /* -- rt_motion.hip -- */
 /* The features of a moving mesh in an earlier pose: device buffers; idx the mesh's
    indices (3 n_tris), pose / prev_verts its current and the earlier vertices (3 n_verts floats each).

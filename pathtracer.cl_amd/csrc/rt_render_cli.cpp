@@ -31,6 +31,10 @@
  *             [--motion-carry [MAXHIST]]   (with --temporal: the view carries its displayed frame across the
  *              p events too (ProgressiveViewHIP::setMotionCarry, that carry's history capped at MAXHIST frames,
  *              default 8))
+ *             [--history-trust [TOL]]   (with --temporal: the view judges its carried history at every display
+ *              (ProgressiveViewHIP::setHistoryTrust, tolerance TOL standard deviations, default rt_trust_defaults';
+ *              "inf" trusts everything); the event e:DX:DY:DZ moves every emissive sphere by (DX, DY, DZ) and
+ *              calls ProgressiveViewHIP::sceneChanged())
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -69,7 +73,7 @@ rt_sphere init_sphere()
 }
 
 /* clrt/main.cpp:44-110 (ply = clrt/plymain.cpp:45-111) */
-void add_scene(RayTracerHIP &rt, bool ply)
+void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0.0f})
 {
     rt_sphere s = init_sphere();
     s.center = {-2.0f, -4.0f, -2.0f};
@@ -103,6 +107,7 @@ void add_scene(RayTracerHIP &rt, bool ply)
     rt.addSphere(s);
     s = init_sphere();
     s.center = ply ? rt_vec3{0.0f, 4.0f, 2.0f} : rt_vec3{2.2f, 1.0f, 2.0f};
+    s.center = {s.center.x + light_offset.x, s.center.y + light_offset.y, s.center.z + light_offset.z}; /* (the e event) */
     s.radius = 0.5f;
     s.mat.emission_power = 1.0f;
     const float e = ply ? 1.1f : 1.8f;
@@ -114,7 +119,7 @@ int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
-                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--denoised f] [--denoised-pfm f] [--features-out f] "
+                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
@@ -147,7 +152,8 @@ bool share_comm_id(const std::string &path, int rank, uint8_t id[RT_COMM_ID_BYTE
 int main(int argc, char **argv)
 {
     std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out, poses_path;
-    bool denoise = false, temporal = false, var_guided = false, motion_carry = false;
+    bool denoise = false, temporal = false, var_guided = false, motion_carry = false, trust = false;
+    rt_trust_params trust_params = RayTracerHIP::trustDefaults();
     float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
@@ -177,6 +183,12 @@ int main(int argc, char **argv)
         if (a == "--motion-carry") { /* an optional history cap follows */
             motion_carry = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') motion_max_history = (float)std::atof(argv[++i]);
+            continue;
+        }
+        if (a == "--history-trust") { /* an optional tolerance follows ("inf": everything is trusted) */
+            trust = true;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || !std::strcmp(argv[i + 1], "inf")))
+                trust_params.tolerance = (float)std::atof(argv[++i]);
             continue;
         }
         if (a == "--variance-guided") { /* an optional luminance tolerance follows */
@@ -220,6 +232,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --motion-carry needs --temporal (without it there is nothing to carry)\n");
         return 2;
     }
+    if (trust && !temporal) {
+        std::fprintf(stderr, "rt_render: --history-trust needs --temporal (without it there is no history to judge)\n");
+        return 2;
+    }
     if (var_guided && events.empty()) {
         std::fprintf(stderr, "rt_render: --variance-guided needs --events (it follows a view's progressive frames)\n");
         return 2;
@@ -257,6 +273,8 @@ int main(int argc, char **argv)
             if (temporal) view.setTemporal(true, temporal_params);
             if (var_guided) view.setVarianceGuided(true, var_params);
             if (motion_carry) view.setMotionCarry(true, motion_max_history);
+            if (trust) view.setHistoryTrust(true, trust_params);
+            rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
             std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
             if (!poses_path.empty()) {
                 std::ifstream pf(poses_path, std::ios::binary | std::ios::ate);
@@ -307,6 +325,13 @@ int main(int argc, char **argv)
                     if (std::sscanf(ev.c_str() + 1, ":%d:%d", &a1, &a2) != 2) return usage();
                     if (ev[0] == 'm') post = view.motion(a1, a2);
                     else view.reshape((unsigned)a1, (unsigned)a2);
+                } else if (ev[0] == 'e') {
+                    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+                    if (std::sscanf(ev.c_str() + 1, ":%f:%f:%f", &dx, &dy, &dz) != 3) return usage();
+                    light_offset = {light_offset.x + dx, light_offset.y + dy, light_offset.z + dz};
+                    rt.clearSpheres();
+                    add_scene(rt, ply, light_offset);
+                    post = view.sceneChanged();
                 } else if (ev[0] == 'p') {
                     unsigned k = 0;
                     if (std::sscanf(ev.c_str() + 1, ":%u", &k) != 1) return usage();

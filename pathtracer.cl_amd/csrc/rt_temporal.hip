@@ -6,16 +6,21 @@
  *                      on the same surface, and carry their colour and history length over
  *   k_temporal_merge   per pixel: blend the carried history with the accumulation buffer by their
  *                      frame counts
+ *   k_history_trust    per pixel: test the carried history against the accumulation buffer over a
+ *                      7 x 7 feature-weighted window staged in LDS, and shorten the history length
+ *                      where the two disagree by more than the window's noise explains
  *
  * Nothing in the reference corresponds to these kernels; their arithmetic is pinned in
- * DESIGN.md §4.10 under the model of include/rt_math.h (no contraction, IEEE division), so that a
- * float32 restatement reproduces every bit.  Neither touches a render's state, and neither writes
- * any of its inputs (the merge may write its history operands in place).
+ * DESIGN.md §4.10 and §4.14 under the model of include/rt_math.h (no contraction, IEEE division,
+ * the pinned exponential), so that a float32 restatement reproduces every bit.  None touches a
+ * render's state, and none writes any of its inputs (the merge may write its history operands in
+ * place).
  */
 #include <hip/hip_runtime.h>
 
 #include "pathtracer_rt.h"
 #include "rt_internal.h"
+#include "rt_math.h"
 
 #pragma clang fp contract(off)
 
@@ -134,6 +139,115 @@ __global__ __launch_bounds__(256) void k_temporal_merge(const float4 *hist, cons
     out_len[p] = l < max_history ? l : max_history;
 }
 
+struct TrustArgs {
+    const float4 *hist;
+    const float4 *cur;
+    const float *hist_len;
+    const float4 *feat;
+    float *out_len;
+    uint32_t W, H;
+    float n, k2, isn, isp;
+};
+
+constexpr int TRUST_R = 3; /* the 7 x 7 window */
+constexpr int TRUST_TW = RT_TILE_BX + 2 * TRUST_R, TRUST_TH = RT_TILE_BY + 2 * TRUST_R, TRUST_CELLS = TRUST_TW * TRUST_TH;
+
+__device__ __forceinline__ float trust_lum(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+
+/* One lane per pixel of the block's RT_TILE_BX x RT_TILE_BY tile.  The tile and
+   its halo of 3 pixels — 38 x 14 cells — are staged in LDS once: per cell the luminance of the
+   accumulation buffer and of the history (computed here, so the 49 taps of a pixel read two dwords
+   where the frame holds two float4), P and N with the surface id.  Planes of their own, as the
+   a-trous pass keeps them (rt_filter.hip): a lane row reads consecutive 16-B cells or consecutive
+   dwords.  40 B a cell, 21,280 B a block.  A cell that cannot count as a tap — outside the frame,
+   without history, or on no surface — is staged as the id RT_FEAT_NONE alone: none of its streams
+   is loaded or read.  (A centre pixel that has a history length and a surface is itself such a
+   cell that counts, so its own P, N and id come from the tile.)  The taps are summed in the
+   definition's order, dy outer, dx inner, whatever the staging.  out_len apart from every input:
+   a neighbouring block reads hist_len for its halo (the host keeps an in-place call apart). */
+__global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustArgs a)
+{
+    __shared__ float4 s_p[TRUST_CELLS], s_n[TRUST_CELLS];
+    __shared__ float s_lc[TRUST_CELLS], s_lh[TRUST_CELLS];
+    const int W = (int)a.W, H = (int)a.H;
+    const size_t npx = (size_t)a.W * a.H;
+    const int x0 = (int)(blockIdx.x * RT_TILE_BX) - TRUST_R, y0 = (int)(blockIdx.y * RT_TILE_BY) - TRUST_R;
+    const int tid = (int)(threadIdx.y * RT_TILE_BX + threadIdx.x);
+    for (int i = tid; i < TRUST_CELLS; i += RT_TILE_BX * RT_TILE_BY) {
+        const int gx = x0 + i % TRUST_TW, gy = y0 + i / TRUST_TW;
+        float4 nq = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(RT_FEAT_NONE));
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t q = (size_t)gy * a.W + gx;
+            if (a.hist_len[q] > 0.0f) {
+                nq = a.feat[npx + q];
+                if (__float_as_int(nq.w) != RT_FEAT_NONE) {
+                    s_p[i] = a.feat[q];
+                    s_lc[i] = trust_lum(a.cur[q]);
+                    s_lh[i] = trust_lum(a.hist[q]);
+                }
+            }
+        }
+        s_n[i] = nq;
+    }
+    __syncthreads();
+    const int x = (int)(blockIdx.x * RT_TILE_BX + threadIdx.x);
+    const int y = (int)(blockIdx.y * RT_TILE_BY + threadIdx.y);
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * a.W + x;
+    const float m = a.hist_len[p];
+    if (!(m > 0.0f)) { /* no history (false for a NaN too) */
+        a.out_len[p] = 0.0f;
+        return;
+    }
+    const int c0 = ((int)threadIdx.y + TRUST_R) * TRUST_TW + (int)threadIdx.x + TRUST_R;
+    const float4 np = s_n[c0];
+    const int idp = __float_as_int(np.w);
+    if (idp == RT_FEAT_NONE) { /* no surface to compare on */
+        a.out_len[p] = m;
+        return;
+    }
+    const float4 pp = s_p[c0];
+    float ws = 0.0f, w2 = 0.0f, ac = 0.0f, ac2 = 0.0f, ah = 0.0f, ah2 = 0.0f;
+    for (int dy = -TRUST_R; dy <= TRUST_R; ++dy) {
+#pragma unroll
+        for (int dx = -TRUST_R; dx <= TRUST_R; ++dx) {
+            const int q = c0 + dy * TRUST_TW + dx;
+            const float4 nq = s_n[q];
+            const int idq = __float_as_int(nq.w);
+            if (idq == RT_FEAT_NONE) continue;
+            if (!((idp >= 0 && idq >= 0) || idp == idq)) continue; /* the surface class, as k_reproject */
+            /* all of a tap's loads before its weight (rt_expf branches) */
+            const float4 pq = s_p[q];
+            const float Lc = s_lc[q], Lh = s_lh[q];
+            const float dnx = nq.x - np.x, dny = nq.y - np.y, dnz = nq.z - np.z;
+            const float en = dnx * dnx + dny * dny + dnz * dnz;
+            const float pl = (pq.x - pp.x) * np.x + (pq.y - pp.y) * np.y + (pq.z - pp.z) * np.z;
+            const float ep = pl * pl;
+            const float w = rt_expf(-(en * a.isn + ep * a.isp));
+            ws += w;
+            w2 += w * w;
+            ac += Lc * w;
+            ac2 += (Lc * Lc) * w;
+            ah += Lh * w;
+            ah2 += (Lh * Lh) * w;
+        }
+    }
+    const float mc = ac / ws, mh = ah / ws;
+    const float dc = ac2 / ws - mc * mc, dh = ah2 / ws - mh * mh;
+    const float vc = dc > 0.0f ? dc : 0.0f, vh = dh > 0.0f ? dh : 0.0f;
+    const float ne = w2 / (ws * ws);
+    float o = m;
+    if (!(ne > 0.5f)) { /* two effective taps at least: there is something to judge by */
+        const float vs = vh * ((m > 1.0f ? m : 1.0f) / a.n);
+        const float v = vc > vs ? vc : vs;
+        const float vd = (v * ne) * (1.0f + a.n / m) + 1e-12f;
+        const float d = mc - mh;
+        const float z2 = (d * d) / vd;
+        if (z2 > a.k2) o = m * (a.k2 / z2);
+    }
+    a.out_len[p] = o;
+}
+
 } // namespace
 
 int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &cam,
@@ -180,5 +294,26 @@ int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, cons
     hipLaunchKernelGGL(k_temporal_merge, dim3((npx + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(hist_rgba), hist_len, reinterpret_cast<const float4 *>(cur_rgba),
                        n_cur, max_history, reinterpret_cast<float4 *>(out_rgba), out_len, npx);
+    return (int)hipGetLastError();
+}
+
+int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                            const float *feat, float *out_len, uint32_t W, uint32_t H, float k2, float isn, float isp,
+                            void *stream)
+{
+    TrustArgs a;
+    a.hist = reinterpret_cast<const float4 *>(hist_rgba);
+    a.cur = reinterpret_cast<const float4 *>(cur_rgba);
+    a.hist_len = hist_len;
+    a.feat = reinterpret_cast<const float4 *>(feat);
+    a.out_len = out_len;
+    a.W = W;
+    a.H = H;
+    a.n = n_cur;
+    a.k2 = k2;
+    a.isn = isn;
+    a.isp = isp;
+    const dim3 grid((W + RT_TILE_BX - 1) / RT_TILE_BX, (H + RT_TILE_BY - 1) / RT_TILE_BY);
+    hipLaunchKernelGGL(k_history_trust, grid, dim3(RT_TILE_BX, RT_TILE_BY), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -400,6 +400,40 @@ class RayTracer:
         self._check(self._lib.rt_last_reproject_ms(self._h, a, b), "rt_last_reproject_ms")
         return ms.value
 
+    # ---- lag-adaptive trust of the carried history (pathtracer_rt.h) ----
+    def trustDefaults(self) -> dict:
+        prm = _abi.RtTrustParams()
+        self._check(self._lib.rt_trust_defaults(ctypes.byref(prm)), "rt_trust_defaults")
+        return dict(tolerance=prm.tolerance, sigma_normal=prm.sigma_normal, sigma_plane=prm.sigma_plane)
+
+    def historyTrust(self, hist_rgba, hist_len, cur_rgba, n_cur: float, feat, out_len, width: int, height: int,
+                     tolerance: float | None = None, sigma_normal: float = 0.3, sigma_plane: float = 0.1, stream=None,
+                     sync: bool = True) -> None:
+        """The history length each pixel of the carried history (`hist_rgba`, `hist_len`, as reproject
+        wrote them for the current view) still deserves against the accumulation buffer `cur_rgba` of
+        `n_cur` = max(progression, 1) frames, judged over a 7x7 window guided by `feat`: `out_len` (W*H
+        floats; may be `hist_len`), to be passed to temporalMerge as its `hist_len`.  `tolerance` in
+        standard deviations (None: the library's default; inf: everything is trusted).  All numpy arrays
+        or all torch CUDA tensors; the inputs are only read."""
+        px = int(width) * int(height)
+        need = [(hist_rgba, 4, "history frame"), (hist_len, 1, "history lengths"), (cur_rgba, 4, "current frame"),
+                (feat, 8, "feature buffer"), (out_len, 1, "destination history lengths")]
+        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
+        if len(set(flags)) != 1:
+            raise ValueError("historyTrust: the buffers must all be host arrays or all device tensors")
+        if tolerance is None:
+            tolerance = self.trustDefaults()["tolerance"]
+        prm = _abi.RtTrustParams(float(tolerance), float(sigma_normal), float(sigma_plane))
+        args = (self._h, _abi.ptr(hist_rgba), _abi.ptr(hist_len), _abi.ptr(cur_rgba), float(n_cur), _abi.ptr(feat),
+                _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags[0])
+        self._aux_call("rt_history_trust", args, stream, sync)
+
+    def lastTrustMs(self) -> float:
+        """Device time of the last historyTrust kernel, ms."""
+        ms = ctypes.c_float()
+        self._check(self._lib.rt_last_trust_ms(self._h, ctypes.byref(ms)), "rt_last_trust_ms")
+        return ms.value
+
     # ---- carrying the displayed frame across updateMesh (pathtracer_rt.h, DESIGN.md §4.13) ----
     def meshPose(self, out=None, device: bool = False):
         """The vertices of the current mesh as the trees hold them (the last successful setMesh /
