@@ -12,7 +12,7 @@
  *
  * Rules that make the results identical on x86 and gfx950:
  *   - only IEEE-754 +, -, *, / and sqrt, each correctly rounded, in binary32
- *     or binary64; no FMA contraction (every TU is built with
+ *     or binary64 (pow, and the trig reduction where binary32 cancels); no FMA contraction (every TU is built with
  *     -ffp-contract=off; HIP division/sqrt are correctly rounded by default);
  *   - integer/bit manipulation for range reduction and scaling;
  *   - no calls into libm or the device math library.
@@ -20,8 +20,20 @@
  * sin/cos/exp/log follow Cephes' single-precision algorithms (S. Moshier,
  * public algorithms: Cody-Waite reduction + minimax polynomials); pow is
  * evaluated as exp(y*log(x)) in binary64 and rounded once to binary32.
- * Accuracy: sin/cos ≤ 2 ulp for |x| < 8192 (the kernels only ever pass
- * 2π·U[0,1)), exp/log ≤ 2 ulp, pow ≈ correctly rounded for x ≥ 0.
+ * Accuracy of sin/cos, as tests/test_math.py establishes it (host build against
+ * binary64):
+ *   - for |x| < 8192 the absolute error is at most 2^-23, i.e. 2 ulps of a result
+ *     in [0.5, 1) (test_sin_cos_absolute_error_below_8192; worst measured 7.8e-8).
+ *     It is not a bound in ulps of the result: near the zeros of sin/cos the error
+ *     reaches ~110 ulps of the (tiny) result;
+ *   - on the kernels' own arguments 2π·k/2^23, every k, the error is at most 2 ulps
+ *     of the result (test_sin_cos_ulp_error_on_the_kernels_range; worst measured
+ *     1.51).  This needs rt_trig_reduce's binary64 step next to multiples of π/2:
+ *     without it cos at k = 6291456 (the float next to 3π/2) was 13.8 ulps off.
+ * exp/log/pow over the kernels' arguments: tests/test_oracle_golden.py
+ * test_math_model_sanity (exp/log ≤ 3 ulp, pow ≤ 16 ulp; pow measured 0.50).
+ * The device build of every function here is pinned to the host build bit for
+ * bit by tests/test_gpu_device_kat.py.
  */
 #ifndef RT_MATH_H
 #define RT_MATH_H
@@ -115,6 +127,18 @@ RT_HD float rt_trig_reduce(float ax, int *jout)
     float r = ax - y * RT_DP1;
     r = r - y * RT_DP2;
     r = r - y * RT_DP3;
+    /* Next to a multiple of pi/2 the three binary32 terms cancel down to their own rounding
+       error (about y 2^-46): below 2^-22 the reduced argument, and with it the sine it becomes,
+       is off by more than an ulp (13.8 ulps at the float next to 3 pi / 2, which the kernels
+       reach at r2 = 0.75).  There the reduction is redone in binary64 with Cephes' double-
+       precision split of pi/4 (each part times y exact) and rounded once. */
+    if (rt_fabsf(r) < 2.384185791015625e-7f) {
+        const double yd = (double)y;
+        double rd = (double)ax - yd * 7.85398125648498535156e-1;
+        rd = rd - yd * 3.77489470793079817668e-8;
+        rd = rd - yd * 2.69515142907905952645e-15;
+        r = (float)rd;
+    }
     return r;
 }
 

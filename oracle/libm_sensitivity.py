@@ -45,26 +45,19 @@ def compare(a: np.ndarray, b: np.ndarray, tol: float = 1e-5) -> dict:
         rel = np.where(scale > 0, diff / scale, 0.0)
     within = diff <= tol * scale
     return {"components": int(a.size), "bit_identical": round(float(same.mean()), 6),
-            "within_1e-5_rel": round(float(within.mean()), 6), "beyond_1e-5_rel": int((~within).sum()),
+            "within_1e-5_rel": round(float(within.mean()), 6), "within_exact": float(within.mean()),
+            "beyond_1e-5_rel": int((~within).sum()),
             "max_rel": float(rel.max()) if rel.size else 0.0}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r03" / "libm_sensitivity.json"))
-    ap.add_argument("--dragon-pixels", type=int, default=16)
-    ap.add_argument("--threads", type=int, default=8)
-    args = ap.parse_args()
-    pt = ptload.load()
-    sc = pt.scenes
-    pinned = Reference(build_if_missing=False)
-    libm = Reference(build_if_missing=False, path=LIBREF_LIBM)
+def golden_configs(pt, pinned, libm, threads: int = 8) -> dict:
+    """The golden configurations (tests/golden/meta.json), every progressive frame, rendered with
+    both builds of the reference: per configuration the frame-by-frame comparison and whether the
+    seed planes end identical (errors accumulate through the mix and, for raytrace, through the
+    seeds: a 1-ulp difference can change a later branch).  The pinned render must equal the
+    fixture bit for bit.  Used by main() and by tests/test_libm_sensitivity.py."""
     meta = json.loads((ROOT / "tests" / "golden" / "meta.json").read_text())
-    res = {"pinned": str(LIBREF.relative_to(ROOT)), "libm": str(LIBREF_LIBM.relative_to(ROOT)),
-           "tolerance": "north star: per-pixel radiance within 1e-5 relative", "configs": {}}
-
-    # the golden configurations, every progressive frame (errors accumulate through the mix
-    # and, for raytrace, through the seeds: a 1-ulp difference can change a later branch)
+    configs = {}
     for name, m in meta["cases"].items():
         if "kernel" not in m:
             continue
@@ -81,14 +74,31 @@ def main():
             fr = []
             for p in range(m["frames"]):
                 ref.launch(m["kernel"], out, g["camera"], spheres, W, H, Wp, Hp, m["sample_rate"], m["max_depth"], p,
-                           sd, verts, idx, nthreads=args.threads)
+                           sd, verts, idx, nthreads=threads)
                 fr.append(out.copy())
             outs[who] = (fr, sd)
         assert all(np.array_equal(f.view(np.uint32), e.view(np.uint32)) for f, e in zip(outs["pinned"][0], g["frames"]))
-        res["configs"][name] = {
+        configs[name] = {
+            "kernel": int(m["kernel"]),
             "frames": [compare(a, b) for a, b in zip(outs["pinned"][0], outs["libm"][0])],
             "seeds_identical": bool(np.array_equal(outs["pinned"][1], outs["libm"][1])),
         }
+    return configs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "r03" / "libm_sensitivity.json"))
+    ap.add_argument("--dragon-pixels", type=int, default=16)
+    ap.add_argument("--threads", type=int, default=8)
+    args = ap.parse_args()
+    pt = ptload.load()
+    sc = pt.scenes
+    pinned = Reference(build_if_missing=False)
+    libm = Reference(build_if_missing=False, path=LIBREF_LIBM)
+    res = {"pinned": str(LIBREF.relative_to(ROOT)), "libm": str(LIBREF_LIBM.relative_to(ROOT)),
+           "tolerance": "north star: per-pixel radiance within 1e-5 relative",
+           "configs": golden_configs(pt, pinned, libm, args.threads)}
 
     # the headline configuration: dragon class, 1920x1080, sampleRate 16 (256 spp), a strided
     # subset of whole pixels (the reference's linear loop over 871,414 triangles)

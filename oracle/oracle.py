@@ -125,12 +125,19 @@ class Oracle:
         self.lib.or_any_hits_bvh(_p(rays), n, _p(bvh.verts), _p(bvh.idx), ctypes.c_void_p(bvh.handle), _p(oi))
         return oi
 
-    MATH_FN = {"sin": 0, "cos": 1, "exp": 2, "log": 3, "pow": 4, "sincos_s": 5, "sincos_c": 6}
+    MATH_FN = {"sin": 0, "cos": 1, "exp": 2, "log": 3, "pow": 4, "sincos_s": 5, "sincos_c": 6, "pow_xy": 7,
+               "sqrt": 8, "rsqrt": 9, "ldexp": 10, "div": 11, "min": 12, "max": 13}
+    MATH_BINARY = ("pow_xy", "ldexp", "div", "min", "max")  # y is an array as long as x (ldexp: int32)
 
-    def math(self, fn: str, x: np.ndarray, y: float = 0.0) -> np.ndarray:
-        """The pinned builtin `fn` (include/rt_math.h) over every element of x (pow: x ** y)."""
+    def math(self, fn: str, x: np.ndarray, y=0.0) -> np.ndarray:
+        """The pinned builtin `fn` (include/rt_math.h) over every element of x (pow: x ** y for one
+        y; the MATH_BINARY codes: element-wise in x[i], y[i])."""
         x = np.ascontiguousarray(x, np.float32)
-        yy = np.array([y], np.float32)
+        if fn in self.MATH_BINARY:
+            yy = np.ascontiguousarray(y, np.int32 if fn == "ldexp" else np.float32)
+            assert yy.shape == x.shape
+        else:
+            yy = np.array([y], np.float32)
         out = np.empty_like(x)
         self.lib.or_math_vec(self.MATH_FN[fn], _p(x), _p(yy), _p(out), x.size)
         return out

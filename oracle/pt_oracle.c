@@ -1332,8 +1332,10 @@ OR_API float or_math_log(float x) { return rt_logf(x); }
 OR_API float or_math_pow(float x, float y) { return rt_powf(x, y); }
 
 /* Vectorised: the pinned builtins over whole argument ranges (tests/test_oracle_golden.py
-   test_math_model_sanity).  fn: 0 sin, 1 cos, 2 exp, 3 log, 4 pow(x, y[0]), 5 / 6 the sine /
-   cosine half of rt_sincosf (the triangle kernel's shared light / bounce direction). */
+   test_math_model_sanity, tests/test_gpu_device_kat.py).  fn: 0 sin, 1 cos, 2 exp, 3 log,
+   4 pow(x, y[0]), 5 / 6 the sine / cosine half of rt_sincosf (the triangle kernel's shared light /
+   bounce direction); element-wise in x[i], y[i]: 7 pow, 8 sqrt, 9 rsqrt, 10 ldexp (y holds int32
+   bits), 11 x / y, 12 min, 13 max.  y may be null for the unary codes. */
 OR_API void or_math_vec(int fn, const float *x, const float *y, float *out, size_t n)
 {
     for (size_t i = 0; i < n; ++i) {
@@ -1345,7 +1347,14 @@ OR_API void or_math_vec(int fn, const float *x, const float *y, float *out, size
         case 3: out[i] = rt_logf(x[i]); break;
         case 4: out[i] = rt_powf(x[i], y[0]); break;
         case 5: rt_sincosf(x[i], &s, &c); out[i] = s; break;
-        default: rt_sincosf(x[i], &s, &c); out[i] = c; break;
+        case 6: rt_sincosf(x[i], &s, &c); out[i] = c; break;
+        case 7: out[i] = rt_powf(x[i], y[i]); break;
+        case 8: out[i] = rt_sqrtf(x[i]); break;
+        case 9: out[i] = rt_rsqrtf(x[i]); break;
+        case 10: out[i] = rt_ldexpf(x[i], (int)rt_f2u(y[i])); break;
+        case 11: out[i] = x[i] / y[i]; break;
+        case 12: out[i] = rt_minf(x[i], y[i]); break;
+        default: out[i] = rt_maxf(x[i], y[i]); break;
         }
     }
 }
@@ -1359,4 +1368,125 @@ OR_API float or_kat_intersect_sphere(const rt_ray *r, const rt_vec3 *c, float ra
 OR_API void or_kat_emissive(rt_ray *r, const rt_vec3 *c, float radius, float r1, float r2)
 {
     or_sphere_emissive_radiance(r, *c, radius, r1, r2);
+}
+
+/* ---- batch forms of the per-function answers (tests/devkat.py: one call for a whole case list) ---- */
+
+/* k draws of frand from each seed pair: vals[n][k] and the seeds after them. */
+OR_API void or_frand_seq(const uint32_t *seeds, uint32_t k, float *vals, uint32_t *seeds_out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        rt_seed s = {seeds[2 * i], seeds[2 * i + 1]};
+        for (uint32_t j = 0; j < k; ++j) vals[i * k + j] = or_frand(&s);
+        seeds_out[2 * i] = s.x;
+        seeds_out[2 * i + 1] = s.y;
+    }
+}
+
+/* k draws of strat_rand(seed, j % total, total), j = 0..k-1. */
+OR_API void or_strat_seq(const uint32_t *seeds, uint32_t k, int total, float *vals, uint32_t *seeds_out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        rt_seed s = {seeds[2 * i], seeds[2 * i + 1]};
+        for (uint32_t j = 0; j < k; ++j) vals[i * k + j] = or_strat_rand(&s, (int)(j % (uint32_t)total), total);
+        seeds_out[2 * i] = s.x;
+        seeds_out[2 * i + 1] = s.y;
+    }
+}
+
+/* intersects_triangle (hit, uvt = u, v and the ray's tmax afterwards) and intersects_triangle_p. */
+OR_API void or_triangle_batch(const rt_ray *rays, const rt_triangle *tris, int32_t *hit, float *uvt, int32_t *hit_p,
+                              size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        rt_ray r = rays[i];
+        float u = 0.0f, v = 0.0f;
+        hit_p[i] = or_intersects_triangle_p(&r, &tris[i]);
+        hit[i] = or_intersects_triangle(&r, &u, &v, &tris[i]);
+        uvt[3 * i] = u;
+        uvt[3 * i + 1] = v;
+        uvt[3 * i + 2] = r.tmax;
+    }
+}
+
+OR_API void or_sphere_batch(const rt_ray *rays, const rt_vec3 *c, const float *radius, float *out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = or_intersect_sphere(&rays[i], c[i], radius[i]);
+}
+
+/* intersectsBox, then boxNormal at o + d t where t is finite (a miss returns 0 or inf: 0 leaves
+   the origin itself, inf has no point and writes a zero normal). */
+OR_API void or_box_batch(const rt_ray *rays, float xs, float ys, float zs, float *t_out, rt_vec3 *nrm, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const rt_ray *r = &rays[i];
+        const float t = or_intersects_box(r, xs, ys, zs);
+        t_out[i] = t;
+        rt_hit_info h;
+        memset(&h, 0, sizeof(h));
+        if (rt_fabsf(t) < rt_inff()) {
+            h.hit_pt.x = r->o.x + r->d.x * t;
+            h.hit_pt.y = r->o.y + r->d.y * t;
+            h.hit_pt.z = r->o.z + r->d.z * t;
+            or_box_normal(&h, xs, ys, zs);
+        }
+        nrm[i] = h.surface_normal;
+    }
+}
+
+OR_API void or_camera_batch(const rt_camera *cams, const int32_t *cam_idx, const float *a, const float *b,
+                            rt_vec3 *out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = camera_ray(&cams[cam_idx[i]], a[i], b[i]).d;
+}
+
+/* fn 0: perpendicular_vector(v); 1: shading_to_world(v, nrm); 2: world_to_shading(v, nrm). */
+OR_API void or_frame_batch(int fn, const rt_vec3 *v, const rt_vec3 *nrm, rt_vec3 *out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        if (fn == 0) out[i] = perpendicular_vector(v[i]);
+        else if (fn == 1) out[i] = shading_to_world(v[i], nrm[i]);
+        else out[i] = world_to_shading(v[i], nrm[i]);
+    }
+}
+
+OR_API void or_cos_hemisphere_batch(const float *r1, const float *r2, rt_vec3 *out, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = cos_sample_hemisphere(r1[i], r2[i]);
+}
+
+OR_API void or_phong_batch(const rt_vec3 *w, const float *spec_exp, const float *r1, const float *r2, rt_vec3 *out,
+                           size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        out[i] = w[i];
+        sample_phong(&out[i], spec_exp[i], r1[i], r2[i]);
+    }
+}
+
+/* sampleRefraction on rays[i] in place (d and propagation change); ret: its return value. */
+OR_API void or_refraction_batch(rt_ray *rays, const float *ior, const float *blur_exp, const float *r1,
+                                const float *r2, int32_t *ret, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        ret[i] = sample_refraction(&rays[i].propagation, &rays[i], ior[i], blur_exp[i], r1[i], r2[i]);
+}
+
+/* sphereEmissiveRadiance on rays[i] in place (o read; d, tmin, tmax written). */
+OR_API void or_emissive_batch(rt_ray *rays, const rt_vec3 *c, const float *radius, const float *r1, const float *r2,
+                              size_t n)
+{
+    for (size_t i = 0; i < n; ++i) or_sphere_emissive_radiance(&rays[i], c[i], radius[i], r1[i], r2[i]);
+}
+
+/* sample_material on rays[i] / seeds[i] in place; hits: hit point and normal; mats[mat_idx[i]]. */
+OR_API void or_sample_material_batch(rt_ray *rays, const rt_hit_info *hits, const rt_material *mats,
+                                     const int32_t *mat_idx, uint32_t *seeds, int32_t *ret, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        rt_seed s = {seeds[2 * i], seeds[2 * i + 1]};
+        ret[i] = or_sample_material(&rays[i], &hits[i], &mats[mat_idx[i]], &s);
+        seeds[2 * i] = s.x;
+        seeds[2 * i + 1] = s.y;
+    }
 }
