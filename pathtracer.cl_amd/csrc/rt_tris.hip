@@ -638,8 +638,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                     (!SPLIT && a.mesh_bounds && !tri_hit && (shadow || depth > 0) && /* (short frames: never split) */
                      segment_misses_box(qo, qd, RT_SMALL_F, qt, a.mesh_lo, a.mesh_hi))) { /* off the mesh */
                     ts.best = -2; /* no hit, without a traversal */
-                    fin = true;
-                    ++cnt[RT_CNT_SKIPPED];
+                    fin = true; /* (counted below) */
                 } else {
                     trav_begin(ts, stk, qo, qd, qt);
                     if (shadow) ts.node = (int)a.shadow_root; /* the shadow queries' tree */
@@ -669,6 +668,12 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                     }
                 }
             }
+            /* the answers without a traversal are counted here, from the block's outcome (a pending
+               lane leaves it with best = -2 only that way), and not inside it: a 64-bit value changed
+               under the block's exec mask — the counter, or a 0 / 1 to add to it — was spilled at the
+               block's end before the mask was restored (counting instantiations built without SLP
+               packing), and the lanes outside the block read back a stale slot */
+            cnt[RT_CNT_SKIPPED] += (pending && ts.best == -2) ? 1ull : 0ull;
             const unsigned long long t_c0 = (COUNT || RT_PLAIN_PIXEL_STATS) ? wave_clock() : 0ull;
             if (COUNT || RT_PLAIN_PIXEL_STATS) pix_ab += t_c0 - t_d1;
             /* The exit threshold follows the wave's live queries: with few lanes left (the
