@@ -77,6 +77,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -89,10 +90,9 @@ public:
     enum Key { KEY_LEFT, KEY_RIGHT, KEY_UP, KEY_DOWN };
 
     ProgressiveViewHIP(RayTracerHIP &rt, unsigned width, unsigned height, int kernel = RT_KERNEL_SPHERES)
-        : rt_(rt), width_(width), height_(height), kernel_(kernel)
+        : rt_(rt), width_(width), height_(height), kernel_(kernel), buf_(new Buffers)
     {
     }
-    ~ProgressiveViewHIP() { release(); }
     ProgressiveViewHIP(const ProgressiveViewHIP &) = delete;
     ProgressiveViewHIP &operator=(const ProgressiveViewHIP &) = delete;
 
@@ -161,23 +161,19 @@ public:
     bool updateMesh(const float *verts_xyz, uint32_t n_verts, int flags = 0)
     {
         const bool carryMotion = motionCarry_ && temporal_ && haveHist_ && !realloc_;
-        if (carryMotion && !(posePending_ && poseVerts_ == n_verts)) {
-            if (poseVerts_ != n_verts) {
-                if (posePrev_) (void)hipFree(posePrev_);
-                posePrev_ = nullptr;
-                poseVerts_ = n_verts;
+        Buffers &b = *buf_;
+        if (carryMotion && !(posePending_ && b.poseVerts == n_verts)) {
+            if (b.poseVerts != n_verts) {
+                b.posePrev.drop();
+                b.poseVerts = n_verts;
             }
-            alloc(posePrev_, (size_t)n_verts * 3 * sizeof(float), "pose snapshot");
-            rt_.meshPose(posePrev_, n_verts, true);
+            b.posePrev.need((size_t)n_verts * 3, "pose snapshot");
+            rt_.meshPose(b.posePrev.p, n_verts, true);
             posePending_ = true;
         }
         rt_.updateMesh(verts_xyz, n_verts, flags);
         featDirty_ = true;
-        if (!carryMotion) {
-            haveHist_ = false;
-            momValid_ = false;
-            posePending_ = false;
-        }
+        if (!carryMotion) dropHistory();
         const bool post = restart();
         if (!carryMotion) carry_ = false;
         return post;
@@ -208,11 +204,7 @@ public:
     bool sceneChanged()
     {
         featDirty_ = true;
-        if (!trust_) {
-            haveHist_ = false;
-            momValid_ = false;
-            posePending_ = false;
-        }
+        if (!trust_) dropHistory();
         const bool post = restart();
         if (!trust_) carry_ = false;
         return post;
@@ -229,8 +221,7 @@ public:
     {
         if (on && !temporal_) {
             featDirty_ = true;
-            haveHist_ = false;
-            posePending_ = false;
+            dropHistory(false); /* the moments follow the accumulation buffer, not the display */
         }
         temporal_ = on;
         temporalParams_ = params;
@@ -240,9 +231,7 @@ public:
     {
         if (on && !varGuided_) {
             featDirty_ = true;
-            haveHist_ = false;
-            momValid_ = false;
-            posePending_ = false;
+            dropHistory();
         }
         varGuided_ = on;
         varParams_ = params;
@@ -255,7 +244,8 @@ public:
     {
         if (!denoise_ && !temporal_ && !varGuided_) return pbo_;
         raw_.assign(pbo_.size(), 0.0f);
-        if (dev_ && hipMemcpy(raw_.data(), dev_, raw_.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        const float *dev = buf_->dev.p;
+        if (dev && hipMemcpy(raw_.data(), dev, raw_.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             throw std::runtime_error("ProgressiveViewHIP: raw frame readback failed");
         return raw_;
     }
@@ -275,209 +265,216 @@ private:
         rt_.setCameraSpherical(target, elevation_, azimuth_, distance_);
         featDirty_ = true;
     }
+    /* device memory with one owner: allocated when first needed, freed when dropped or destroyed */
+    struct DeviceFloats {
+        float *p = nullptr;
+        DeviceFloats() = default;
+        DeviceFloats(const DeviceFloats &) = delete;
+        DeviceFloats &operator=(const DeviceFloats &) = delete;
+        ~DeviceFloats() { drop(); }
+        void need(size_t floats, const char *what)
+        {
+            if (!p && hipMalloc(&p, floats * sizeof(float)) != hipSuccess)
+                throw std::runtime_error(std::string("ProgressiveViewHIP: ") + what + " allocation failed");
+        }
+        void drop()
+        {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+    };
+    /* What setTemporal keeps of a displayed quantity: the merged frame of the last display, and the one
+       carried into the current view, which every display of that view merges with.  Each is an RGBA
+       frame followed by its plane of history lengths. */
+    struct History {
+        struct Pair {
+            DeviceFloats buf;
+            size_t px = 0;
+            float *rgba() const { return buf.p; }
+            float *len() const { return buf.p + 4 * px; }
+        } kept, carried;
+        void need(size_t pixels, const char *what)
+        {
+            kept.px = carried.px = pixels;
+            kept.buf.need(5 * pixels, what);
+            carried.buf.need(5 * pixels, what);
+        }
+    };
+    /* everything the view holds on the device for one frame size: a reshape replaces the lot */
+    struct Buffers {
+        DeviceFloats dev;      /* the accumulation buffer the tracer renders into */
+        DeviceFloats den;      /* setDenoise / setVarianceGuided: the filtered frame */
+        DeviceFloats feat;     /* the view's first-hit features */
+        DeviceFloats featPrev; /* setTemporal: the features the kept frame was displayed with */
+        History colour;        /* setTemporal: the displayed frame */
+        /* setMotionCarry: the pose the kept frame was displayed in (a device copy taken at the first
+           updateMesh after a display), and the current features warped into it */
+        DeviceFloats posePrev, featWarp;
+        uint32_t poseVerts = 0;
+        DeviceFloats trustLen; /* setHistoryTrust: the lengths the carried history still deserves at this display */
+        /* setVarianceGuided: the accumulation buffer before the frame, the view's moments, with
+           setTemporal their history, the variance plane and (without setTemporal) the plane of history lengths */
+        DeviceFloats accPrev, mom, var, len;
+        History moments;
+    };
+
+    /* What earlier frames left is no longer valid: the next display starts the history afresh (and
+       the moments, unless the caller keeps them). */
+    void dropHistory(bool moments = true)
+    {
+        haveHist_ = false;
+        posePending_ = false;
+        if (moments) momValid_ = false;
+    }
     void allocate()
     {
-        release();
-        if (hipMalloc(&dev_, (size_t)width_ * height_ * 4 * sizeof(float)) != hipSuccess)
-            throw std::runtime_error("ProgressiveViewHIP: framebuffer allocation failed");
+        buf_.reset(new Buffers); /* frees the old size's buffers, the pose snapshot among them */
+        buf_->dev.need((size_t)width_ * height_ * 4, "framebuffer");
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
         featDirty_ = true;
-        haveHist_ = false;
-        momValid_ = false;
-        posePending_ = false;
+        dropHistory();
     }
-    void release()
+    /* The view's features, rendered again where a camera move, a mesh or scene change or a setter has
+       made them stale.  Returns the features the kept frame was displayed with: with setTemporal a
+       re-render keeps the previous ones (the swap) and makes this display carry the history. */
+    const float *refreshFeatures()
     {
-        if (dev_) (void)hipFree(dev_);
-        if (den_) (void)hipFree(den_);
-        if (feat_) (void)hipFree(feat_);
-        if (featPrev_) (void)hipFree(featPrev_);
-        if (hist_) (void)hipFree(hist_);
-        if (carried_) (void)hipFree(carried_);
-        for (float *b : {accPrev_, mom_, momHist_, momCarried_, var_, len_, featWarp_, posePrev_, trustLen_})
-            if (b) (void)hipFree(b);
-        dev_ = den_ = feat_ = featPrev_ = hist_ = carried_ = nullptr;
-        accPrev_ = mom_ = momHist_ = momCarried_ = var_ = len_ = featWarp_ = posePrev_ = trustLen_ = nullptr;
-        poseVerts_ = 0;
-    }
-    void alloc(float *&buf, size_t bytes, const char *what)
-    {
-        if (!buf && hipMalloc(&buf, bytes) != hipSuccess)
-            throw std::runtime_error(std::string("ProgressiveViewHIP: ") + what + " allocation failed");
-    }
-    /* the merged frame of this display into hist_ (colour, then its plane of history lengths); with
-       setVarianceGuided the view's moments mom_ go the same way into momHist_ */
-    void mergeTemporal()
-    {
-        const size_t px = (size_t)width_ * height_, frame = px * 4 * sizeof(float);
-        /* hist_ / carried_: a colour frame followed by its plane of history lengths */
-        alloc(feat_, 2 * frame, "feature buffer");
-        alloc(featPrev_, 2 * frame, "feature buffer");
-        alloc(hist_, frame + px * sizeof(float), "history buffer");
-        alloc(carried_, frame + px * sizeof(float), "history buffer");
-        if (varGuided_) {
-            alloc(momHist_, frame + px * sizeof(float), "moments history buffer");
-            alloc(momCarried_, frame + px * sizeof(float), "moments history buffer");
-        }
-        const rt_camera cam = rt_.getCamera(width_);
-        const float *histFeat = feat_; /* the features of the view the kept frame was displayed in */
-        if (featDirty_) {
-            std::swap(feat_, featPrev_);
-            histFeat = featPrev_;
-            rt_.renderFeatures(feat_, width_, height_, kernel_, true);
-            featDirty_ = false;
+        Buffers &b = *buf_;
+        const size_t floats = (size_t)width_ * height_ * 8;
+        b.feat.need(floats, "feature buffer");
+        if (temporal_) b.featPrev.need(floats, "feature buffer");
+        if (!featDirty_) return b.feat.p;
+        if (temporal_) {
+            std::swap(b.feat.p, b.featPrev.p);
             carry_ = true;
         }
+        rt_.renderFeatures(b.feat.p, width_, height_, kernel_, true);
+        featDirty_ = false;
+        return temporal_ ? b.featPrev.p : b.feat.p;
+    }
+    /* The merged frame of this display into the colour history's kept pair; with setVarianceGuided the
+       view's moments go the same way into theirs.  Both take their lengths from the colour history:
+       they keep one length. */
+    void mergeTemporal(const float *histFeat, float n)
+    {
+        Buffers &b = *buf_;
+        const size_t px = (size_t)width_ * height_;
+        b.colour.need(px, "history buffer");
+        if (varGuided_) b.moments.need(px, "moments history buffer");
+        const History *const hist[] = {&b.colour, &b.moments}; /* the active ones, and what this display merges into each */
+        const float *const cur[] = {b.dev.p, b.mom.p};
+        const int nHist = varGuided_ ? 2 : 1;
+        const rt_camera cam = rt_.getCamera(width_);
         const bool judged = trust_ && haveHist_; /* a history exists: it is judged at every display */
-        if (!haveHist_) { /* after a (re)allocation: no history anywhere */
-            if (hipMemset(carried_, 0, frame + px * sizeof(float)) != hipSuccess ||
-                (varGuided_ && hipMemset(momCarried_, 0, frame + px * sizeof(float)) != hipSuccess) ||
-                hipDeviceSynchronize() != hipSuccess)
-                throw std::runtime_error("ProgressiveViewHIP: history reset failed");
-        } else if (carry_) { /* a new accumulation begins: carry the kept frame into it */
-            const float *curFeat = feat_;
+        if (!haveHist_) { /* after a (re)allocation or a drop: no history anywhere */
+            bool ok = true;
+            for (int i = 0; i < nHist; ++i) ok = ok && hipMemset(hist[i]->carried.rgba(), 0, 5 * px * sizeof(float)) == hipSuccess;
+            if (!ok || hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("ProgressiveViewHIP: history reset failed");
+        } else if (carry_) { /* a new accumulation begins: carry the kept frames into it */
+            const float *curFeat = b.feat.p;
             rt_reproject_params prm = temporalParams_;
             if (posePending_) { /* the mesh has moved since: the taps are sought where the material was */
-                alloc(featWarp_, 2 * frame, "feature buffer");
-                rt_.warpFeatures(feat_, posePrev_, poseVerts_, featWarp_, width_, height_, true);
-                curFeat = featWarp_;
+                b.featWarp.need(8 * px, "feature buffer");
+                rt_.warpFeatures(b.feat.p, b.posePrev.p, b.poseVerts, b.featWarp.p, width_, height_, true);
+                curFeat = b.featWarp.p;
                 prm.max_history = std::fmin(temporalParams_.max_history, motionMaxHistory_);
             }
-            rt_.reproject(hist_, hist_ + 4 * px, histFeat, histCam_, curFeat, carried_, carried_ + 4 * px, width_, height_, prm,
-                          true);
-            if (varGuided_) /* the same lengths, features and cameras: the colour's taps and weights */
-                rt_.reproject(momHist_, hist_ + 4 * px, histFeat, histCam_, curFeat, momCarried_, momCarried_ + 4 * px, width_,
-                              height_, prm, true);
+            for (int i = 0; i < nHist; ++i) /* the same lengths, features and cameras: the same taps and weights */
+                rt_.reproject(hist[i]->kept.rgba(), b.colour.kept.len(), histFeat, histCam_, curFeat, hist[i]->carried.rgba(),
+                              hist[i]->carried.len(), width_, height_, prm, true);
         }
         posePending_ = false;
         carry_ = false;
-        const float n = (float)(progression_ > 1 ? progression_ : 1);
         /* the lengths the merges blend by: the carried ones, or with setHistoryTrust what this display's
-           accumulation buffer leaves of them (one plane for colour and moments: they keep one length) */
-        const float *colLen = carried_ + 4 * px, *momLen = varGuided_ ? momCarried_ + 4 * px : nullptr;
+           accumulation buffer leaves of the colour's (one plane for both) */
         if (judged) {
-            alloc(trustLen_, px * sizeof(float), "trusted history length buffer");
-            rt_.historyTrust(carried_, carried_ + 4 * px, dev_, n, feat_, trustLen_, width_, height_, trustParams_, true);
-            colLen = momLen = trustLen_;
+            b.trustLen.need(px, "trusted history length buffer");
+            rt_.historyTrust(b.colour.carried.rgba(), b.colour.carried.len(), b.dev.p, n, b.feat.p, b.trustLen.p, width_, height_,
+                             trustParams_, true);
         }
-        rt_.temporalMerge(carried_, colLen, dev_, n, temporalParams_.max_history, hist_, hist_ + 4 * px, width_, height_, true);
-        if (varGuided_)
-            rt_.temporalMerge(momCarried_, momLen, mom_, n, temporalParams_.max_history, momHist_, momHist_ + 4 * px, width_,
-                              height_, true);
+        for (int i = 0; i < nHist; ++i)
+            rt_.temporalMerge(hist[i]->carried.rgba(), judged ? b.trustLen.p : hist[i]->carried.len(), cur[i], n,
+                              temporalParams_.max_history, hist[i]->kept.rgba(), hist[i]->kept.len(), width_, height_, true);
         histCam_ = cam;
         haveHist_ = true;
-    }
-    void traceTemporal()
-    {
-        const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
-        if (denoise_) alloc(den_, frame, "denoised framebuffer");
-        mergeTemporal();
-        const float *shown = hist_;
-        if (denoise_) {
-            rt_.denoise(hist_, feat_, den_, width_, height_, denoiseParams_, true);
-            shown = den_;
-        }
-        if (hipMemcpy(pbo_.data(), shown, frame, hipMemcpyDeviceToHost) != hipSuccess)
-            throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
     }
     /* before a render that refines the accumulation buffer: its copy, for the frame's own sample */
     void keepAccumulation()
     {
-        const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
-        alloc(accPrev_, frame, "accumulation copy");
-        if (progression_ > 1 &&
-            (hipMemcpy(accPrev_, dev_, frame, hipMemcpyDeviceToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+        Buffers &b = *buf_;
+        const size_t frame = (size_t)width_ * height_ * 4;
+        b.accPrev.need(frame, "accumulation copy");
+        if (progression_ > 1 && (hipMemcpy(b.accPrev.p, b.dev.p, frame * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
+                                 hipDeviceSynchronize() != hipSuccess))
             throw std::runtime_error("ProgressiveViewHIP: accumulation copy failed");
     }
-    void traceVarianceGuided()
+    /* setVarianceGuided without setTemporal: one view, n frames everywhere */
+    const float *constantLengths(float n)
     {
-        const size_t px = (size_t)width_ * height_, frame = px * 4 * sizeof(float);
-        alloc(mom_, frame, "moments buffer");
-        alloc(var_, px * sizeof(float), "variance buffer");
-        alloc(den_, frame, "denoised framebuffer");
-        /* (without valid moments, after it was switched on in mid-accumulation: start from this frame) */
-        const float n = (float)(progression_ > 1 ? progression_ : 1);
-        rt_.momentsAccumulate(accPrev_, dev_, momValid_ ? n : 1.0f, mom_, mom_, width_, height_, true);
-        momValid_ = true;
-        const float *shown = dev_, *moments = mom_, *len = nullptr;
-        if (temporal_) {
-            mergeTemporal();
-            shown = hist_;
-            moments = momHist_;
-            len = hist_ + 4 * px;
-        } else {
-            alloc(feat_, 2 * frame, "feature buffer");
-            alloc(len_, px * sizeof(float), "history length buffer");
-            if (featDirty_) {
-                rt_.renderFeatures(feat_, width_, height_, kernel_, true);
-                featDirty_ = false;
-            }
-            const std::vector<float> lens(px, n); /* one view, n frames everywhere */
-            if (hipMemcpy(len_, lens.data(), px * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-                throw std::runtime_error("ProgressiveViewHIP: history length upload failed");
-            len = len_;
-        }
-        rt_.variance(shown, moments, len, feat_, var_, width_, height_, varParams_, true);
-        rt_.denoiseVar(shown, var_, feat_, den_, nullptr, width_, height_, varParams_, true);
-        if (hipMemcpy(pbo_.data(), den_, frame, hipMemcpyDeviceToHost) != hipSuccess)
-            throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
+        const size_t px = (size_t)width_ * height_;
+        buf_->len.need(px, "history length buffer");
+        const std::vector<float> lens(px, n);
+        if (hipMemcpy(buf_->len.p, lens.data(), px * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            throw std::runtime_error("ProgressiveViewHIP: history length upload failed");
+        return buf_->len.p;
     }
+    /* One traced display, whatever is switched on: render, then compose what is shown from the
+       accumulation buffer, which every stage only reads. */
     void trace()
     {
+        Buffers &b = *buf_;
+        const size_t px = (size_t)width_ * height_;
+        const float n = (float)(progression_ > 1 ? progression_ : 1);
         if (varGuided_) keepAccumulation();
-        rt_.rayTrace(dev_, width_, height_, progression_, kernel_, true);
+        rt_.rayTrace(b.dev.p, width_, height_, progression_, kernel_, true);
         if (varGuided_) {
-            traceVarianceGuided();
-        } else if (temporal_) {
-            traceTemporal();
-        } else if (denoise_) {
-            const size_t frame = (size_t)width_ * height_ * 4 * sizeof(float);
-            if (!den_ && hipMalloc(&den_, frame) != hipSuccess)
-                throw std::runtime_error("ProgressiveViewHIP: denoised framebuffer allocation failed");
-            if (!feat_ && hipMalloc(&feat_, 2 * frame) != hipSuccess)
-                throw std::runtime_error("ProgressiveViewHIP: feature buffer allocation failed");
-            if (featDirty_) {
-                rt_.renderFeatures(feat_, width_, height_, kernel_, true);
-                featDirty_ = false;
-            }
-            rt_.denoise(dev_, feat_, den_, width_, height_, denoiseParams_, true);
-            if (hipMemcpy(pbo_.data(), den_, frame, hipMemcpyDeviceToHost) != hipSuccess)
-                throw std::runtime_error("ProgressiveViewHIP: denoised frame readback failed");
-        } else {
-            rt_.read(pbo_.data(), pbo_.size()); /* the non-sharing readback into the PBO */
+            b.mom.need(4 * px, "moments buffer");
+            /* (without valid moments, after it was switched on in mid-accumulation: start from this frame) */
+            rt_.momentsAccumulate(b.accPrev.p, b.dev.p, momValid_ ? n : 1.0f, b.mom.p, b.mom.p, width_, height_, true);
+            momValid_ = true;
         }
+        const float *histFeat = varGuided_ || denoise_ || temporal_ ? refreshFeatures() : nullptr;
+        /* what is displayed, its moments and its history lengths */
+        const float *shown = b.dev.p, *moments = b.mom.p, *len = nullptr;
+        if (temporal_) {
+            mergeTemporal(histFeat, n);
+            shown = b.colour.kept.rgba();
+            moments = b.moments.kept.rgba();
+            len = b.colour.kept.len();
+        } else if (varGuided_) {
+            len = constantLengths(n);
+        }
+        if (varGuided_ || denoise_) b.den.need(4 * px, "denoised framebuffer");
+        if (varGuided_) { /* in place of setDenoise's filter, whether that is on or not */
+            b.var.need(px, "variance buffer");
+            rt_.variance(shown, moments, len, b.feat.p, b.var.p, width_, height_, varParams_, true);
+            rt_.denoiseVar(shown, b.var.p, b.feat.p, b.den.p, nullptr, width_, height_, varParams_, true);
+            shown = b.den.p;
+        } else if (denoise_) {
+            rt_.denoise(shown, b.feat.p, b.den.p, width_, height_, denoiseParams_, true);
+            shown = b.den.p;
+        }
+        if (shown == b.dev.p) /* nothing is switched on: the non-sharing readback into the PBO */
+            rt_.read(pbo_.data(), pbo_.size());
+        else if (hipMemcpy(pbo_.data(), shown, 4 * px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
         rendered_ = true;
     }
 
     RayTracerHIP &rt_;
     unsigned width_, height_;
     int kernel_;
-    float *dev_ = nullptr;  /* the accumulation buffer the tracer renders into */
-    float *den_ = nullptr;  /* setDenoise: the filtered frame */
-    float *feat_ = nullptr; /* setDenoise: the view's first-hit features */
+    std::unique_ptr<Buffers> buf_; /* never null: a reshape frees the lot by starting a new one */
     bool denoise_ = false, featDirty_ = true;
-    /* setTemporal: the last displayed frame (merged colour + history length), its features and
-       camera; the history carried into the current view (colour + length) */
-    float *hist_ = nullptr, *featPrev_ = nullptr, *carried_ = nullptr;
+    /* setTemporal: the camera of the kept frame; whether there is one; whether this display carries it */
     rt_camera histCam_{};
     bool temporal_ = false, haveHist_ = false, carry_ = false;
-    /* setMotionCarry: the pose the kept frame was displayed in (a device copy taken at the first
-       updateMesh after a display), and the current features warped into it */
-    float *posePrev_ = nullptr, *featWarp_ = nullptr;
-    uint32_t poseVerts_ = 0;
     bool motionCarry_ = false, posePending_ = false;
     float motionMaxHistory_ = 8.0f;
-    /* setHistoryTrust: the plane of history lengths the carried history still deserves at this display */
-    float *trustLen_ = nullptr;
     bool trust_ = false;
     rt_trust_params trustParams_ = RayTracerHIP::trustDefaults();
     rt_reproject_params temporalParams_ = RayTracerHIP::reprojectDefaults();
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
-    /* setVarianceGuided: the accumulation buffer before the frame, the view's moments, with
-       setTemporal their merged and carried histories (moments + length plane, as hist_ / carried_),
-       the variance plane and (without setTemporal) the plane of history lengths */
-    float *accPrev_ = nullptr, *mom_ = nullptr, *momHist_ = nullptr, *momCarried_ = nullptr, *var_ = nullptr,
-          *len_ = nullptr;
     bool varGuided_ = false, momValid_ = false;
     rt_denoise_var_params varParams_ = RayTracerHIP::denoiseVarDefaults();
     std::vector<float> pbo_, raw_;

@@ -147,6 +147,19 @@ bool share_comm_id(const std::string &path, int rank, uint8_t id[RT_COMM_ID_BYTE
     return false;
 }
 
+/* The numeric value that may follow a flag: argv[i + 1] if it starts with a digit (or, where the flag
+   takes it, is "inf"), and then i moves on to it; else nullptr and the flag keeps its default. */
+const char *optional_number(int argc, char **argv, int &i, bool or_inf = false)
+{
+    if (i + 1 >= argc) return nullptr;
+    const char *v = argv[i + 1];
+    const bool number = (v[0] >= '0' && v[0] <= '9') || (or_inf && !std::strcmp(v, "inf"));
+    return number ? argv[++i] : nullptr;
+}
+
+/* one more frame at the end of a --frames-out / --raw-frames-out / --features-out file */
+bool append(FILE *f, const std::vector<float> &frame) { return std::fwrite(frame.data(), 4, frame.size(), f) == frame.size(); }
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -172,28 +185,27 @@ int main(int argc, char **argv)
         }
         if (a == "--denoise") { /* an optional pass count follows */
             denoise = true;
-            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') den_params.iterations = (unsigned)std::atoi(argv[++i]);
+            if ((v = optional_number(argc, argv, i))) den_params.iterations = (unsigned)std::atoi(v);
             continue;
         }
         if (a == "--temporal") { /* an optional history cap follows */
             temporal = true;
-            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') temporal_params.max_history = (float)std::atof(argv[++i]);
+            if ((v = optional_number(argc, argv, i))) temporal_params.max_history = (float)std::atof(v);
             continue;
         }
         if (a == "--motion-carry") { /* an optional history cap follows */
             motion_carry = true;
-            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') motion_max_history = (float)std::atof(argv[++i]);
+            if ((v = optional_number(argc, argv, i))) motion_max_history = (float)std::atof(v);
             continue;
         }
         if (a == "--history-trust") { /* an optional tolerance follows ("inf": everything is trusted) */
             trust = true;
-            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || !std::strcmp(argv[i + 1], "inf")))
-                trust_params.tolerance = (float)std::atof(argv[++i]);
+            if ((v = optional_number(argc, argv, i, true))) trust_params.tolerance = (float)std::atof(v);
             continue;
         }
         if (a == "--variance-guided") { /* an optional luminance tolerance follows */
             var_guided = true;
-            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') var_params.sigma_lum = (float)std::atof(argv[++i]);
+            if ((v = optional_number(argc, argv, i))) var_params.sigma_lum = (float)std::atof(v);
             continue;
         }
         if (!(v = next())) return usage();
@@ -303,18 +315,12 @@ int main(int argc, char **argv)
                 if (ev == "d") {
                     post = view.display();
                     traced = view.rendered();
-                    if (traced && fo) {
-                        const std::vector<float> &px = view.pixels();
-                        if (std::fwrite(px.data(), 4, px.size(), fo) != px.size()) return 1;
-                    }
-                    if (traced && fr) {
-                        const std::vector<float> &px = view.rawPixels();
-                        if (std::fwrite(px.data(), 4, px.size(), fr) != px.size()) return 1;
-                    }
+                    if (traced && fo && !append(fo, view.pixels())) return 1;
+                    if (traced && fr && !append(fr, view.rawPixels())) return 1;
                     if (traced && ff) {
                         std::vector<float> ft((size_t)view.width() * view.height() * 8);
                         rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
-                        if (std::fwrite(ft.data(), 4, ft.size(), ff) != ft.size()) return 1;
+                        if (!append(ff, ft)) return 1;
                     }
                 } else if (ev == "l") post = view.specialKey(ProgressiveViewHIP::KEY_LEFT);
                 else if (ev == "r") post = view.specialKey(ProgressiveViewHIP::KEY_RIGHT);
