@@ -126,6 +126,11 @@ typedef struct rt_mesh_stats {
                              hit (|det| < 1e-4 for every unit direction, geometryFuncs.h:167) */
     uint32_t n_nodes4_shadow; /* the shadow queries' 4-wide tree (host build with lights: its cost
                                  area leans toward them); 0: they walk the closest-hit tree */
+    uint32_t cone_root;   /* the lights' cone split of the shadow tree (host build, RT_LIGHT_CONE): the node
+                             of the subtree over the triangles that can occlude the lights it was built for —
+                             the shadow queries start there while the lights and the tree stay as they were
+                             (rt_render_info.shadow_start); 0: no split */
+    uint32_t n_tris_cone; /* that subtree's triangles */
 } rt_mesh_stats;
 /* BVH builder used by the next rt_set_mesh: the host binned-SAH build (default: the best
    trees) or the GPU build (LBVH over Morton codes, collapsed on the device: seconds-to-
@@ -287,6 +292,8 @@ typedef struct rt_render_info {
                                    per-pixel costs (its traversal steps), not by the cost probe */
     uint32_t schedule_pilot;    /* 1: a view's first frame, ordered by the per-pixel costs of a pilot render of
                                    a few samples per pixel (scratch seeds and framebuffer), not by the probe */
+    uint32_t shadow_start;      /* the node the shadow queries started at: rt_mesh_stats.cone_root, or the shadow
+                                   tree's root (the closest-hit tree's, 0, without one) */
 } rt_render_info;
 int rt_last_render_info(rt_ctx *ctx, rt_render_info *out);
 /* The long chains of the last sample-split render (pixels_long of them: tile-local y * W + x, the

@@ -116,7 +116,7 @@ class RtMeshStats(ctypes.Structure):
     _fields_ = [("n_tris", ctypes.c_uint32), ("n_nodes2", ctypes.c_uint32), ("depth2", ctypes.c_uint32),
                 ("n_nodes4", ctypes.c_uint32), ("depth4", ctypes.c_uint32), ("stack4", ctypes.c_uint32),
                 ("build_seconds", ctypes.c_double), ("builder", ctypes.c_uint32), ("n_tris_tree", ctypes.c_uint32),
-                ("n_nodes4_shadow", ctypes.c_uint32)]
+                ("n_nodes4_shadow", ctypes.c_uint32), ("cone_root", ctypes.c_uint32), ("n_tris_cone", ctypes.c_uint32)]
 
 
 class RtMeshUpdateInfo(ctypes.Structure):
@@ -169,6 +169,7 @@ class RtRenderInfo(ctypes.Structure):
         ("split_hit_depth", ctypes.c_uint32),
         ("schedule_measured", ctypes.c_uint32),
         ("schedule_pilot", ctypes.c_uint32),
+        ("shadow_start", ctypes.c_uint32),
     ]
 
 

@@ -302,6 +302,64 @@ static bool never_hit(const float *a, const float *p1, const float *p2)
     return bound < 0.999 * (double)1e-4f;
 }
 
+/* True when no shadow query aimed at these lights (centres, 3 floats each; radii) can ever accept
+   this triangle.  A traversed shadow ray ends on its light's sphere (rt_tris.hip: tmax is the
+   ray's own meeting with the sphere, less RT_SMALL), and it accepts a triangle only at a point P
+   of it before that end S, so its direction is (S - P) / |S - P| with |S - C| <= R' (C, R the
+   light's centre and radius; R' = 1.001 R covers the rounding of tmax and of the accepted P).
+   With cen the triangle's centroid and rt the largest distance from it to a vertex,
+   S - P = (C - cen) + (S - C) - (P - cen) differs from C - cen by at most R' + rt, so d lies
+   within theta = asin(min(1, (R' + rt) / |C - cen|)) of C - cen, and with phi in [0, pi/2] the
+   angle between C - cen and the line of N = e2 x e1, |d . N| <= |N| cos(max(0, phi - theta)).
+   The float evaluation and |d| are bounded as in never_hit, the cosine is rounded up.  A light
+   whose inflated sphere reaches the triangle (sin theta = 1) gives never_hit's own bound, which
+   a triangle of the tree fails: it sets nothing aside.  The vertices are those of the float
+   record the kernel reads (v0, v0 + e1, v0 + e2), the bound is evaluated in double.  Such a
+   triangle is never accepted by a shadow query aimed at these lights, so leaving it out of
+   their traversal changes no result bit. */
+static bool never_occludes(const float *a, const float *p1, const float *p2, const std::vector<float> &centres,
+                           const std::vector<float> &radii)
+{
+    const float e1[3] = {p1[0] - a[0], p1[1] - a[1], p1[2] - a[2]};
+    const float e2[3] = {p2[0] - a[0], p2[1] - a[1], p2[2] - a[2]};
+    const double n[3] = {(double)e2[1] * e1[2] - (double)e2[2] * e1[1], (double)e2[2] * e1[0] - (double)e2[0] * e1[2],
+                         (double)e2[0] * e1[1] - (double)e2[1] * e1[0]};
+    const double cr = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double n1 = std::fabs((double)e1[0]) + std::fabs((double)e1[1]) + std::fabs((double)e1[2]);
+    const double n2 = std::fabs((double)e2[0]) + std::fabs((double)e2[1]) + std::fabs((double)e2[2]);
+    const double u = 1.0 / 16777216.0;
+    double cen[3], rt2 = 0.0;
+    for (int k = 0; k < 3; ++k) cen[k] = (double)a[k] + ((double)e1[k] + (double)e2[k]) / 3.0;
+    for (int v = 0; v < 3; ++v) {
+        double d2 = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const double p = (double)a[k] + (v == 1 ? (double)e1[k] : v == 2 ? (double)e2[k] : 0.0);
+            d2 += (p - cen[k]) * (p - cen[k]);
+        }
+        rt2 = std::max(rt2, d2);
+    }
+    const double rt = std::sqrt(rt2);
+    for (size_t l = 0; l < radii.size(); ++l) {
+        double L[3], dist2 = 0.0, ln = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            L[k] = (double)centres[3 * l + k] - cen[k];
+            dist2 += L[k] * L[k];
+            ln += L[k] * n[k];
+        }
+        const double dist = std::sqrt(dist2);
+        const double reach = 1.001 * std::fabs((double)radii[l]) + rt;
+        double maxcos = 1.0;
+        if (reach < dist && cr > 0.0) {
+            const double st = reach / dist, ct = std::sqrt(1.0 - st * st);
+            const double cp = std::min(1.0, std::fabs(ln) / (dist * cr)), sp = std::sqrt(1.0 - cp * cp);
+            if (cp < ct) maxcos = std::min(1.0, (cp * ct + sp * st) * (1.0 + 1e-9) + 1e-12);
+        }
+        const double bound = 1.001 * (cr * maxcos + 16.0 * u * n1 * n2);
+        if (!(bound < 0.999 * (double)1e-4f)) return false;
+    }
+    return true;
+}
+
 bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, RtBvh &out,
                   std::string &err)
 {
@@ -339,7 +397,9 @@ bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint
     /* The tree holds the triangles a ray can hit (never_hit above), slots [0, n_hit); the
        rest follow in slots [n_hit, n_tris) for the linear traversal.  At least one
        triangle stays in the tree, so it is never empty. */
-    uint32_t n_hit = 0;
+    uint32_t n_hit = 0, n_cone = 0;
+    out.cone_root4 = 0;
+    out.n_cone = 0;
     if (out.cull_unhittable) {
         std::vector<uint8_t> hit(n_tris);
         for (uint32_t t = 0; t < n_tris; ++t) {
@@ -350,14 +410,43 @@ bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint
             n_hit += hit[t];
         }
         if (n_hit == 0) hit[0] = 1, n_hit = 1;
-        for (uint32_t t = 0, k = 0, r = n_hit; t < n_tris; ++t) b.perm[hit[t] ? k++ : r++] = t;
+        /* The lights' cone split: of the kept triangles, those a shadow query aimed at the given
+           lights can accept (never_occludes) go first, slots [0, n_cone), under a subtree of
+           their own (A); the others are parked under a second child of the root (B).  Only with
+           radii for every centre, and when both parts are more than a leaf. */
+        if (!out.light_radii.empty() && 3 * out.light_radii.size() == out.light_centres.size()) {
+            uint32_t n_b = 0;
+            for (uint32_t t = 0; t < n_tris; ++t) {
+                if (!hit[t]) continue;
+                const float *a = verts + 3ull * (uint32_t)idx[3ull * t];
+                const float *p1 = verts + 3ull * (uint32_t)idx[3ull * t + 1];
+                const float *p2 = verts + 3ull * (uint32_t)idx[3ull * t + 2];
+                if (never_occludes(a, p1, p2, out.light_centres, out.light_radii)) hit[t] = 2, ++n_b;
+            }
+            if (n_hit - n_b > RT_LEAF_MAX && n_b > RT_LEAF_MAX) n_cone = n_hit - n_b;
+        }
+        for (uint32_t t = 0, k = 0, m = n_cone, r = n_hit; t < n_tris; ++t)
+            b.perm[!hit[t] ? r++ : (n_cone && hit[t] == 2) ? m++ : k++] = t;
     } else {
         n_hit = n_tris;
         for (uint32_t t = 0; t < n_tris; ++t) b.perm[t] = t;
     }
     out.n_hit = n_hit;
     b.nodes.reserve(2ull * n_hit / RT_LEAF_MAX + 16);
-    const int root = b.build(0, n_hit, 1);
+    int root;
+    if (n_cone) { /* the root's two children: A over the possible occluders, B over the rest */
+        root = (int)b.nodes.size();
+        b.nodes.emplace_back();
+        b.nodes[root].box = b.bounds(0, n_hit);
+        b.nodes[root].first = 0;
+        b.nodes[root].count = n_hit;
+        const int l = b.build(0, n_cone, 2);
+        const int r = b.build(n_cone, n_hit - n_cone, 2);
+        b.nodes[root].left = l;
+        b.nodes[root].right = r;
+    } else {
+        root = b.build(0, n_hit, 1);
+    }
 
     /* Flatten: inner nodes in DFS preorder, each storing both children's boxes. */
     std::vector<int> order; /* TmpNode index per output inner node */
@@ -478,6 +567,14 @@ bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint
             }
         }
     }
+    if (n_cone && (as_leaf[b.nodes[root].left] || as_leaf[b.nodes[root].right])) {
+        /* a subtree that would be one leaf (costs that overflow): the build without the split */
+        std::vector<float> radii;
+        radii.swap(out.light_radii);
+        const bool ok = rt_build_bvh(verts, n_verts, idx, n_tris, out, err);
+        radii.swap(out.light_radii);
+        return ok;
+    }
     {
         std::vector<int> n4_src;      /* TmpNode behind each 4-wide node */
         std::vector<int> kids_of;     /* 4 TmpNode children per 4-wide node (-1 = empty) */
@@ -496,6 +593,9 @@ bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint
             int n = 0;
             if (b.nodes[id].left < 0) { /* a leaf root */
                 k[n++] = id;
+            } else if (n_cone && id == root) { /* the cone split's root keeps its two subtrees apart */
+                k[n++] = b.nodes[id].left;
+                k[n++] = b.nodes[id].right;
             } else {
                 const int l = b.nodes[id].left, r = b.nodes[id].right;
                 int best_a = 1;
@@ -655,6 +755,13 @@ bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint
             out.nodes4q.clear();
             break;
         }
+
+    if (n_cone && !out.nodes4q.empty()) { /* A: the root's first child (breadth-first: node 1) */
+        int32_t c;
+        std::memcpy(&c, &out.nodes4[24], 4);
+        out.cone_root4 = (uint32_t)c;
+        out.n_cone = n_cone;
+    }
 
     /* Triangles in leaf order: (v0, orig), (e1 = v1 - v0), (e2 = v2 - v0). */
     out.tris.assign(12ull * n_tris, 0.0f);

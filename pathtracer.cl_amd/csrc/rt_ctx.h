@@ -100,6 +100,9 @@ static_assert((kCounterBytes + kWorkWords * sizeof(uint32_t)) % sizeof(unsigned 
 #define RT_REPAIR_SLOTS 4096u /* repaired pixels with per-sample seeds by slot (8.4 MB at 256 spp) */
 #endif
 
+/* the lights' cone split of the host build's shadow tree (rt_mesh.cpp, RT_LIGHT_CONE) */
+constexpr bool kLightCone = true;
+
 /* the display-side stages with a kernel time of their own (rt_display.cpp) */
 enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_COUNT };
 
@@ -129,6 +132,15 @@ struct rt_ctx {
     std::vector<std::pair<uint32_t, uint32_t>> shadow_levels;
     bool shadow_cache = true;
     int shadow_cache_depth = -1;
+    /* the lights' cone split of the shadow tree (rt_bvh.cpp never_occludes): subtree A's node in
+       d_nodes4q (0: none), its triangles, its own levels, and the bits of the (centre, radius) of
+       every light the split was made for, 4 words each.  The shadow queries start at A while every
+       current light is one of those and the tree is as built (cone_stale: refitted since); else at
+       shadow_root (tri_scene) */
+    uint32_t cone_root = 0, n_cone = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> cone_levels;
+    std::vector<uint32_t> cone_lights;
+    bool cone_stale = false;
     DevBuf<uint16_t> d_list_code;  /* per pixel: offset in its tile's block << 5 | count - 1 (k_pixel_lists) */
     DevBuf<uint32_t> d_list_tile;  /* per 8x8 tile: first slot of its block of lists */
     DevBuf<uint32_t> d_list_alloc; /* the list area's allocator */

@@ -107,7 +107,13 @@ struct RtBvh {
     bool det_cull = true;        /* in: normal boxes in the compressed nodes (rt_quant.h determinant cull) */
     std::vector<float> light_centres; /* in: the scene's lights (3 floats each): the cost area leans toward them */
     float light_cost_weight = 0.6f;   /* in: their share of the cost area (rt_bvh.cpp Builder::area) */
+    /* in: the lights' radii, one per centre (empty: no cone split).  With them, and cull_unhittable, the
+       root's two children are subtree A over the triangles a shadow query aimed at these lights can
+       accept and subtree B over the rest (rt_bvh.cpp never_occludes) */
+    std::vector<float> light_radii;
     uint32_t n_hit = 0;          /* out: triangles in the tree (slots [0, n_hit)) */
+    uint32_t cone_root4 = 0;     /* out: A's node in nodes4 / nodes4q (0: no cone split) */
+    uint32_t n_cone = 0;         /* out: A's triangles */
 };
 
 /* Builds a binned-SAH BVH over the mesh (rt_bvh.cpp).  Returns false and sets

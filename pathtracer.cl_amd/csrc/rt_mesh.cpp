@@ -17,8 +17,10 @@ namespace {
    the root (q4: every node's RT_QNODE_DWORDS, n nodes; the links are dwords 12-15).  Both builders
    number a tree breadth-first, so level k + 1 starts where level k ends; the walk checks that on
    the links themselves and returns the levels it could confirm (the shadow cache's cut is one of
-   them, or none). */
-std::vector<std::pair<uint32_t, uint32_t>> tree_levels(const uint32_t *q4, uint32_t n, uint32_t root)
+   them, or none).  A subtree's levels (adjoining = false: the cone split's subtree A, whose nodes
+   precede its sibling's on every level) are index ranges too, each somewhere after the one before. */
+std::vector<std::pair<uint32_t, uint32_t>> tree_levels(const uint32_t *q4, uint32_t n, uint32_t root,
+                                                       bool adjoining = true)
 {
     std::vector<std::pair<uint32_t, uint32_t>> lv;
     if (!q4 || root >= n) return lv;
@@ -35,7 +37,7 @@ std::vector<std::pair<uint32_t, uint32_t>> tree_levels(const uint32_t *q4, uint3
                 ++cnt;
             }
         if (!cnt) break;
-        if (cmin != hi || cmax - cmin + 1u != cnt || cmax >= n) break; /* not a contiguous next level */
+        if ((adjoining ? cmin != hi : cmin < hi) || cmax - cmin + 1u != cnt || cmax >= n) break; /* not a contiguous next level */
         lo = cmin;
         hi = cmax + 1u;
     }
@@ -116,6 +118,10 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
     c->shadow_root = 0;
     c->n_nodes4_shadow = 0;
     c->stack4_all = g.stack4;
+    c->cone_root = c->n_cone = 0; /* (the GPU build has no cone split) */
+    c->cone_levels.clear();
+    c->cone_lights.clear();
+    c->cone_stale = false;
     c->shadow_levels.clear();
     if (c->shadow_cache && g.nodes4q) { /* the one tree's levels, read from its links */
         std::vector<uint32_t> hq((size_t)RT_QNODE_DWORDS * g.n_nodes4);
@@ -159,6 +165,12 @@ static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const
         sb.light_centres.push_back(L.center.z);
     }
     if (const char *v = getenv("RT_BVH_LIGHT_W")) sb.light_cost_weight = (float)atof(v); /* A/B knob (0: one tree) */
+    /* the lights' cone split of the shadow tree (rt_bvh.cpp never_occludes); RT_LIGHT_CONE=0: the
+       build without it */
+    bool cone = kLightCone;
+    if (const char *v = getenv("RT_LIGHT_CONE")) cone = atoi(v) != 0; /* A/B knob */
+    if (cone)
+        for (const rt_sphere &L : c->lights) sb.light_radii.push_back(L.radius);
     b.light_cost_weight = 0.0f;
     bool two = !sb.light_centres.empty() && sb.light_cost_weight > 0.0f && 2ull * n_tris < (1ull << 28);
     bool ok2 = false;
@@ -216,6 +228,20 @@ static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const
     c->shadow_root = two ? n_a : 0u;
     c->n_nodes4_shadow = two ? sb.n_nodes4 : 0u;
     c->shadow_levels = tree_levels(q4.data(), (uint32_t)(q4.size() / RT_QNODE_DWORDS), c->shadow_root);
+    c->cone_root = two && sb.cone_root4 ? n_a + sb.cone_root4 : 0u;
+    c->n_cone = c->cone_root ? sb.n_cone : 0u;
+    c->cone_levels.clear();
+    c->cone_lights.clear();
+    c->cone_stale = false;
+    if (c->cone_root) {
+        c->cone_levels = tree_levels(q4.data(), (uint32_t)(q4.size() / RT_QNODE_DWORDS), c->cone_root, false);
+        for (const rt_sphere &L : c->lights) {
+            const float w[4] = {L.center.x, L.center.y, L.center.z, L.radius};
+            uint32_t bits[4];
+            memcpy(bits, w, sizeof(bits));
+            c->cone_lights.insert(c->cone_lights.end(), bits, bits + 4);
+        }
+    }
     c->stack4_all = two ? std::max(b.stack4, sb.stack4) : b.stack4;
     c->n_tris = n_tris;
     c->mesh_serial++;
@@ -406,6 +432,7 @@ try {
     HIPCHK(c, hipMemcpyAsync(part, r.d_part, sizeof(part), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     c->mesh_serial++; /* the records have changed: the schedule, the lists and the pilot are the old mesh's */
+    c->cone_stale = true; /* and the cone split was made for the old ones: the whole shadow tree from here on */
     if (res[RT_REFIT_RES_BAD]) return fail(c, RT_ERR_STATE, "rt_update_mesh: a link of the tree is out of range");
     /* the compressed form holds every node, or none: a change either way is a rebuild (the
        half-written nodes are replaced with everything else) */
@@ -468,6 +495,8 @@ try {
     out->builder = (uint32_t)c->mesh_builder;
     out->build_seconds = c->bvh.build_seconds;
     out->n_tris_tree = c->bvh.n_hit;
+    out->cone_root = c->cone_root;
+    out->n_tris_cone = c->n_cone;
     return RT_OK;
 } RT_CATCH(err_of(c))
 

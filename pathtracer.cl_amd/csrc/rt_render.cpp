@@ -645,16 +645,29 @@ int tri_scene(rt_ctx *c, RtTriLaunch &a)
 {
     a.nodes = trav_nodes(c);
     a.shadow_root = trav_kind(c) == RT_TRAV_BVH4Q ? c->shadow_root : 0u; /* the shadow tree: compressed nodes only */
+    /* The cone split's subtree A holds every triangle a shadow query aimed at the lights it was made
+       for can accept (rt_bvh.cpp never_occludes): the queries start there while every current light
+       is, bit for bit, one of those, and the records are the build's.  Any other light (a later
+       rt_set_spheres), or a refit since, and they walk the whole shadow tree, which answers for any. */
+    bool cone = a.shadow_root && c->cone_root && !c->cone_stale;
+    for (size_t l = 0; cone && l < c->lights.size(); ++l) {
+        const float w[4] = {c->lights[l].center.x, c->lights[l].center.y, c->lights[l].center.z, c->lights[l].radius};
+        bool found = false;
+        for (size_t k = 0; !found && k + 4 <= c->cone_lights.size(); k += 4) found = !memcmp(w, &c->cone_lights[k], sizeof(w));
+        cone = found;
+    }
+    if (cone) a.shadow_root = c->cone_root;
     if (trav_kind(c) == RT_TRAV_BVH4Q && c->shadow_cache) {
-        /* the cut: a level below the root, by default kShadowCutDepth or, in a shallow tree, the
-           middle level */
-        const size_t nl = c->shadow_levels.size();
+        /* the cut: a level below the root (A's, when the queries start there), by default
+           kShadowCutDepth or, in a shallow tree, the middle level */
+        const auto &lv = cone ? c->cone_levels : c->shadow_levels;
+        const size_t nl = lv.size();
         const size_t d = c->shadow_cache_depth >= 0 ? (size_t)c->shadow_cache_depth
                                                     : std::min<size_t>(kShadowCutDepth, (nl - (nl > 0)) / 2);
         /* (the lane's word is the node's index in its level, 16 bits: a wider level is no cut) */
-        if (d >= 1 && d < nl && c->shadow_levels[d].second - c->shadow_levels[d].first <= 0xffffu) {
-            a.shadow_cut_lo = c->shadow_levels[d].first;
-            a.shadow_cut_hi = c->shadow_levels[d].second;
+        if (d >= 1 && d < nl && lv[d].second - lv[d].first <= 0xffffu) {
+            a.shadow_cut_lo = lv[d].first;
+            a.shadow_cut_hi = lv[d].second;
         }
     }
     a.tris = c->d_tris;
@@ -1026,6 +1039,7 @@ void tris_info(rt_ctx *c, const RtTriLaunch &a, const TriPlan &p)
     c->info.schedule_rebuilt = c->schedule_rebuilt ? 1u : 0u;
     c->info.schedule_host_ms = p.sched_ms;
     c->info.schedule_pilot = p.pilot ? 1u : 0u;
+    c->info.shadow_start = a.shadow_root;
     c->info_list_pending = p.lists;
 }
 

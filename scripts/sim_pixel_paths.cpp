@@ -12,7 +12,9 @@
 //       the shadow cache: over a strided sample of mesh pixels, the steps of the
 //       shadow queries from camera hits without the cache and with it at cuts 4 to 8, on the
 //       lights' tree (tree = 1, the default: built as rt_set_mesh builds it) or the closest-hit
-//       tree (0), with the kernel's cull (7) and any-hit order (5)
+//       tree (0), with the kernel's cull (7) and any-hit order (5); tree = 2: the lights' tree built
+//       with the light's radius, the queries starting at the cone split's subtree A (rt_bvh.cpp
+//       never_occludes), depths and cuts counted from A
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -112,9 +114,11 @@ static bool mt(const float *tr, V o, V d, float &t)
 static const float *g_bin; /* the host's binary tree (16 floats per node) */
 static int g_wide = 0;      /* > 0: traverse an n-wide collapse of it (query_wide) */
 static long query_wide(V o, V d, float tmax, bool any, float &t_hit, int &hit);
-static long query(V o, V d, float tmax, bool any, float &t_hit, int &hit, int start = 0)
+static int g_root = 0;      /* where a query starts unless told (sweep, tree = 2: the cone split's subtree A) */
+static long query(V o, V d, float tmax, bool any, float &t_hit, int &hit, int start = -1)
 {
     if (g_wide) return query_wide(o, d, tmax, any, t_hit, hit);
+    if (start < 0) start = g_root;
     V inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
     struct It {
         int c;
@@ -372,6 +376,7 @@ static int sweep(int argc, char **argv)
     bvh.light_cost_weight = 0.0f;
     if (!rt_build_bvh(verts.data(), (uint32_t)(verts.size() / 3), idx.data(), n_tris, bvh, err)) return 1;
     sb.light_centres = {light.x, light.y, light.z};
+    if (which == 2) sb.light_radii = {0.5f};
     if (!rt_build_bvh(verts.data(), (uint32_t)(verts.size() / 3), idx.data(), n_tris, sb, err)) return 1;
     const RtBvh &sh = which ? sb : bvh;
     auto use = [](const RtBvh &t) {
@@ -382,7 +387,13 @@ static int sweep(int argc, char **argv)
     /* depths of the shadow queries' tree (breadth-first numbering: children after parents) */
     g_depth.assign(sh.n_nodes4, 0);
     int max_depth = 0;
-    for (uint32_t i = 0; i < sh.n_nodes4; ++i)
+    const uint32_t shadow_start = which == 2 ? sh.cone_root4 : 0u;
+    if (which == 2 && !shadow_start) {
+        printf("the build made no cone split\n");
+        return 1;
+    }
+    if (which == 2) printf("cone split: %u of %u kept triangles can occlude the light\n", sh.n_cone, sh.n_hit);
+    for (uint32_t i = shadow_start; i < sh.n_nodes4; ++i)
         for (int k = 0; k < 4; ++k) {
             int c;
             memcpy(&c, &sh.nodes4[32ull * i + 24 + k], 4);
@@ -406,6 +417,7 @@ static int sweep(int argc, char **argv)
                 float t;
                 int hit;
                 use(bvh);
+                g_root = 0;
                 g_cut = 0;
                 query(pos, norm(add(add(view, mul(right, px + 0.5f - W / 2.0f)), mul(up, py + 0.5f - H / 2.0f))), 1e30f,
                       false, t, hit);
@@ -416,6 +428,7 @@ static int sweep(int argc, char **argv)
                 for (int s = 0; s < spp; ++s) {
                     const V d = norm(add(add(view, mul(right, px + U(rng) - W / 2.0f)), mul(up, py + U(rng) - H / 2.0f)));
                     use(bvh);
+                    g_root = 0;
                     g_cut = 0;
                     query(pos, d, 1e30f, false, t, hit);
                     const float r1 = U(rng), r2 = U(rng);
@@ -428,6 +441,7 @@ static int sweep(int argc, char **argv)
                     if (!(dot(ld, n) > 0)) continue;
                     const float tl = std::sqrt(dot(sub(light, so), sub(light, so))) - 0.5f;
                     use(sh);
+                    g_root = (int)shadow_start;
                     g_from_mesh = true;
                     int h2;
                     float t2;
@@ -456,7 +470,7 @@ static int sweep(int argc, char **argv)
                 }
             }
     printf("%s tree (depth %d), %d mesh pixels x %d samples: %.0f shadow queries from camera hits, %.1f%% occluded\n",
-           which ? "lights'" : "closest-hit", max_depth, pixels, spp, n_q[0] + n_q[1], 100 * n_q[1] / (n_q[0] + n_q[1]));
+           which == 2 ? "possible occluders'" : which ? "lights'" : "closest-hit", max_depth, pixels, spp, n_q[0] + n_q[1], 100 * n_q[1] / (n_q[0] + n_q[1]));
     printf("| cut | occluded | unoccluded | all | tried | answered | steps saved |\n|---|---|---|---|---|---|---|\n");
     const double all0 = steps[0][0] + steps[0][1], nq = n_q[0] + n_q[1];
     printf("| none | %.1f | %.1f | %.1f | | | |\n", steps[0][1] / n_q[1], steps[0][0] / n_q[0], all0 / nq);
