@@ -70,6 +70,20 @@
  *                    again and the progression restarts.  The history and the moments are dropped, as
  *                    updateMesh drops them without the motion carry — unless setHistoryTrust is on, which
  *                    keeps them and lets the test shorten them where the shading has changed.
+ *   setToneMap(on, params, autoExposure, meter)  (no counterpart in the reference) the last display stage
+ *                    (DESIGN.md §4.15): whatever the stages above chose to show is metered (with
+ *                    autoExposure: the exposure is a float on the device that the meter reads and writes at
+ *                    every traced display, so `meter.rate` < 1 adapts smoothly; without it params.exposure
+ *                    holds) and tone-mapped into an RGBA8 device buffer, which display() reads back into
+ *                    pixels8() (W*H words r | g << 8 | b << 16 | 255 << 24, bottom row first as
+ *                    glDrawPixels(GL_RGBA, GL_UNSIGNED_BYTE) expects).  The shown float frame is only read:
+ *                    pixels() is what it was without the stage.  The exposure starts afresh ("none") at a
+ *                    (re)allocation and when the stage is switched on; restart(), updateMesh() and
+ *                    sceneChanged() keep it.  Off (the default), nothing changes, allocation included.
+ *   setFloatReadback(on)  with setToneMap: off, display() reads back only the 8-bit frame (a quarter of
+ *                    the bytes) and pixels() keeps its last contents — those of the last display with the
+ *                    readback on, zeros before any; rawPixels() still fetches the accumulation buffer.  On
+ *                    (the default), and always without setToneMap, pixels() is read at every display.
  */
 #ifndef PROGRESSIVE_VIEW_HIP_HPP
 #define PROGRESSIVE_VIEW_HIP_HPP
@@ -238,11 +252,39 @@ public:
     }
     bool varianceGuided() const { return varGuided_; }
 
+    /* (no counterpart in the reference) the tone-mapped 8-bit display output */
+    void setToneMap(bool on, const rt_tonemap_params &params = RayTracerHIP::toneMapDefaults(), bool autoExposure = true,
+                    const rt_meter_params &meter = RayTracerHIP::meterDefaults())
+    {
+        if (on && !toneMap_) exposureReset_ = true;
+        toneMap_ = on;
+        toneParams_ = params;
+        autoExposure_ = autoExposure;
+        meterParams_ = meter;
+    }
+    bool toneMapping() const { return toneMap_; }
+    void setFloatReadback(bool on) { floatReadback_ = on; }
+    bool floatReadback() const { return floatReadback_; }
+    /* The tone-mapped frame of the last traced display with setToneMap on (empty before one). */
+    const std::vector<uint32_t> &pixels8() const { return pbo8_; }
+    /* The exposure the last traced display was tone-mapped under: the metered one, read back now, or
+       params.exposure without autoExposure; 0 before a display with setToneMap on. */
+    float exposure() const
+    {
+        if (!toneMap_ || pbo8_.empty()) return 0.0f;
+        if (!autoExposure_) return toneParams_.exposure;
+        float e = 0.0f;
+        if (!buf_->exposure.p || hipMemcpy(&e, buf_->exposure.p, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("ProgressiveViewHIP: exposure readback failed");
+        return e;
+    }
+
+    /* With setToneMap and setFloatReadback(false): the contents of the last display that read it back. */
     const std::vector<float> &pixels() const { return pbo_; }
     /* The accumulation buffer as rendered (what pixels() holds with the denoiser off), read back now. */
     const std::vector<float> &rawPixels()
     {
-        if (!denoise_ && !temporal_ && !varGuided_) return pbo_;
+        if (!denoise_ && !temporal_ && !varGuided_ && !(toneMap_ && !floatReadback_)) return pbo_;
         raw_.assign(pbo_.size(), 0.0f);
         const float *dev = buf_->dev.p;
         if (dev && hipMemcpy(raw_.data(), dev, raw_.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
@@ -316,6 +358,8 @@ private:
            setTemporal their history, the variance plane and (without setTemporal) the plane of history lengths */
         DeviceFloats accPrev, mom, var, len;
         History moments;
+        /* setToneMap: the RGBA8 frame (W*H words) and the metered exposure (one float; 0: none yet) */
+        DeviceFloats tone8, exposure;
     };
 
     /* What earlier frames left is no longer valid: the next display starts the history afresh (and
@@ -331,6 +375,8 @@ private:
         buf_.reset(new Buffers); /* frees the old size's buffers, the pose snapshot among them */
         buf_->dev.need((size_t)width_ * height_ * 4, "framebuffer");
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
+        pbo8_.clear();
+        exposureReset_ = true;
         featDirty_ = true;
         dropHistory();
     }
@@ -418,6 +464,24 @@ private:
             throw std::runtime_error("ProgressiveViewHIP: history length upload failed");
         return buf_->len.p;
     }
+    /* setToneMap: meter what is shown (the exposure float stays on the device: no host sync between the
+       meter and the tone map), then tone-map it into the 8-bit buffer. */
+    void toneMapShown(const float *shown)
+    {
+        Buffers &b = *buf_;
+        b.tone8.need((size_t)width_ * height_, "8-bit framebuffer");
+        const float *exposure = nullptr;
+        if (autoExposure_) {
+            if (!b.exposure.p) exposureReset_ = true; /* (a new float holds nothing yet) */
+            b.exposure.need(1, "exposure");
+            if (exposureReset_ && (hipMemset(b.exposure.p, 0, sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+                throw std::runtime_error("ProgressiveViewHIP: exposure reset failed");
+            exposureReset_ = false;
+            rt_.meterExposure(shown, b.exposure.p, nullptr, width_, height_, meterParams_, true, /*sync=*/false);
+            exposure = b.exposure.p;
+        }
+        rt_.toneMap(shown, exposure, reinterpret_cast<uint32_t *>(b.tone8.p), width_, height_, toneParams_, true);
+    }
     /* One traced display, whatever is switched on: render, then compose what is shown from the
        accumulation buffer, which every stage only reads. */
     void trace()
@@ -454,10 +518,18 @@ private:
             rt_.denoise(shown, b.feat.p, b.den.p, width_, height_, denoiseParams_, true);
             shown = b.den.p;
         }
-        if (shown == b.dev.p) /* nothing is switched on: the non-sharing readback into the PBO */
-            rt_.read(pbo_.data(), pbo_.size());
-        else if (hipMemcpy(pbo_.data(), shown, 4 * px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
+        if (toneMap_) toneMapShown(shown);
+        if (!toneMap_ || floatReadback_) { /* (else the 8-bit frame alone: pixels() keeps its last contents) */
+            if (shown == b.dev.p) /* nothing is switched on: the non-sharing readback into the PBO */
+                rt_.read(pbo_.data(), pbo_.size());
+            else if (hipMemcpy(pbo_.data(), shown, 4 * px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
+        }
+        if (toneMap_) {
+            pbo8_.resize(px);
+            if (hipMemcpy(pbo8_.data(), b.tone8.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: 8-bit frame readback failed");
+        }
         rendered_ = true;
     }
 
@@ -477,6 +549,10 @@ private:
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
     bool varGuided_ = false, momValid_ = false;
     rt_denoise_var_params varParams_ = RayTracerHIP::denoiseVarDefaults();
+    bool toneMap_ = false, autoExposure_ = true, exposureReset_ = true, floatReadback_ = true;
+    rt_tonemap_params toneParams_ = RayTracerHIP::toneMapDefaults();
+    rt_meter_params meterParams_ = RayTracerHIP::meterDefaults();
+    std::vector<uint32_t> pbo8_;
     std::vector<float> pbo_, raw_;
     bool realloc_ = true, rendered_ = false;
     unsigned progression_ = 0, maxProgression_ = 10000;

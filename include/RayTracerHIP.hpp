@@ -379,6 +379,45 @@ public:
         return ms;
     }
 
+    /* ---- tone-mapped 8-bit display output with auto-exposure (pathtracer_rt.h) ---- */
+    static rt_tonemap_params toneMapDefaults()
+    {
+        rt_tonemap_params p;
+        rt_tonemap_defaults(&p);
+        return p;
+    }
+    static rt_meter_params meterDefaults()
+    {
+        rt_meter_params p;
+        rt_meter_defaults(&p);
+        return p;
+    }
+    /* Meter the RGBA32F frame: *exposure_io is read as the previous exposure (not positive: none) and
+       written as the new one; hist_out: NULL, or RT_METER_BINS counts.  sync = false (device buffers): enqueued
+       on the tracer's stream without a wait — a toneMap that follows is ordered after it. */
+    void meterExposure(const float *rgba, float *exposure_io, uint32_t *hist_out, unsigned width, unsigned height,
+                       const rt_meter_params &params = meterDefaults(), bool on_device = false, bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_meter_exposure(ctx_, rgba, exposure_io, hist_out, width, height, &params, flags)
+                   : rt_meter_exposure_async(ctx_, rgba, exposure_io, hist_out, width, height, &params, flags, nullptr),
+              "meterExposure");
+    }
+    /* Tone-map the RGBA32F frame into out_rgba8 (W*H words, GL_RGBA / GL_UNSIGNED_BYTE in memory) under
+       *exposure (as meterExposure wrote it), or with NULL under params.exposure. */
+    void toneMap(const float *rgba, const float *exposure, uint32_t *out_rgba8, unsigned width, unsigned height,
+                 const rt_tonemap_params &params = toneMapDefaults(), bool on_device = false)
+    {
+        check(rt_tonemap(ctx_, rgba, exposure, out_rgba8, width, height, &params, on_device ? RT_OUT_DEVICE : 0), "toneMap");
+    }
+    /* Device time of the last tone-map kernel, or (meter) of the last meter, ms. */
+    float lastToneMapMs(bool meter = false) const
+    {
+        float ms = 0.0f;
+        check(rt_last_tonemap_ms(ctx_, meter ? &ms : nullptr, meter ? nullptr : &ms), "lastToneMapMs");
+        return ms;
+    }
+
     rt_counters counters() const
     {
         rt_counters c;

@@ -529,6 +529,68 @@ int rt_denoise_var_async(rt_ctx *ctx, const float *in_rgba, const float *in_var,
    a kernel asked for has not run. */
 int rt_last_variance_ms(const rt_ctx *ctx, float *moments_ms, float *variance_ms, float *denoise_var_ms);
 
+/* ---- tone-mapped 8-bit display output with histogram auto-exposure: the last
+   display stage, from the shown RGBA32F frame to RGBA8 (GL_RGBA / GL_UNSIGNED_BYTE in memory: the
+   word r | g << 8 | b << 16 | 255 << 24, rows in the input's order).  The rules of the calls above
+   hold: display only, no render state is changed, the frame is only read, the same stream ordering,
+   and arithmetic that a float32 restatement reproduces to the bit (no contraction, IEEE division,
+   rt_math.h's rt_powf, rt_minf, rt_maxf; lum as above).  `flags` takes RT_OUT_DEVICE only: with it
+   every buffer of a call is a device pointer, the one-float exposure included; without it every
+   buffer is host memory and the library stages them.  No input is written. ---- */
+enum { RT_TONE_CLAMP = 0, RT_TONE_REINHARD = 1, RT_TONE_ACES = 2 };
+enum { RT_METER_BINS = 384 };
+typedef struct rt_tonemap_params {
+    uint32_t curve;  /* RT_TONE_* */
+    uint32_t srgb;   /* non-zero: the sRGB transfer function before the quantisation */
+    uint32_t dither; /* non-zero: the 8x8 ordered dither */
+    float exposure;  /* the factor on the radiance, when the call is given no metered exposure; > 0 */
+    float white;     /* RT_TONE_REINHARD: the luminance that maps to 1; > 0 */
+} rt_tonemap_params;
+typedef struct rt_meter_params {
+    float key;          /* the value the metered mean luminance is brought to; > 0 */
+    float lo, hi;       /* the percentile range of the counted pixels that is metered: 0 <= lo < hi <= 1 */
+    float e_min, e_max; /* the exposure's bounds: 0 < e_min <= e_max */
+    float rate;         /* the share of the way from the previous exposure to the target, in (0, 1] */
+} rt_meter_params;
+int rt_tonemap_defaults(rt_tonemap_params *p); /* RT_TONE_ACES, 1, 1, 1.0f, 4.0f */
+int rt_meter_defaults(rt_meter_params *p);     /* 0.18f, 0.10f, 0.95f, 2^-8, 2^12, 1.0f */
+/* The meter.  Histogram, integers only: per pixel L = lum(rgb), u = L's bits; the pixel is counted
+   when 0 < u < 0x7f800000 (L positive and finite; zero, negative, NaN, +INFINITY are not), into bin
+   min(max((int)(u >> 19) - 1776, 0), 383): exponent and top four mantissa bits, 16 bins per octave
+   over 24 octaves from 2^-16 (1776 = bits(2^-16) >> 19).  hist_out: NULL, or RT_METER_BINS counts.
+   Exposure, from the counts n_i in index order: N = sum n_i; N == 0: E = prev > 0 ? prev : 1.0f.
+   Else lo_n = min((uint64)((double)lo (double)N), N - 1), hi_n = min(max((uint64)((double)hi
+   (double)N), lo_n + 1), N); with c_i the count before bin i, k_i the length of [c_i, c_i + n_i) cut
+   with [lo_n, hi_n): S = sum k_i (2 i + 1), K = hi_n - lo_n (uint64),
+   m = (float)((double)S / (double)(32 K)) - 16.0f (the mean log2 luminance of the range at bin
+   centres), Et = rt_minf(rt_maxf(key rt_powf(2.0f, -m), e_min), e_max); E = Et when !(prev > 0) or
+   prev is not finite, else prev + (Et - prev) rate.  *exposure_io is read as prev and written as E.
+   Null rgba, exposure_io or params, an empty frame, key <= 0 or NaN, lo outside [0, 1), hi outside
+   (lo, 1], e_min <= 0 or NaN or above e_max, rate outside (0, 1]: RT_ERR_ARG. */
+int rt_meter_exposure(rt_ctx *ctx, const float *rgba, float *exposure_io, uint32_t *hist_out, uint32_t width,
+                      uint32_t height, const rt_meter_params *params, int flags);
+int rt_meter_exposure_async(rt_ctx *ctx, const float *rgba, float *exposure_io, uint32_t *hist_out, uint32_t width,
+                            uint32_t height, const rt_meter_params *params, int flags, void *hip_stream);
+/* The tone map, per component c of pixel (x, y) with E = *exposure, or params->exposure when
+   `exposure` is NULL: v = c E; v = v > 0 ? v : 0 (NaN too); v = rt_minf(v, 65536.0f).  The curve:
+   RT_TONE_CLAMP nothing; RT_TONE_REINHARD L = lum(v), s = (1.0f + L iw) / (1.0f + L) with iw = 1.0f /
+   (white white) computed by the host in float, v = v s; RT_TONE_ACES v = (v (2.51f v + 0.03f)) /
+   (v (2.43f v + 0.59f) + 0.14f), every operation rounded on its own.  Then v = rt_minf(rt_maxf(v, 0),
+   1); with srgb v = v <= 0.0031308f ? 12.92f v : 1.055f rt_powf(v, 0.41666666f) - 0.055f and the same
+   clamp again; q = min((int)(v 255.0f + d), 255) with d = 0.5f, or with dither d = ((float)B + 0.5f)
+   0.015625f, B the 8x8 Bayer index of (x & 7, y & 7): with a = x ^ y, b = y and bit 0 the least
+   significant, B = a0 << 5 | b0 << 4 | a1 << 3 | b1 << 2 | a2 << 1 | b2.  out_rgba8: W*H words.
+   Null rgba, out_rgba8 or params, an empty frame, curve beyond RT_TONE_ACES, white <= 0 or NaN,
+   params->exposure <= 0 or NaN when it is used: RT_ERR_ARG. */
+int rt_tonemap(rt_ctx *ctx, const float *rgba, const float *exposure, uint32_t *out_rgba8, uint32_t width,
+               uint32_t height, const rt_tonemap_params *params, int flags);
+int rt_tonemap_async(rt_ctx *ctx, const float *rgba, const float *exposure, uint32_t *out_rgba8, uint32_t width,
+                     uint32_t height, const rt_tonemap_params *params, int flags, void *hip_stream);
+/* Device time of the last meter (the histogram's reset, both kernels) and of the last tone-map kernel
+   (HIP events of their own), ms; either pointer may be NULL (not both).  RT_ERR_STATE when a stage
+   asked for has not run. */
+int rt_last_tonemap_ms(const rt_ctx *ctx, float *meter_ms, float *tonemap_ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

@@ -55,6 +55,11 @@ RT_FEAT_BOX = -1
 RT_FEAT_NONE = -2
 RT_FEAT_SPHERE0 = -16
 
+RT_TONE_CLAMP = 0
+RT_TONE_REINHARD = 1
+RT_TONE_ACES = 2
+RT_METER_BINS = 384
+
 # --- record layouts (rt_types.h) --------------------------------------------------------
 VEC3 = ("<f4", 3)
 SPHERE_DTYPE = np.dtype(
@@ -191,6 +196,16 @@ class RtDenoiseVarParams(ctypes.Structure):
                 ("sigma_plane", ctypes.c_float), ("min_len", ctypes.c_float)]
 
 
+class RtTonemapParams(ctypes.Structure):
+    _fields_ = [("curve", ctypes.c_uint32), ("srgb", ctypes.c_uint32), ("dither", ctypes.c_uint32),
+                ("exposure", ctypes.c_float), ("white", ctypes.c_float)]
+
+
+class RtMeterParams(ctypes.Structure):
+    _fields_ = [("key", ctypes.c_float), ("lo", ctypes.c_float), ("hi", ctypes.c_float), ("e_min", ctypes.c_float),
+                ("e_max", ctypes.c_float), ("rate", ctypes.c_float)]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -275,6 +290,14 @@ SIGNATURES = {
     "rt_denoise_var_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtDenoiseVarParams), _i32,
                                     _vp]),
     "rt_last_variance_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    # tone-mapped 8-bit display output with auto-exposure (csrc/rt_tonemap.hip)
+    "rt_tonemap_defaults": (_i32, [ctypes.POINTER(RtTonemapParams)]),
+    "rt_meter_defaults": (_i32, [ctypes.POINTER(RtMeterParams)]),
+    "rt_meter_exposure": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtMeterParams), _i32]),
+    "rt_meter_exposure_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtMeterParams), _i32, _vp]),
+    "rt_tonemap": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTonemapParams), _i32]),
+    "rt_tonemap_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTonemapParams), _i32, _vp]),
+    "rt_last_tonemap_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

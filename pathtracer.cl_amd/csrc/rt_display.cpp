@@ -2,7 +2,8 @@
  * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
  * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
  * §4.10), the trust of the carried history (rt_temporal.hip, §4.14), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
- * (rt_filter.hip, §4.9 and §4.11), with their kernel times.  Every call runs through one driver
+ * (rt_filter.hip, §4.9 and §4.11), the meter and the tone map to 8 bits (rt_tonemap.hip, §4.15), with
+ * their kernel times.  Every call runs through one driver
  * (AuxCall).
  */
 #include <cmath>
@@ -572,6 +573,115 @@ try {
         if (out[k])
             if (const int r = stage_ms(c, stage[k], out[k])) return r;
     return RT_OK;
+} RT_CATCH(err_of(c))
+
+/* ---- tone-mapped 8-bit display output with auto-exposure ---- */
+
+int rt_tonemap_defaults(rt_tonemap_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->curve = RT_TONE_ACES;
+    p->srgb = 1;
+    p->dither = 1;
+    p->exposure = 1.0f;
+    p->white = 4.0f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_meter_defaults(rt_meter_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->key = 0.18f;
+    p->lo = 0.10f;
+    p->hi = 0.95f;
+    p->e_min = 0.00390625f; /* 2^-8 */
+    p->e_max = 4096.0f;     /* 2^12 */
+    p->rate = 1.0f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_meter_exposure_async(rt_ctx *c, const float *rgba, float *exposure_io, uint32_t *hist_out, uint32_t W, uint32_t H,
+                            const rt_meter_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!rgba || !exposure_io || !prm) return fail(c, RT_ERR_ARG, "rt_meter_exposure: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_meter_exposure: flags other than RT_OUT_DEVICE");
+    if (!(prm->key > 0.0f)) return fail(c, RT_ERR_ARG, "rt_meter_exposure: key is not positive"); /* <= 0 or NaN */
+    if (!(prm->lo >= 0.0f && prm->lo < 1.0f)) return fail(c, RT_ERR_ARG, "rt_meter_exposure: lo outside [0, 1)");
+    if (!(prm->hi > prm->lo && prm->hi <= 1.0f)) return fail(c, RT_ERR_ARG, "rt_meter_exposure: hi outside (lo, 1]");
+    if (!(prm->e_min > 0.0f) || !(prm->e_min <= prm->e_max))
+        return fail(c, RT_ERR_ARG, "rt_meter_exposure: e_min is not positive, or above e_max");
+    if (!(prm->rate > 0.0f && prm->rate <= 1.0f)) return fail(c, RT_ERR_ARG, "rt_meter_exposure: rate outside (0, 1]");
+    AuxCall x = {c, RT_ST_METER};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged: the frame, the exposure, then the counts (words where the other planes hold floats) */
+    const Plane pl[] = {{rgba, nullptr, 0, 4 * px},
+                        {exposure_io, exposure_io, 4 * px, 1},
+                        {nullptr, reinterpret_cast<float *>(hist_out), 4 * px + 1, RT_METER_BINS}};
+    if (!x.host && !hist_out) HIPCHK(c, c->d_meter_hist.reserve(RT_METER_BINS)); /* (allocated once, never grown) */
+    if (const int r = x.begin(pl, 3, 4 * px + 1 + RT_METER_BINS)) return r;
+    uint32_t *hist = x.host || hist_out ? reinterpret_cast<uint32_t *>(x.at(2, reinterpret_cast<float *>(hist_out)))
+                                        : c->d_meter_hist.p;
+    int e = rt_launch_lum_hist(x.at(0, rgba), W, H, hist, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "meter histogram kernel launch");
+    e = rt_launch_exposure(hist, x.at(1, exposure_io), prm->key, prm->lo, prm->hi, prm->e_min, prm->e_max, prm->rate, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "exposure kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_meter_exposure(rt_ctx *c, const float *rgba, float *exposure_io, uint32_t *hist_out, uint32_t W, uint32_t H,
+                      const rt_meter_params *prm, int flags)
+try {
+    return finish_sync(c, rt_meter_exposure_async(c, rgba, exposure_io, hist_out, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_tonemap_async(rt_ctx *c, const float *rgba, const float *exposure, uint32_t *out, uint32_t W, uint32_t H,
+                     const rt_tonemap_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!rgba || !out || !prm) return fail(c, RT_ERR_ARG, "rt_tonemap: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tonemap: flags other than RT_OUT_DEVICE");
+    if (prm->curve > RT_TONE_ACES) return fail(c, RT_ERR_ARG, "rt_tonemap: unknown curve");
+    if (!(prm->white > 0.0f)) return fail(c, RT_ERR_ARG, "rt_tonemap: white is not positive"); /* <= 0 or NaN */
+    if (!exposure && !(prm->exposure > 0.0f)) return fail(c, RT_ERR_ARG, "rt_tonemap: exposure is not positive");
+    AuxCall x = {c, RT_ST_TONEMAP};
+    if (const int r = x.open(stream, flags)) return r;
+    const size_t px = (size_t)W * H;
+    /* staged: the frame, the 8-bit frame (words), then the exposure */
+    const Plane pl[] = {{rgba, nullptr, 0, 4 * px}, {nullptr, reinterpret_cast<float *>(out), 4 * px, px}, {exposure, nullptr, 5 * px, 1}};
+    if (const int r = x.begin(pl, 3, 5 * px + 1)) return r;
+    const RtToneLaunch a = {x.at(0, rgba),
+                            exposure ? x.at(2, exposure) : nullptr,
+                            reinterpret_cast<uint32_t *>(x.at(1, reinterpret_cast<float *>(out))),
+                            W,
+                            H,
+                            prm->curve,
+                            prm->srgb,
+                            prm->dither,
+                            prm->exposure,
+                            1.0f / (prm->white * prm->white)};
+    const int e = rt_launch_tonemap(a, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "tone-map kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_tonemap(rt_ctx *c, const float *rgba, const float *exposure, uint32_t *out, uint32_t W, uint32_t H,
+               const rt_tonemap_params *prm, int flags)
+try {
+    return finish_sync(c, rt_tonemap_async(c, rgba, exposure, out, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_tonemap_ms(const rt_ctx *c, float *meter_ms, float *tonemap_ms)
+try {
+    if (!c || (!meter_ms && !tonemap_ms)) return RT_ERR_ARG;
+    if ((meter_ms && !c->stage_time[RT_ST_METER].have) || (tonemap_ms && !c->stage_time[RT_ST_TONEMAP].have))
+        return RT_ERR_STATE;
+    if (meter_ms)
+        if (const int r = stage_ms(c, RT_ST_METER, meter_ms)) return r;
+    return tonemap_ms ? stage_ms(c, RT_ST_TONEMAP, tonemap_ms) : RT_OK;
 } RT_CATCH(err_of(c))
 
 } /* extern "C" */

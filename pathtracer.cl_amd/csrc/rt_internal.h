@@ -183,7 +183,7 @@ int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, v
 size_t rt_refit_nbox_bytes(void);
 
 /* ---- the render kernels' launch structs and launchers (rt_tris.hip, rt_split.hip, rt_spheres.hip,
-   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_motion.hip, rt_filter.hip) ---- */
+   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_motion.hip, rt_filter.hip, rt_tonemap.hip) ---- */
 #ifndef RT_QHEADS
 #define RT_QHEADS 8 /* heads of the multi-head pixel queue (k_tris mq_take) */
 #endif
@@ -475,5 +475,20 @@ struct RtAtrousLaunch {
     float isn, isp;
 };
 int rt_launch_atrous(const RtAtrousLaunch &a, void *stream);
+/* -- rt_tonemap.hip -- */
+/* The tone-mapped 8-bit display output: device buffers.  The meter: hist (RT_METER_BINS
+   words) is zeroed on the stream and then counted into; the exposure kernel reads *exposure_io as the
+   previous exposure and writes the new one. */
+int rt_launch_lum_hist(const float *rgba, uint32_t W, uint32_t H, uint32_t *hist, void *stream);
+int rt_launch_exposure(const uint32_t *hist, float *exposure_io, float key, float lo, float hi, float e_min, float e_max,
+                       float rate, void *stream);
+/* exposure: one float on the device, or NULL for exposure_fixed; iw = 1 / white^2 (Reinhard) */
+struct RtToneLaunch {
+    const float *rgba, *exposure;
+    uint32_t *out;
+    uint32_t W, H, curve, srgb, dither;
+    float exposure_fixed, iw;
+};
+int rt_launch_tonemap(const RtToneLaunch &a, void *stream);
 
 #endif /* RT_INTERNAL_H */

@@ -35,6 +35,13 @@
  *              (ProgressiveViewHIP::setHistoryTrust, tolerance TOL standard deviations, default rt_trust_defaults';
  *              "inf" trusts everything); the event e:DX:DY:DZ moves every emissive sphere by (DX, DY, DZ) and
  *              calls ProgressiveViewHIP::sceneChanged())
+ *             [--tonemap [clamp|reinhard|aces]]   (the tone-mapped 8-bit display output, default aces
+ *              (rt_tonemap; with --events ProgressiveViewHIP::setToneMap: the float frames of --frames-out stay what
+ *              they are without it) [--exposure auto|VALUE] (the histogram meter, the default, or a fixed factor)
+ *              [--adapt RATE] (the meter's rate, default 1) [--no-srgb] [--no-dither]
+ *              [--ppm FILE] (binary P6 of the final shown 8-bit frame, top row first: flipped like the PFM)
+ *              [--frames8-out FILE] (with --events: every displayed RGBA8 frame, appended as W*H words)
+ *              [--exposure-log FILE] (with --events: per displayed frame the bits of its exposure, one hex word a line))
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -120,7 +127,8 @@ int usage()
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
                          "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--denoised f] [--denoised-pfm f] [--features-out f] "
-                         "[--raw-frames-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
+                         "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
+                         "[--ppm f] [--frames8-out f] [--exposure-log f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
 
@@ -160,12 +168,32 @@ const char *optional_number(int argc, char **argv, int &i, bool or_inf = false)
 /* one more frame at the end of a --frames-out / --raw-frames-out / --features-out file */
 bool append(FILE *f, const std::vector<float> &frame) { return std::fwrite(frame.data(), 4, frame.size(), f) == frame.size(); }
 
+/* binary P6 of an RGBA8 frame (bottom row first in memory), top row first */
+bool write_ppm(const std::string &path, const std::vector<uint32_t> &px, unsigned W, unsigned H)
+{
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, "P6\n%u %u\n255\n", W, H);
+    bool ok = true;
+    for (int y = (int)H - 1; y >= 0; --y)
+        for (unsigned x = 0; x < W; ++x) {
+            const uint32_t w = px[(size_t)y * W + x];
+            const unsigned char rgb[3] = {(unsigned char)(w & 255u), (unsigned char)(w >> 8 & 255u), (unsigned char)(w >> 16 & 255u)};
+            ok = ok && std::fwrite(rgb, 1, 3, f) == 3;
+        }
+    return std::fclose(f) == 0 && ok;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out, poses_path;
     bool denoise = false, temporal = false, var_guided = false, motion_carry = false, trust = false;
+    std::string ppm, frames8_out, exposure_log;
+    bool tonemap = false, auto_exposure = true;
+    rt_tonemap_params tone_params = RayTracerHIP::toneMapDefaults();
+    rt_meter_params meter_params = RayTracerHIP::meterDefaults();
     rt_trust_params trust_params = RayTracerHIP::trustDefaults();
     float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
@@ -181,6 +209,21 @@ int main(int argc, char **argv)
         const char *v = nullptr;
         if (a == "--linear") {
             linear = true;
+            continue;
+        }
+        if (a == "--no-srgb" || a == "--no-dither") {
+            (a == "--no-srgb" ? tone_params.srgb : tone_params.dither) = 0;
+            continue;
+        }
+        if (a == "--tonemap") { /* an optional curve follows */
+            tonemap = true;
+            const char *names[] = {"clamp", "reinhard", "aces"};
+            for (unsigned k = 0; k < 3 && i + 1 < argc; ++k)
+                if (!std::strcmp(argv[i + 1], names[k])) {
+                    tone_params.curve = k;
+                    ++i;
+                    break;
+                }
             continue;
         }
         if (a == "--denoise") { /* an optional pass count follows */
@@ -214,6 +257,14 @@ int main(int argc, char **argv)
         else if (a == "--denoised-pfm") den_pfm = v;
         else if (a == "--features-out") feat_out = v;
         else if (a == "--raw-frames-out") raw_frames_out = v;
+        else if (a == "--ppm") ppm = v;
+        else if (a == "--frames8-out") frames8_out = v;
+        else if (a == "--exposure-log") exposure_log = v;
+        else if (a == "--adapt") meter_params.rate = (float)std::atof(v);
+        else if (a == "--exposure") {
+            auto_exposure = !std::strcmp(v, "auto");
+            if (!auto_exposure) tone_params.exposure = (float)std::atof(v);
+        }
         else if (a == "--width") W = (unsigned)std::atoi(v);
         else if (a == "--height") H = (unsigned)std::atoi(v);
         else if (a == "--frames") frames = (unsigned)std::atoi(v);
@@ -246,6 +297,14 @@ int main(int argc, char **argv)
     }
     if (trust && !temporal) {
         std::fprintf(stderr, "rt_render: --history-trust needs --temporal (without it there is no history to judge)\n");
+        return 2;
+    }
+    if (!tonemap && (!ppm.empty() || !frames8_out.empty() || !exposure_log.empty())) {
+        std::fprintf(stderr, "rt_render: --ppm / --frames8-out / --exposure-log need --tonemap (there is no 8-bit frame without it)\n");
+        return 2;
+    }
+    if (events.empty() && (!frames8_out.empty() || !exposure_log.empty())) {
+        std::fprintf(stderr, "rt_render: --frames8-out / --exposure-log need --events (they follow a view's displays)\n");
         return 2;
     }
     if (var_guided && events.empty()) {
@@ -286,6 +345,7 @@ int main(int argc, char **argv)
             if (var_guided) view.setVarianceGuided(true, var_params);
             if (motion_carry) view.setMotionCarry(true, motion_max_history);
             if (trust) view.setHistoryTrust(true, trust_params);
+            if (tonemap) view.setToneMap(true, tone_params, auto_exposure, meter_params);
             rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
             std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
             if (!poses_path.empty()) {
@@ -304,6 +364,9 @@ int main(int argc, char **argv)
             FILE *fr = raw_frames_out.empty() ? nullptr : std::fopen(raw_frames_out.c_str(), "wb");
             FILE *ff = feat_out.empty() ? nullptr : std::fopen(feat_out.c_str(), "wb");
             if ((!raw_frames_out.empty() && !fr) || (!feat_out.empty() && !ff)) return 1;
+            FILE *f8 = frames8_out.empty() ? nullptr : std::fopen(frames8_out.c_str(), "wb");
+            FILE *fe = exposure_log.empty() ? nullptr : std::fopen(exposure_log.c_str(), "w");
+            if ((!frames8_out.empty() && !f8) || (!exposure_log.empty() && !fe)) return 1;
             size_t pos = 0;
             while (pos <= events.size()) {
                 const size_t end = std::min(events.find(',', pos), events.size());
@@ -317,6 +380,13 @@ int main(int argc, char **argv)
                     traced = view.rendered();
                     if (traced && fo && !append(fo, view.pixels())) return 1;
                     if (traced && fr && !append(fr, view.rawPixels())) return 1;
+                    if (traced && f8 && std::fwrite(view.pixels8().data(), 4, view.pixels8().size(), f8) != view.pixels8().size()) return 1;
+                    if (traced && fe) {
+                        const float e = view.exposure();
+                        uint32_t u;
+                        std::memcpy(&u, &e, 4);
+                        std::fprintf(fe, "%08x\n", u);
+                    }
                     if (traced && ff) {
                         std::vector<float> ft((size_t)view.width() * view.height() * 8);
                         rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
@@ -358,6 +428,9 @@ int main(int argc, char **argv)
             if (fo) std::fclose(fo);
             if (fr) std::fclose(fr);
             if (ff) std::fclose(ff);
+            if (f8) std::fclose(f8);
+            if (fe) std::fclose(fe);
+            if (!ppm.empty() && (view.pixels8().empty() || !write_ppm(ppm, view.pixels8(), view.width(), view.height()))) return 1;
             std::printf("{\"progression\": %u, \"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, "
                         "\"height\": %u}\n",
                         view.progression(), view.azimuth(), view.elevation(), view.width(), view.height());
@@ -442,6 +515,25 @@ int main(int argc, char **argv)
                     for (unsigned x = 0; x < W; ++x) std::fwrite(&den[((size_t)y * W + x) * 4], 4, 3, f);
                 std::fclose(f);
             }
+        }
+        if (tonemap) { /* the final shown frame (the filtered one with --denoise) through meter and tone map */
+            if (tiled) {
+                std::fprintf(stderr, "rt_render: --tonemap needs the whole frame (no --tile)\n");
+                return 1;
+            }
+            std::vector<float> shown = img;
+            if (denoise) {
+                std::vector<float> feat((size_t)W * H * 8);
+                rt.renderFeatures(feat.data(), W, H, kernel);
+                rt.denoise(img.data(), feat.data(), shown.data(), W, H, den_params);
+            }
+            float exposure = 0.0f;
+            if (auto_exposure) rt.meterExposure(shown.data(), &exposure, nullptr, W, H, meter_params);
+            std::vector<uint32_t> px8((size_t)W * H);
+            rt.toneMap(shown.data(), auto_exposure ? &exposure : nullptr, px8.data(), W, H, tone_params);
+            std::printf("{\"meter_ms\": %.4f, \"tonemap_ms\": %.4f, \"exposure\": %.9g}\n", auto_exposure ? rt.lastToneMapMs(true) : 0.0f,
+                        rt.lastToneMapMs(), auto_exposure ? exposure : tone_params.exposure);
+            if (!ppm.empty() && !write_ppm(ppm, px8, W, H)) return 1;
         }
         std::printf("{\"frames\": %u, \"seconds\": %.6f, \"frames_per_sec\": %.4f, \"mrays_per_sec\": %.2f}\n", frames,
                     dt, frames / dt, rays / dt / 1e6);

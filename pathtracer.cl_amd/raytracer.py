@@ -553,6 +553,80 @@ class RayTracer:
         self._check(self._lib.rt_last_variance_ms(self._h, *a), "rt_last_variance_ms")
         return ms.value
 
+    # ---- tone-mapped 8-bit display output with auto-exposure (pathtracer_rt.h) ----
+    @staticmethod
+    def _word_buffer(buf, need: int, what: str) -> int:
+        """_frame_buffer for a buffer of 32-bit words (uint32 or int32)."""
+        if isinstance(buf, np.ndarray):
+            if buf.dtype not in (np.uint32, np.int32) or not buf.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{what} must be a contiguous uint32 array")
+            n, dev = buf.size, 0
+        else:
+            if buf.dtype.__str__() not in ("torch.uint32", "torch.int32"):
+                raise TypeError(f"{what} must be uint32 or int32")
+            if not buf.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+            n, dev = buf.numel(), _abi.RT_OUT_DEVICE if getattr(buf, "is_cuda", False) else 0
+        if n < need:
+            raise ValueError(f"{what} holds {n} words, {need} needed")
+        return dev
+
+    def toneMapDefaults(self) -> dict:
+        prm = _abi.RtTonemapParams()
+        self._check(self._lib.rt_tonemap_defaults(ctypes.byref(prm)), "rt_tonemap_defaults")
+        return dict(curve=prm.curve, srgb=prm.srgb, dither=prm.dither, exposure=prm.exposure, white=prm.white)
+
+    def meterDefaults(self) -> dict:
+        prm = _abi.RtMeterParams()
+        self._check(self._lib.rt_meter_defaults(ctypes.byref(prm)), "rt_meter_defaults")
+        return dict(key=prm.key, lo=prm.lo, hi=prm.hi, e_min=prm.e_min, e_max=prm.e_max, rate=prm.rate)
+
+    def meterExposure(self, rgba, exposure, width: int, height: int, hist=None, stream=None, sync: bool = True,
+                      **params) -> None:
+        """Meter the RGBA32F frame `rgba`: `exposure` (one float32) is read as the previous exposure (not
+        positive: none) and written as the new one; `hist` (None, or 384 uint32 / int32 words) receives
+        the luminance histogram.  `params`: fields of rt_meter_params other than the library's defaults
+        (key, lo, hi, e_min, e_max, rate).  All numpy arrays or all torch CUDA tensors; the frame is
+        only read."""
+        px = int(width) * int(height)
+        flags = [self._frame_buffer(rgba, px * 4, "frame"), self._frame_buffer(exposure, 1, "exposure")]
+        if hist is not None:
+            flags.append(self._word_buffer(hist, _abi.RT_METER_BINS, "histogram"))
+        if len(set(flags)) != 1:
+            raise ValueError("meterExposure: the buffers must all be host arrays or all device tensors")
+        prm = _abi.RtMeterParams(**{**self.meterDefaults(), **{k: float(v) for k, v in params.items()}})
+        args = (self._h, _abi.ptr(rgba), _abi.ptr(exposure), _abi.ptr(hist), int(width), int(height), ctypes.byref(prm),
+                flags[0])
+        self._aux_call("rt_meter_exposure", args, stream, sync)
+
+    def toneMap(self, rgba, out_rgba8, width: int, height: int, exposure=None, stream=None, sync: bool = True,
+                **params) -> None:
+        """Tone-map the RGBA32F frame `rgba` into `out_rgba8` (W*H uint32 / int32 words: r | g << 8 |
+        b << 16 | 255 << 24) under `exposure`: a buffer of one float32 as meterExposure wrote it, or a
+        number, the fixed factor (None: the library's default, 1).  `params`: fields of rt_tonemap_params
+        other than the library's defaults (curve, srgb, dither, white).  All numpy arrays or all torch CUDA
+        tensors; the frame is only read."""
+        px = int(width) * int(height)
+        flags = [self._frame_buffer(rgba, px * 4, "frame"), self._word_buffer(out_rgba8, px, "destination 8-bit frame")]
+        d = {**self.toneMapDefaults(), **params}
+        if isinstance(exposure, (int, float, np.floating)):
+            d["exposure"], exposure = float(exposure), None
+        if exposure is not None:
+            flags.append(self._frame_buffer(exposure, 1, "exposure"))
+        if len(set(flags)) != 1:
+            raise ValueError("toneMap: the buffers must all be host arrays or all device tensors")
+        prm = _abi.RtTonemapParams(int(d["curve"]), int(d["srgb"]), int(d["dither"]), float(d["exposure"]), float(d["white"]))
+        args = (self._h, _abi.ptr(rgba), _abi.ptr(exposure), _abi.ptr(out_rgba8), int(width), int(height), ctypes.byref(prm),
+                flags[0])
+        self._aux_call("rt_tonemap", args, stream, sync)
+
+    def lastToneMapMs(self, meter: bool = False) -> float:
+        """Device time of the last tone-map kernel, or (meter=True) of the last meter, ms."""
+        ms = ctypes.c_float()
+        a, b = (ctypes.byref(ms), None) if meter else (None, ctypes.byref(ms))
+        self._check(self._lib.rt_last_tonemap_ms(self._h, a, b), "rt_last_tonemap_ms")
+        return ms.value
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
