@@ -70,6 +70,18 @@
  *                    again and the progression restarts.  The history and the moments are dropped, as
  *                    updateMesh drops them without the motion carry — unless setHistoryTrust is on, which
  *                    keeps them and lets the test shorten them where the shading has changed.
+ *   setSphereCarry(on, max_history)  (no counterpart in the reference) with setTemporal, in a view of a sphere
+ *                    kernel, carry the displayed frame (and setVarianceGuided's moments) across sceneChanged()
+ *                    (DESIGN.md §4.16): the view keeps the sphere list every frame was displayed with, and the
+ *                    first display after the change reprojects the history through the new features with
+ *                    every sphere pixel put back where its sphere stood (rt_warp_features_spheres), its length
+ *                    capped at max_history.  The caller's contract: sphere i before and after the change is
+ *                    the same object — a caller who reorders the list leaves the carry off for that change.
+ *                    The denoisers and setHistoryTrust read the unwarped features; with setHistoryTrust both
+ *                    apply: the warp puts the history on the sphere, the test shortens it where shadows and
+ *                    reflections changed.  In an RT_KERNEL_TRIS view (its spheres are lights only: no pixel
+ *                    carries a sphere id) and off (the default), sceneChanged() does what it did before: no
+ *                    call is made, nothing is allocated, no output bit changes.
  *   setToneMap(on, params, autoExposure, meter)  (no counterpart in the reference) the last display stage
  *                    (DESIGN.md §4.15): whatever the stages above chose to show is metered (with
  *                    autoExposure: the exposure is a float on the device that the meter reads and writes at
@@ -212,15 +224,37 @@ public:
         trustParams_ = params;
     }
     bool historyTrust() const { return trust_; }
+    /* (no counterpart in the reference) carry the displayed frame across sceneChanged() in a view of a
+       sphere kernel.  max_history caps the history length of that carry alone (with
+       setTemporal's own cap): reflections and refractions in a moved sphere lag, and the cap bounds for
+       how long.  Sphere i before and after a change must be the same object; a caller who reorders the
+       list leaves the carry off for that change.  Needs setTemporal; off (the default), sceneChanged()
+       does what it did before. */
+    void setSphereCarry(bool on, float max_history = 8.0f)
+    {
+        sphereCarry_ = on;
+        sphereMaxHistory_ = max_history;
+        if (!on) {
+            spheresPending_ = shownValid_ = false;
+            shownSpheres_.clear();
+        }
+    }
+    bool sphereCarry() const { return sphereCarry_; }
     /* The spheres have changed (the caller's addSphere / clearSpheres).  Without setHistoryTrust the
        history and the moments show the old lighting and are dropped; with it they are kept and judged.
-       Progression back to 0; returns restart()'s answer. */
+       With setSphereCarry (and setTemporal, a sphere kernel and a kept frame) they are kept too, and the
+       next display seeks every sphere pixel's history where its sphere stood when the kept frame was
+       displayed (mergeTemporal) — several changes between two displays keep that oldest list, which is
+       copied at displays only.  Progression back to 0; returns restart()'s answer. */
     bool sceneChanged()
     {
+        const bool carrySpheres =
+            sphereCarry_ && temporal_ && haveHist_ && shownValid_ && !realloc_ && kernel_ != RT_KERNEL_TRIS;
         featDirty_ = true;
-        if (!trust_) dropHistory();
+        if (carrySpheres) spheresPending_ = true;
+        else if (!trust_) dropHistory();
         const bool post = restart();
-        if (!trust_) carry_ = false;
+        if (!carrySpheres && !trust_) carry_ = false;
         return post;
     }
 
@@ -353,6 +387,10 @@ private:
            updateMesh after a display), and the current features warped into it */
         DeviceFloats posePrev, featWarp;
         uint32_t poseVerts = 0;
+        /* setSphereCarry: the spheres the kept frame was displayed with, uploaded for the warp (which
+           shares featWarp) */
+        DeviceFloats spherePrev;
+        size_t spherePrevCount = 0;
         DeviceFloats trustLen; /* setHistoryTrust: the lengths the carried history still deserves at this display */
         /* setVarianceGuided: the accumulation buffer before the frame, the view's moments, with
            setTemporal their history, the variance plane and (without setTemporal) the plane of history lengths */
@@ -368,6 +406,7 @@ private:
     {
         haveHist_ = false;
         posePending_ = false;
+        spheresPending_ = false;
         if (moments) momValid_ = false;
     }
     void allocate()
@@ -425,11 +464,29 @@ private:
                 curFeat = b.featWarp.p;
                 prm.max_history = std::fmin(temporalParams_.max_history, motionMaxHistory_);
             }
+            if (spheresPending_) { /* spheres have moved since: the taps are sought where each sphere stood */
+                const size_t n = shownSpheres_.size();
+                if (b.spherePrevCount != n) {
+                    b.spherePrev.drop();
+                    b.spherePrevCount = n;
+                }
+                if (n) {
+                    b.spherePrev.need(n * (sizeof(rt_sphere) / sizeof(float)), "sphere list");
+                    if (hipMemcpy(b.spherePrev.p, shownSpheres_.data(), n * sizeof(rt_sphere), hipMemcpyHostToDevice) != hipSuccess)
+                        throw std::runtime_error("ProgressiveViewHIP: sphere list upload failed");
+                }
+                b.featWarp.need(8 * px, "feature buffer");
+                rt_.warpFeaturesSpheres(curFeat, reinterpret_cast<const rt_sphere *>(b.spherePrev.p), (uint32_t)n, b.featWarp.p,
+                                        width_, height_, true);
+                curFeat = b.featWarp.p;
+                prm.max_history = std::fmin(prm.max_history, sphereMaxHistory_);
+            }
             for (int i = 0; i < nHist; ++i) /* the same lengths, features and cameras: the same taps and weights */
                 rt_.reproject(hist[i]->kept.rgba(), b.colour.kept.len(), histFeat, histCam_, curFeat, hist[i]->carried.rgba(),
                               hist[i]->carried.len(), width_, height_, prm, true);
         }
         posePending_ = false;
+        spheresPending_ = false;
         carry_ = false;
         /* the lengths the merges blend by: the carried ones, or with setHistoryTrust what this display's
            accumulation buffer leaves of the colour's (one plane for both) */
@@ -530,6 +587,10 @@ private:
             if (hipMemcpy(pbo8_.data(), b.tone8.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: 8-bit frame readback failed");
         }
+        if (sphereCarry_ && kernel_ != RT_KERNEL_TRIS) { /* the spheres this frame was displayed with */
+            shownSpheres_ = rt_.spheres();
+            shownValid_ = true;
+        }
         rendered_ = true;
     }
 
@@ -543,6 +604,10 @@ private:
     bool temporal_ = false, haveHist_ = false, carry_ = false;
     bool motionCarry_ = false, posePending_ = false;
     float motionMaxHistory_ = 8.0f;
+    /* setSphereCarry: the sphere list of the last traced display, whether it is one, whether a change is to be carried */
+    bool sphereCarry_ = false, shownValid_ = false, spheresPending_ = false;
+    float sphereMaxHistory_ = 8.0f;
+    std::vector<rt_sphere> shownSpheres_;
     bool trust_ = false;
     rt_trust_params trustParams_ = RayTracerHIP::trustDefaults();
     rt_reproject_params temporalParams_ = RayTracerHIP::reprojectDefaults();

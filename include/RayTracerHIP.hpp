@@ -334,6 +334,26 @@ public:
         return ms;
     }
 
+    /* ---- carrying the displayed frame across sphere moves (pathtracer_rt.h) ---- */
+    /* The sphere list as added (uploaded at the next render or display call, if it changed). */
+    const std::vector<rt_sphere> &spheres() const { return spheres_; }
+    /* cur_feat with every sphere pixel's hit point put back on sphere i of prev_spheres: out_feat (may be
+       cur_feat), reproject's cur_feat across a change of the sphere list that keeps its order. */
+    void warpFeaturesSpheres(const float *cur_feat, const rt_sphere *prev_spheres, uint32_t n_prev, float *out_feat,
+                             unsigned width, unsigned height, bool on_device = false)
+    {
+        flushScene();
+        check(rt_warp_features_spheres(ctx_, cur_feat, prev_spheres, n_prev, out_feat, width, height,
+                                       on_device ? RT_OUT_DEVICE : 0),
+              "warpFeaturesSpheres");
+    }
+    float lastSphereWarpMs() const
+    {
+        float ms = 0.0f;
+        check(rt_last_sphere_warp_ms(ctx_, &ms), "lastSphereWarpMs");
+        return ms;
+    }
+
     /* ---- variance-guided display filter (pathtracer_rt.h) ---- */
     static rt_denoise_var_params denoiseVarDefaults()
     {

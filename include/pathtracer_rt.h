@@ -475,6 +475,30 @@ int rt_warp_features_async(rt_ctx *ctx, const float *cur_feat, const float *prev
 /* Device time of the last warp kernel (HIP events of its own), ms; RT_ERR_STATE before a first run. */
 int rt_last_warp_ms(const rt_ctx *ctx, float *ms);
 
+/* ---- carrying the displayed frame across rt_set_spheres: the sphere twin of
+   rt_warp_features.  cur_feat: the features of the current view under the context's current spheres
+   (the last rt_set_spheres; rt_render_features with a sphere kernel).  out_feat: the same buffer with
+   every sphere pixel's hit point put back where that sphere stood in prev_spheres (n_prev records; sphere
+   i of both lists is the same object).  Per pixel with (N, id) of plane 1: a mesh pixel, the box, nothing
+   or any other id above RT_FEAT_SPHERE0 is copied bit for bit.  Sphere s = RT_FEAT_SPHERE0 - id: not
+   below both counts, "no surface" (P = N = 0, t = INFINITY, id RT_FEAT_NONE: rt_reproject gives it no
+   history); centre and radius of current and earlier sphere s equal in all four words' bits (the
+   material is not compared), copied bit for bit; otherwise P' = (C'.x + N.x r', C'.y + N.y r', C'.z +
+   N.z r') with (C', r') the earlier sphere, every product and sum one rounded float32 operation, and N, t
+   and id stay — or "no surface" when r' is not positive and finite or a component of P' is not finite.
+   Display only, under rt_warp_features' rules: no render state changed, flags takes RT_OUT_DEVICE only
+   and then every buffer incl. prev_spheres is a device pointer, the same stream ordering.  n_prev == 0
+   is legal (prev_spheres may then be NULL): every sphere pixel becomes "no surface".  out_feat ==
+   cur_feat is allowed (no other overlap).  RT_ERR_NO_SCENE without current spheres; RT_ERR_ARG for null
+   frame pointers, NULL prev_spheres with n_prev > 0, an empty or oversized frame, other flags, or
+   out_feat overlapping anything but exactly cur_feat. */
+int rt_warp_features_spheres(rt_ctx *ctx, const float *cur_feat, const rt_sphere *prev_spheres, uint32_t n_prev,
+                             float *out_feat, uint32_t width, uint32_t height, int flags);
+int rt_warp_features_spheres_async(rt_ctx *ctx, const float *cur_feat, const rt_sphere *prev_spheres, uint32_t n_prev,
+                                   float *out_feat, uint32_t width, uint32_t height, int flags, void *hip_stream);
+/* Device time of the last sphere warp kernel (HIP events of its own), ms; RT_ERR_STATE before a first run. */
+int rt_last_sphere_warp_ms(const rt_ctx *ctx, float *ms);
+
 /* ---- variance-guided display filter driven by temporal luminance moments.  The
    rules of the calls above hold: display only, no render state is changed, the accumulation buffer
    is only read, `flags` takes RT_OUT_DEVICE only, the same stream ordering, and arithmetic that a

@@ -280,6 +280,10 @@ SIGNATURES = {
     "rt_warp_features": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32]),
     "rt_warp_features_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_warp_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
+    # the features of moved spheres on the earlier spheres (csrc/rt_motion.hip)
+    "rt_warp_features_spheres": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32]),
+    "rt_warp_features_spheres_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32, _vp]),
+    "rt_last_sphere_warp_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
     # variance-guided display filter (csrc/rt_filter.hip)
     "rt_denoise_var_defaults": (_i32, [ctypes.POINTER(RtDenoiseVarParams)]),
     "rt_moments_accumulate": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32]),

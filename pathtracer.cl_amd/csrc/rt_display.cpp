@@ -1,7 +1,7 @@
 /*
  * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
  * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
- * §4.10), the trust of the carried history (rt_temporal.hip, §4.14), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
+ * §4.10), the trust of the carried history (rt_temporal.hip, §4.14), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13) and of moved spheres on the earlier ones (§4.16), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
  * (rt_filter.hip, §4.9 and §4.11), the meter and the tone map to 8 bits (rt_tonemap.hip, §4.15), with
  * their kernel times.  Every call runs through one driver
  * (AuxCall).
@@ -458,6 +458,54 @@ try {
     if (!c || !ms) return RT_ERR_ARG;
     if (!c->stage_time[RT_ST_WARP].have) return RT_ERR_STATE;
     return stage_ms(c, RT_ST_WARP, ms);
+} RT_CATCH(err_of(c))
+
+/* ---- the features of moved spheres on the earlier spheres ---- */
+
+int rt_warp_features_spheres_async(rt_ctx *c, const float *cur_feat, const rt_sphere *prev_spheres, uint32_t n_prev,
+                                   float *out_feat, uint32_t W, uint32_t H, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (c->spheres.empty() || !c->d_spheres) return fail(c, RT_ERR_NO_SCENE, "no spheres set");
+    if (!cur_feat || !out_feat) return fail(c, RT_ERR_ARG, "rt_warp_features_spheres: null feature buffer");
+    if (n_prev && !prev_spheres) return fail(c, RT_ERR_ARG, "rt_warp_features_spheres: null earlier spheres");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_warp_features_spheres: flags other than RT_OUT_DEVICE");
+    const size_t px = (size_t)W * H;
+    /* out_feat is cur_feat exactly, or apart from both inputs (addresses of one kind: all host or all device) */
+    const auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return x < y + nb && y < x + na;
+    };
+    const size_t feat_bytes = 8 * px * sizeof(float), prev_bytes = (size_t)n_prev * sizeof(rt_sphere);
+    if ((out_feat != cur_feat && overlap(out_feat, feat_bytes, cur_feat, feat_bytes)) ||
+        (n_prev && overlap(out_feat, feat_bytes, prev_spheres, prev_bytes)))
+        return fail(c, RT_ERR_ARG, "rt_warp_features_spheres: the output overlaps an input other than exactly cur_feat");
+    AuxCall x = {c, RT_ST_WARP_SPH};
+    if (const int r = x.open(stream, flags)) return r;
+    /* staged: the two feature planes, warped in place there, then the earlier spheres (20 words each) */
+    constexpr size_t kSphereFloats = sizeof(rt_sphere) / sizeof(float);
+    const float *prev = n_prev ? reinterpret_cast<const float *>(prev_spheres) : nullptr;
+    const Plane pl[] = {{cur_feat, out_feat, 0, 8 * px}, {prev, nullptr, 8 * px, kSphereFloats * n_prev}};
+    if (const int r = x.begin(pl, 2, 8 * px + kSphereFloats * n_prev)) return r;
+    const int e = rt_launch_warp_features_spheres(x.at(0, cur_feat), c->d_spheres, (uint32_t)c->spheres.size(),
+                                                  prev ? reinterpret_cast<const rt_sphere *>(x.at(1, prev)) : nullptr, n_prev,
+                                                  x.at(0, out_feat), W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "sphere feature warp kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_warp_features_spheres(rt_ctx *c, const float *cur_feat, const rt_sphere *prev_spheres, uint32_t n_prev, float *out_feat,
+                             uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_warp_features_spheres_async(c, cur_feat, prev_spheres, n_prev, out_feat, W, H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_sphere_warp_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->stage_time[RT_ST_WARP_SPH].have) return RT_ERR_STATE;
+    return stage_ms(c, RT_ST_WARP_SPH, ms);
 } RT_CATCH(err_of(c))
 
 /* ---- variance-guided display filter --------------------- */

@@ -455,6 +455,11 @@ int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const
    out_feat may be cur_feat. */
 int rt_launch_warp_features(const float *cur_feat, const int32_t *idx, const float *pose, const float *prev_verts,
                             uint32_t n_tris, uint32_t n_verts, float *out_feat, uint32_t W, uint32_t H, void *stream);
+/* The features of moved spheres on the earlier spheres of the same index: device
+   buffers; spheres / prev_spheres the current and the earlier list (prev_spheres may be null with
+   n_prev 0).  out_feat may be cur_feat. */
+int rt_launch_warp_features_spheres(const float *cur_feat, const rt_sphere *spheres, uint32_t n_cur, const rt_sphere *prev_spheres,
+                                    uint32_t n_prev, float *out_feat, uint32_t W, uint32_t H, void *stream);
 /* -- rt_filter.hip -- */
 /* The display filters: device buffers.  The
    moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in. */

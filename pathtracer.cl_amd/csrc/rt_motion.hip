@@ -1,15 +1,19 @@
 /*
- * rt_motion.hip — first-hit features of a moving mesh, rewritten into an earlier pose (gfx950).
+ * rt_motion.hip — first-hit features of a moving mesh or of moved spheres, rewritten into an earlier
+ * pose (gfx950).
  *
  *   k_warp_features   per pixel of the current view's feature buffer: a mesh pixel's hit point as
  *                     barycentrics of its triangle in the current pose, then position and normal of
  *                     that material point in an earlier pose of the same mesh (same indices).
  *                     rt_reproject, given the result as its cur_feat, carries the history that is
  *                     attached to the material, not to the place.
+ *   k_warp_features_sph   the sphere twin: a sphere pixel's hit point, which the features hold as the
+ *                     unit normal N = (P - C) / r, put back on the sphere of the same index in an
+ *                     earlier list of spheres: P' = C' + N r'.
  *
- * Nothing in the reference corresponds to this kernel; its arithmetic is pinned in DESIGN.md §4.13
- * under the model of include/rt_math.h (no contraction, IEEE division and square root), so that a
- * float32 restatement reproduces every bit.  It touches no render state, and writes nothing but
+ * Nothing in the reference corresponds to these kernels; their arithmetic is pinned in DESIGN.md §4.13
+ * and §4.16 under the model of include/rt_math.h (no contraction, IEEE division and square root), so
+ * that a float32 restatement reproduces every bit.  They touch no render state, and write nothing but
  * out_feat (which may be cur_feat: a lane reads its own pixel before it writes it).
  */
 #include <hip/hip_runtime.h>
@@ -81,6 +85,48 @@ __global__ __launch_bounds__(RT_BLOCK) void k_warp_features(WarpArgs a)
     a.out[(size_t)a.npx + p] = o1;
 }
 
+struct SphWarpArgs {
+    const float4 *cur;
+    float4 *out;
+    const rt_sphere *sph;  /* the current spheres */
+    const rt_sphere *prev; /* the earlier ones */
+    uint32_t npx, n_cur, n_prev;
+};
+
+/* One lane per pixel, row-major as k_features_sph.  No address is formed from the pixel's id before
+   the sphere index it names has been compared with both counts. */
+__global__ __launch_bounds__(RT_BLOCK) void k_warp_features_sph(SphWarpArgs a)
+{
+    const uint32_t p = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (p >= a.npx) return;
+    float4 o0 = a.cur[p], o1 = a.cur[(size_t)a.npx + p];
+    const int id = __float_as_int(o1.w);
+    if (id <= RT_FEAT_SPHERE0) { /* a sphere pixel; mesh, box, none and the unused ids are copied bit for bit */
+        const uint32_t s = (uint32_t)RT_FEAT_SPHERE0 - (uint32_t)id; /* modulo 2^32: INT32_MIN gives 2^31 - 16 */
+        bool ok = false;
+        if (s < a.n_cur && s < a.n_prev) {
+            const rt_sphere &c = a.sph[s], &q = a.prev[s];
+            const float r = q.radius;
+            if (__float_as_uint(c.center.x) == __float_as_uint(q.center.x) && __float_as_uint(c.center.y) == __float_as_uint(q.center.y) &&
+                __float_as_uint(c.center.z) == __float_as_uint(q.center.z) && __float_as_uint(c.radius) == __float_as_uint(r)) {
+                ok = true; /* it stands where it stood: the input's bits */
+            } else {
+                const V3 P = v3(q.center.x + o1.x * r, q.center.y + o1.y * r, q.center.z + o1.z * r);
+                if (r > 0.0f && r < kInf && finite3(P)) { /* (r > 0 is false for a NaN) */
+                    ok = true;
+                    o0 = make_float4(P.x, P.y, P.z, o0.w);
+                }
+            }
+        }
+        if (!ok) { /* no surface: rt_reproject gives it no history */
+            o0 = make_float4(0.0f, 0.0f, 0.0f, kInf);
+            o1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(RT_FEAT_NONE));
+        }
+    }
+    a.out[p] = o0;
+    a.out[(size_t)a.npx + p] = o1;
+}
+
 } // namespace
 
 int rt_launch_warp_features(const float *cur_feat, const int32_t *idx, const float *pose, const float *prev_verts,
@@ -96,5 +142,20 @@ int rt_launch_warp_features(const float *cur_feat, const int32_t *idx, const flo
     a.n_tris = n_tris;
     a.n_verts = n_verts;
     hipLaunchKernelGGL(k_warp_features, dim3((a.npx + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int rt_launch_warp_features_spheres(const float *cur_feat, const rt_sphere *spheres, uint32_t n_cur, const rt_sphere *prev_spheres,
+                                    uint32_t n_prev, float *out_feat, uint32_t W, uint32_t H, void *stream)
+{
+    SphWarpArgs a;
+    a.cur = reinterpret_cast<const float4 *>(cur_feat);
+    a.out = reinterpret_cast<float4 *>(out_feat);
+    a.sph = spheres;
+    a.prev = prev_spheres;
+    a.npx = W * H; /* < 2^28 (the host's frame check) */
+    a.n_cur = n_cur;
+    a.n_prev = n_prev;
+    hipLaunchKernelGGL(k_warp_features_sph, dim3((a.npx + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -35,6 +35,11 @@
  *              (ProgressiveViewHIP::setHistoryTrust, tolerance TOL standard deviations, default rt_trust_defaults';
  *              "inf" trusts everything); the event e:DX:DY:DZ moves every emissive sphere by (DX, DY, DZ) and
  *              calls ProgressiveViewHIP::sceneChanged())
+ *             [--sphere-carry [MAXHIST]]   (with --temporal: the view carries its displayed frame across the
+ *              o events (ProgressiveViewHIP::setSphereCarry, that carry's history capped at MAXHIST frames,
+ *              default 8); the event o:I:DX:DY:DZ[:DR] adds (DX, DY, DZ) to the centre of sphere I of the scene
+ *              and DR to its radius (cumulative, like e), rebuilds the scene in the same order and calls
+ *              ProgressiveViewHIP::sceneChanged())
  *             [--tonemap [clamp|reinhard|aces]]   (the tone-mapped 8-bit display output, default aces
  *              (rt_tonemap; with --events ProgressiveViewHIP::setToneMap: the float frames of --frames-out stay what
  *              they are without it) [--exposure auto|VALUE] (the histogram meter, the default, or a fixed factor)
@@ -53,6 +58,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <fstream>
 #include <thread>
@@ -79,39 +85,54 @@ rt_sphere init_sphere()
     return s;
 }
 
+constexpr unsigned kSceneSpheres = 6; /* of add_scene */
+/* the o events so far, per sphere: what is added to its centre and to its radius */
+using SphereOffsets = std::array<std::array<float, 4>, kSceneSpheres>;
+
 /* clrt/main.cpp:44-110 (ply = clrt/plymain.cpp:45-111) */
-void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0.0f})
+void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}, const SphereOffsets *moved = nullptr)
 {
+    /* the scene's spheres in order, each moved by its o events (an untouched sphere keeps its bits) */
+    unsigned n = 0;
+    const auto add = [&](rt_sphere s) {
+        const std::array<float, 4> o = moved ? (*moved)[n] : std::array<float, 4>{};
+        if (o[0] != 0.0f || o[1] != 0.0f || o[2] != 0.0f || o[3] != 0.0f) {
+            s.center = {s.center.x + o[0], s.center.y + o[1], s.center.z + o[2]};
+            s.radius += o[3];
+        }
+        ++n;
+        rt.addSphere(s);
+    };
     rt_sphere s = init_sphere();
     s.center = {-2.0f, -4.0f, -2.0f};
     s.mat.kd = 1.0f;
     s.mat.diffuse = {0.0f, 0.7f, 0.7f};
-    rt.addSphere(s);
+    add(s);
     s = init_sphere();
     s.center = {2.0f, -3.0f, 2.0f};
     s.mat.ks = 0.2f;
     s.mat.kt = 0.8f;
     s.mat.extinction = ply ? rt_vec3{0.95f, 0.85f, 0.90f} : rt_vec3{0.99f, 0.95f, 0.95f};
     s.mat.ior = 1.1f;
-    rt.addSphere(s);
+    add(s);
     s = init_sphere();
     s.center = {0.0f, -4.0f, 0.0f};
     s.mat.ks = 1.0f;
-    rt.addSphere(s);
+    add(s);
     s = init_sphere();
     s.center = {2.0f, -4.0f, -2.0f};
     s.mat.kd = 0.2f;
     s.mat.ks = 0.8f;
     s.mat.diffuse = {0.7f, 0.7f, 0.0f};
     s.mat.specExp = 100.0f;
-    rt.addSphere(s);
+    add(s);
     s = init_sphere();
     s.center = {-2.0f, -4.0f, 2.0f};
     s.mat.kd = 0.6f;
     s.mat.ks = 0.4f;
     s.mat.diffuse = {0.7f, 0.0f, 0.8f};
     s.mat.specExp = 1000.0f;
-    rt.addSphere(s);
+    add(s);
     s = init_sphere();
     s.center = ply ? rt_vec3{0.0f, 4.0f, 2.0f} : rt_vec3{2.2f, 1.0f, 2.0f};
     s.center = {s.center.x + light_offset.x, s.center.y + light_offset.y, s.center.z + light_offset.z}; /* (the e event) */
@@ -119,14 +140,14 @@ void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0
     s.mat.emission_power = 1.0f;
     const float e = ply ? 1.1f : 1.8f;
     s.mat.emission = {e, e, e};
-    rt.addSphere(s);
+    add(s);
 }
 
 int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
-                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--denoised f] [--denoised-pfm f] [--features-out f] "
+                         "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--sphere-carry [MAXHIST]] (--events o:I:DX:DY:DZ[:DR] moves sphere I) [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
@@ -189,7 +210,8 @@ bool write_ppm(const std::string &path, const std::vector<uint32_t> &px, unsigne
 int main(int argc, char **argv)
 {
     std::string scene = "main", raw, pfm, ply_path, events, comm_id, frames_out, den_raw, den_pfm, feat_out, raw_frames_out, poses_path;
-    bool denoise = false, temporal = false, var_guided = false, motion_carry = false, trust = false;
+    bool denoise = false, temporal = false, var_guided = false, motion_carry = false, trust = false, sphere_carry = false;
+    float sphere_max_history = 8.0f;
     std::string ppm, frames8_out, exposure_log;
     bool tonemap = false, auto_exposure = true;
     rt_tonemap_params tone_params = RayTracerHIP::toneMapDefaults();
@@ -239,6 +261,11 @@ int main(int argc, char **argv)
         if (a == "--motion-carry") { /* an optional history cap follows */
             motion_carry = true;
             if ((v = optional_number(argc, argv, i))) motion_max_history = (float)std::atof(v);
+            continue;
+        }
+        if (a == "--sphere-carry") { /* an optional history cap follows */
+            sphere_carry = true;
+            if ((v = optional_number(argc, argv, i))) sphere_max_history = (float)std::atof(v);
             continue;
         }
         if (a == "--history-trust") { /* an optional tolerance follows ("inf": everything is trusted) */
@@ -295,6 +322,22 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --motion-carry needs --temporal (without it there is nothing to carry)\n");
         return 2;
     }
+    if (sphere_carry && !temporal) {
+        std::fprintf(stderr, "rt_render: --sphere-carry needs --temporal (without it there is nothing to carry)\n");
+        return 2;
+    }
+    for (size_t pos = 0; pos <= events.size();) { /* the o events name spheres of the scene */
+        const size_t end = std::min(events.find(',', pos), events.size());
+        const std::string ev = events.substr(pos, end - pos);
+        pos = end + 1;
+        unsigned k = 0;
+        if (ev.empty() || ev[0] != 'o') continue;
+        if (std::sscanf(ev.c_str() + 1, ":%u", &k) != 1 || ev[2] == '-') return usage();
+        if (k >= kSceneSpheres) {
+            std::fprintf(stderr, "rt_render: event %s: the scene holds no sphere %u (it has %u)\n", ev.c_str(), k, kSceneSpheres);
+            return 2;
+        }
+    }
     if (trust && !temporal) {
         std::fprintf(stderr, "rt_render: --history-trust needs --temporal (without it there is no history to judge)\n");
         return 2;
@@ -345,8 +388,10 @@ int main(int argc, char **argv)
             if (var_guided) view.setVarianceGuided(true, var_params);
             if (motion_carry) view.setMotionCarry(true, motion_max_history);
             if (trust) view.setHistoryTrust(true, trust_params);
+            if (sphere_carry) view.setSphereCarry(true, sphere_max_history);
             if (tonemap) view.setToneMap(true, tone_params, auto_exposure, meter_params);
             rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
+            SphereOffsets sphere_offsets{};            /* the o events so far */
             std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
             if (!poses_path.empty()) {
                 std::ifstream pf(poses_path, std::ios::binary | std::ios::ate);
@@ -406,7 +451,15 @@ int main(int argc, char **argv)
                     if (std::sscanf(ev.c_str() + 1, ":%f:%f:%f", &dx, &dy, &dz) != 3) return usage();
                     light_offset = {light_offset.x + dx, light_offset.y + dy, light_offset.z + dz};
                     rt.clearSpheres();
-                    add_scene(rt, ply, light_offset);
+                    add_scene(rt, ply, light_offset, &sphere_offsets);
+                    post = view.sceneChanged();
+                } else if (ev[0] == 'o') { /* (its index was checked with the arguments) */
+                    unsigned k = 0;
+                    float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (std::sscanf(ev.c_str() + 1, ":%u:%f:%f:%f:%f", &k, &d[0], &d[1], &d[2], &d[3]) < 4) return usage();
+                    for (int j = 0; j < 4; ++j) sphere_offsets[k][j] += d[j];
+                    rt.clearSpheres();
+                    add_scene(rt, ply, light_offset, &sphere_offsets);
                     post = view.sceneChanged();
                 } else if (ev[0] == 'p') {
                     unsigned k = 0;

@@ -476,6 +476,40 @@ class RayTracer:
         self._check(self._lib.rt_last_warp_ms(self._h, ctypes.byref(ms)), "rt_last_warp_ms")
         return ms.value
 
+    # ---- carrying the displayed frame across sphere moves (pathtracer_rt.h) ----
+    def warpFeaturesSpheres(self, cur_feat, prev_spheres, out_feat, width: int, height: int, stream=None,
+                            sync: bool = True) -> None:
+        """Put every sphere pixel of `cur_feat` (renderFeatures with a sphere kernel under the current
+        spheres) back where its sphere stood in `prev_spheres` (a SPHERE_DTYPE array, or a CUDA byte
+        tensor of one; sphere i of both lists is the same object; it may be empty): `out_feat` (may be
+        `cur_feat`) is reproject's `cur_feat` across a change of the spheres.  All numpy arrays or all
+        torch CUDA tensors."""
+        self._sync_scene()
+        px = int(width) * int(height)
+        size = _abi.SPHERE_DTYPE.itemsize
+        if isinstance(prev_spheres, np.ndarray):
+            prev_spheres = np.ascontiguousarray(prev_spheres, _abi.SPHERE_DTYPE).reshape(-1)
+            n_prev, f_prev = prev_spheres.size, 0
+        else:
+            if prev_spheres.dtype.__str__() != "torch.uint8" or not prev_spheres.is_contiguous():
+                raise TypeError("earlier spheres must be a SPHERE_DTYPE array or a contiguous uint8 tensor of one")
+            if prev_spheres.numel() % size:
+                raise ValueError(f"earlier spheres hold {prev_spheres.numel()} bytes, no multiple of {size}")
+            n_prev, f_prev = prev_spheres.numel() // size, _abi.RT_OUT_DEVICE if prev_spheres.is_cuda else 0
+        flags = [self._frame_buffer(cur_feat, px * 8, "feature buffer"), f_prev,
+                 self._frame_buffer(out_feat, px * 8, "destination feature buffer")]
+        if len(set(flags)) != 1:
+            raise ValueError("warpFeaturesSpheres: the buffers must all be host arrays or all device tensors")
+        args = (self._h, _abi.ptr(cur_feat), _abi.ptr(prev_spheres) if n_prev else None, n_prev, _abi.ptr(out_feat),
+                int(width), int(height), flags[0])
+        self._aux_call("rt_warp_features_spheres", args, stream, sync)
+
+    def lastSphereWarpMs(self) -> float:
+        """Device time of the last warpFeaturesSpheres kernel, ms."""
+        ms = ctypes.c_float()
+        self._check(self._lib.rt_last_sphere_warp_ms(self._h, ctypes.byref(ms)), "rt_last_sphere_warp_ms")
+        return ms.value
+
     # ---- variance-guided display filter (pathtracer_rt.h, DESIGN.md §4.11) ----
     def denoiseVarDefaults(self) -> dict:
         prm = _abi.RtDenoiseVarParams()
