@@ -8,8 +8,12 @@
  *   batch_take, mq_take   the pixel queues' takes (one head, RT_QHEADS heads), kBatch
  *   box_items             the item count of an RT_SPLIT_BOX launch
  *   wave_clock, wave_sum, flush_counters   the device counters
- *   camera_dir, global_row                 a pixel's camera ray and frame row
- *   list_pack, RT_LPACK_* a pixel's candidate list in one word
+ *   pixel_stats_rec       a pixel's record of the RT_PIXEL_STATS diagnostics
+ *   camera_dir, global_row, camera_ray     a pixel's camera ray and frame row, a sample's ray
+ *   tile_pixel            a queue item's tile and in-tile index to its pixel
+ *   seed_slot, load_seed, store_seed       a pixel's frame seeds
+ *   pixel_mean, write_pixel                a finished pixel: the mean, the progressive mix, the store
+ *   list_pack, RT_LPACK_*, list_range      a pixel's candidate list in one word, and back
  *   mwc_jump              frand's generators advanced by k draws
  *
  * Only force-inlined functions and constants that two of those files use belong here; everything
@@ -201,6 +205,12 @@ __device__ __forceinline__ void flush_counters(unsigned long long *dst, const un
         }
 }
 
+/* pixel (x, yl)'s 8-word record of the RT_PIXEL_STATS diagnostics */
+__device__ __forceinline__ uint32_t *pixel_stats_rec(const RtTriLaunch &a, uint32_t x, uint32_t yl)
+{
+    return a.pixel_stats + 8 * ((size_t)yl * a.W + x);
+}
+
 /* raytracer.cl:81-85: normalize(view + right*a + up*b), float4 lanes incl. w,
    normalize pinned as v / sqrt(dot(v, v)). */
 __device__ __forceinline__ V3 camera_dir(const rt_camera &cam, float a, float b)
@@ -223,6 +233,69 @@ __device__ __forceinline__ uint32_t global_row(const L &a, uint32_t yl)
     return ((yl / a.stripe) * a.n_ranks + a.rank) * a.stripe + (yl % a.stripe);
 }
 
+/* The camera ray of sample (sx, sy) of the pixel in column x of frame row y (global_row)
+   (raytracer.cl:216-224: sx outer, sy inner, the x draw before the y draw); hw, hh: half the frame's
+   width and height */
+template <class L>
+__device__ __forceinline__ void camera_ray(const L &a, Seed &seed, uint32_t x, uint32_t y, uint32_t sx, uint32_t sy,
+                                           float hw, float hh, V3 &o, V3 &d)
+{
+    const float fa = (float)x + strat_rand(seed, (int)sx, (int)a.sample_rate);
+    const float fb = (float)y + strat_rand(seed, (int)sy, (int)a.sample_rate);
+    o = v3(a.cam.position.x, a.cam.position.y, a.cam.position.z);
+    d = camera_dir(a.cam, fa - hw, fb - hh);
+}
+
+/* Pixel `in` (row-major) of 8 x 8 tile `tile` (position `tile` of the queue's order, when there is
+   one) of a frame tiles_x tiles wide; false outside the frame */
+template <class L>
+__device__ __forceinline__ bool tile_pixel(const L &a, const uint32_t *order, uint32_t tile, uint32_t in,
+                                           uint32_t tiles_x, uint32_t &x, uint32_t &yl)
+{
+    if (order) tile = order[tile];
+    x = (tile % tiles_x) * 8u + (in & 7u);
+    yl = (tile / tiles_x) * 8u + (in >> 3);
+    return x < a.W && yl < a.Hl;
+}
+
+/* A pixel's frame seeds: words `slot` and plane + `slot` of a.seeds (raytracer.cl:207-209, :241-242:
+   the unshifted slot of its frame row) */
+template <class L>
+__device__ __forceinline__ uint32_t seed_slot(const L &a, uint32_t x, uint32_t yl)
+{
+    return global_row(a, yl) * a.Wpad + x;
+}
+template <class L>
+__device__ __forceinline__ Seed load_seed(const L &a, uint32_t slot)
+{
+    const Seed s = {a.seeds[slot], a.seeds[a.Wpad * a.Hpad + slot]};
+    return s;
+}
+template <class L>
+__device__ __forceinline__ void store_seed(const L &a, uint32_t slot, uint32_t sx, uint32_t sy)
+{
+    a.seeds[slot] = sx;
+    a.seeds[a.Wpad * a.Hpad + slot] = sy;
+}
+
+/* A finished pixel (raytracer.cl:234-242): the mean of its n samples' sum (0 / 0 without samples),
+   then mixed into the frame's pixel by t = 1 / progressive when `mix` (progressive > 0), and stored */
+__device__ __forceinline__ float4 pixel_mean(float sx, float sy, float sz, float n)
+{
+    return make_float4(sx / n, sy / n, sz / n, 0.0f / n);
+}
+__device__ __forceinline__ void write_pixel(float4 *dst, float4 p, bool mix, float t)
+{
+    if (mix) {
+        const float4 old = *dst;
+        p.x = old.x + (p.x - old.x) * t;
+        p.y = old.y + (p.y - old.y) * t;
+        p.z = old.z + (p.z - old.z) * t;
+        p.w = old.w + (p.w - old.w) * t;
+    }
+    *dst = p;
+}
+
 /* A pixel's camera-ray candidate list (k_pixel_lists) packed in one word, read when the lane takes
    the pixel instead of before every sample's camera query (one dependent load less per sample):
    (first slot / 8) << RT_LIST_BITS | (count - 1) — lists start on 8-record multiples and slots stay
@@ -237,6 +310,15 @@ __device__ __forceinline__ uint32_t list_pack(const RtTriLaunch &a, uint32_t x, 
     if (code == RT_LIST_EMPTY) return RT_LPACK_EMPTY;
     const uint32_t first = block + ((code >> RT_LIST_BITS) << 3);
     return ((first >> 3) << RT_LIST_BITS) | (code & (RT_LIST_MAX - 1u));
+}
+/* ... and back: the list's record count and first slot (of a word below RT_LPACK_EMPTY) */
+struct ListRange {
+    uint32_t count, first;
+};
+__device__ __forceinline__ ListRange list_range(uint32_t lpack)
+{
+    const ListRange r = {(lpack & (RT_LIST_MAX - 1u)) + 1u, (lpack >> RT_LIST_BITS) << 3};
+    return r;
 }
 
 /* One MWC generator of frand (rng.h:9-47: x = A (x & 0xffff) + (x >> 16)) advanced by k draws.

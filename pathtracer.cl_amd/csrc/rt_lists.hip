@@ -265,9 +265,9 @@ __global__ __launch_bounds__(RT_BLOCK) void k_pixel_lists(RtTriLaunch a, const f
     /* one wave per 8 x 8 pixel tile: neighbouring frusta walk the same nodes */
     __shared__ int s_fstack[kFrustumStack * RT_BLOCK];
     const uint32_t item = blockIdx.x * RT_BLOCK + threadIdx.x, tiles_x = (a.W + 7u) / 8u;
-    const uint32_t tile = item >> 6, in = item & 63u;
-    const uint32_t x = (tile % tiles_x) * 8u + (in & 7u), yl = (tile / tiles_x) * 8u + (in >> 3);
-    const bool valid = x < a.W && yl < a.Hl;
+    const uint32_t tile = item >> 6;
+    uint32_t x, yl;
+    const bool valid = tile_pixel(a, nullptr, tile, item & 63u, tiles_x, x, yl);
     const uint32_t p = yl * a.W + x;
     const float4 *__restrict__ tris = reinterpret_cast<const float4 *>(a.tris);
     int slot[RT_LIST_MAX];

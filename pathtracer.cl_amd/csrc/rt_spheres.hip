@@ -140,10 +140,9 @@ __global__ __launch_bounds__(RT_SPH_TILE * RT_SPH_TILE) void k_spheres(RtSphLaun
     unsigned long long n_closest = 0, n_shadow = 0, n_skipped = 0;
     if (x < a.W && yl < a.Hl) {
         const uint32_t y = global_row(a, yl);
-        const uint32_t plane = a.Wpad * a.Hpad;
         /* get_seed (raytracer.cl:20-24): rows shifted by `progressive`; raytrace_ss unshifted */
         const uint32_t slot = SS ? (y * a.Wpad + x) : (((y + a.progressive) % a.Hpad) * a.Wpad + x);
-        Seed seed = {a.seeds[slot], a.seeds[plane + slot]};
+        Seed seed = load_seed(a, slot);
         const float hw = ((float)a.W) / 2.0f, hh = ((float)a.H) / 2.0f;
         float4 pc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (SS) {
@@ -163,11 +162,8 @@ __global__ __launch_bounds__(RT_SPH_TILE * RT_SPH_TILE) void k_spheres(RtSphLaun
             const uint32_t sr = a.sample_rate;
             for (uint32_t sx = 0; sx < sr; ++sx) {
                 for (uint32_t sy = 0; sy < sr; ++sy) {
-                    const float fa = (float)x + strat_rand(seed, (int)sx, (int)sr);
-                    const float fb = (float)y + strat_rand(seed, (int)sy, (int)sr);
                     PathRay r;
-                    r.o = v3(a.cam.position.x, a.cam.position.y, a.cam.position.z);
-                    r.d = camera_dir(a.cam, fa - hw, fb - hh);
+                    camera_ray(a, seed, x, y, sx, sy, hw, hh, r.o, r.d);
                     r.tmin = RT_SMALL_F;
                     r.tmax = kInf;
                     r.prop = v3(1.0f, 1.0f, 1.0f);
@@ -179,24 +175,11 @@ __global__ __launch_bounds__(RT_SPH_TILE * RT_SPH_TILE) void k_spheres(RtSphLaun
                     pc.z += c.z;
                 }
             }
-            const float n = (float)(sr * sr);
-            pc.x /= n;
-            pc.y /= n;
-            pc.z /= n;
-            pc.w /= n;
+            pc = pixel_mean(pc.x, pc.y, pc.z, (float)(sr * sr));
         }
-        float4 *dst = reinterpret_cast<float4 *>(a.out) + ((size_t)yl * a.W + x);
-        if (a.progressive > 0) {
-            const float4 old = *dst;
-            const float t = 1.0f / (float)a.progressive;
-            pc.x = old.x + (pc.x - old.x) * t;
-            pc.y = old.y + (pc.y - old.y) * t;
-            pc.z = old.z + (pc.z - old.z) * t;
-            pc.w = old.w + (pc.w - old.w) * t;
-        }
-        *dst = pc;
-        a.seeds[slot] = seed.x;
-        a.seeds[plane + slot] = seed.y;
+        write_pixel(reinterpret_cast<float4 *>(a.out) + ((size_t)yl * a.W + x), pc, a.progressive > 0,
+                    1.0f / (float)a.progressive);
+        store_seed(a, slot, seed.x, seed.y);
     }
     unsigned long long cnt[RT_N_COUNTERS] = {};
     cnt[0] = n_closest;

@@ -247,6 +247,61 @@ __device__ __forceinline__ bool lane_root(uint4 r0, uint4 r1, uint4 r2, uint4 r3
     return nh > 0;
 }
 
+/* What both seed passes replay of a finished segment (rtcommon.h:411-466): the lights' skipped
+   draws, 2 per light, and off the box at hp (normal hn) the cosine-hemisphere bounce, drawn even at
+   the last depth */
+__device__ __forceinline__ void light_draws(Seed &seed, uint32_t nl)
+{
+    for (uint32_t l = 0; l < nl; ++l) {
+        (void)frand(seed);
+        (void)frand(seed);
+    }
+}
+__device__ __forceinline__ void box_bounce(Seed &seed, uint32_t nl, V3 hp, V3 hn, V3 &qo, V3 &qd)
+{
+    light_draws(seed, nl);
+    const float r1 = frand(seed);
+    const float r2 = frand(seed);
+    const float ct = rt_sqrtf(1.0f - r1);
+    const float st = rt_sqrtf(1.0f - ct * ct);
+    const float phi = RT_M_2PI_F * r2;
+    float sphi, cphi;
+    rt_sincosf(phi, &sphi, &cphi);
+    qd = shading_to_world(v3(cphi * st, sphi * st, ct), hn);
+    qo = hp;
+}
+
+/* A seed pass's end of a sample, by the chain's writer lane: the sample's mesh-hit depth (0xff: only
+   the box) of the chain's seeds at pslot ... */
+__device__ __forceinline__ void seed_sample_end(const RtTriLaunch &a, uint32_t pslot, uint32_t sample, bool mesh_hit,
+                                                uint32_t depth)
+{
+    if (a.split_hit_depth)
+        a.split_hit_depth[(size_t)pslot * (a.sample_rate * a.sample_rate) + sample] =
+            mesh_hit ? (uint8_t)depth : (uint8_t)0xffu;
+}
+/* ... and before the next sample the seed a chunk of split_fine samples starts from, or after the
+   last the pixel's final seed and (true returned) its record of the RT_PIXEL_STATS diagnostics:
+   its clocks, its steps, its camera rays that met the box, and `kind` */
+__device__ __forceinline__ bool seed_sample_next(const RtTriLaunch &a, uint32_t pslot, uint32_t x, uint32_t yl,
+                                                 uint32_t sample, Seed seed, uint32_t st_t0, uint32_t st_steps,
+                                                 uint32_t st_box, uint32_t kind)
+{
+    const uint32_t spp = a.sample_rate * a.sample_rate;
+    if (sample == spp || sample % a.split_fine == 0u) {
+        const uint32_t c = sample == spp ? a.split_nseed - 1u : sample / a.split_fine;
+        reinterpret_cast<uint2 *>(a.split_seed)[(size_t)pslot * a.split_nseed + c] = make_uint2(seed.x, seed.y);
+    }
+    if (sample != spp || !a.pixel_stats) return false;
+    uint32_t *ps = pixel_stats_rec(a, x, yl);
+    ps[0] = st_t0;
+    ps[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+    ps[2] = st_steps;
+    ps[3] = st_box;
+    ps[4] = kind;
+    return true;
+}
+
 template <int G> /* lanes per query: 1 (trav_step_q) or 4 (coop_round) */
 __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
 {
@@ -263,8 +318,7 @@ __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
     /* the root node (coop_root): a uniform address, so scalar loads */
     const uint4 *__restrict__ rootp = reinterpret_cast<const uint4 *>(a.nodes);
     const uint4 rq0 = rootp[0], rq1 = rootp[1], rq2 = rootp[2], rq3 = rootp[3];
-    const uint32_t spp = a.sample_rate * a.sample_rate, fine = a.split_fine, nseed = a.split_nseed;
-    const uint32_t plane = a.Wpad * a.Hpad;
+    const uint32_t spp = a.sample_rate * a.sample_rate;
     const uint32_t tiles_x = (a.W + 7u) >> 3, tiles_y = (a.Hl + 7u) >> 3;
     const uint32_t n_items = a.split_which == RT_SPLIT_BOX ? box_items(a)
                                                            : tiles_x * tiles_y * 64u;
@@ -279,13 +333,7 @@ __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
     uint32_t bnext = 0, bend = 0; /* the wave's batch of queue items (batch_take) */
     Seed seed = {0u, 0u};
     V3 qo = v3(0.0f, 0.0f, 0.0f), qd = v3(0.0f, 0.0f, 1.0f);
-    TravState ts;
-    ts.node = 0;
-    ts.best = -1;
-    ts.best_orig = -1;
-    ts.best_t = kInf;
-    ts.inv = qo;
-    ts.oi = qo;
+    TravState ts = trav_idle();
     CoopQuery cq;
     coop_begin(cq, qo, qd, kInf);
     uint32_t st_steps = 0, st_box = 0, st_t0 = 0; /* diagnostics (RT_PIXEL_STATS): per pixel */
@@ -315,19 +363,12 @@ __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
                         pslot = a.split_seed_slot ? item : p;
                         take = true;
                     } else {
-                        uint32_t tile = item >> 6;
-                        const uint32_t in = item & 63u;
-                        if (a.tile_order) tile = a.tile_order[tile];
-                        x = (tile % tiles_x) * 8u + (in & 7u);
-                        yl = (tile / tiles_x) * 8u + (in >> 3);
-                        take = x < a.W && yl < a.Hl;
+                        take = tile_pixel(a, a.tile_order, item >> 6, item & 63u, tiles_x, x, yl);
                         if (take && a.split_which == RT_SPLIT_MESH) take = a.pixel_class[(size_t)yl * a.W + x] == -1;
                         pslot = yl * a.W + x;
                     }
                     if (take) {
-                        const uint32_t slot = global_row(a, yl) * a.Wpad + x;
-                        seed.x = a.seeds[slot];
-                        seed.y = a.seeds[plane + slot];
+                        seed = load_seed(a, seed_slot(a, x, yl));
                         lpack = list_pack(a, x, yl, tiles_x);
                         sample = 0;
                         have = true;
@@ -359,61 +400,41 @@ __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
             /* a new sample: the chunk's first seed, then the camera ray and its query */
             if (next) {
                 next = false;
-                if ((sample == spp || sample % fine == 0u) && lane == gbase) {
-                    const uint32_t c = sample == spp ? nseed - 1u : sample / fine;
-                    reinterpret_cast<uint2 *>(a.split_seed)[(size_t)pslot * nseed + c] = make_uint2(seed.x, seed.y);
+                if (lane == gbase &&
+                    seed_sample_next(a, pslot, x, yl, sample, seed, st_t0, st_steps, st_box,
+                                     1u + (uint32_t)a.split_which | (RT_SEED_STATS ? st_it << 4 : 0u)) &&
+                    RT_SEED_STATS) {
+                    uint32_t *ps = pixel_stats_rec(a, x, yl);
+                    ps[7] = st_q << 16 | (st_imm & 0xffffu);
+                    ps[5] = (uint32_t)(st_adv >> 6);
+                    ps[6] = (uint32_t)(st_rnd >> 6);
                 }
                 if (sample == spp) {
                     have = false;
-                    if (a.pixel_stats && lane == gbase) {
-                        uint32_t *ps = a.pixel_stats + 8 * ((size_t)yl * a.W + x);
-                        ps[0] = st_t0;
-                        ps[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-                        ps[2] = st_steps;
-                        ps[3] = st_box;
-                        ps[4] = 1u + (uint32_t)a.split_which | (RT_SEED_STATS ? st_it << 4 : 0u);
-                        if (RT_SEED_STATS) {
-                            ps[7] = st_q << 16 | (st_imm & 0xffffu);
-                            ps[5] = (uint32_t)(st_adv >> 6);
-                            ps[6] = (uint32_t)(st_rnd >> 6);
-                        }
-                    }
                 } else {
-                    const uint32_t sx = sample / a.sample_rate, sy = sample % a.sample_rate;
-                    const float fa = (float)x + strat_rand(seed, (int)sx, (int)a.sample_rate);
-                    const uint32_t y = global_row(a, yl);
-                    const float fb = (float)y + strat_rand(seed, (int)sy, (int)a.sample_rate);
-                    qo = v3(a.cam.position.x, a.cam.position.y, a.cam.position.z);
-                    qd = camera_dir(a.cam, fa - hw, fb - hh);
+                    camera_ray(a, seed, x, global_row(a, yl), sample / a.sample_rate, sample % a.sample_rate, hw, hh,
+                               qo, qd);
                     depth = 0;
                     if (COOP) coop_begin(cq, qo, qd, kInf);
                     else trav_begin(ts, stk, qo, qd, kInf);
                     q_steps = 0;
                     running = true;
                     { /* the pixel's candidate list, as k_tris takes it */
-                        const uint32_t pc = (lpack & (RT_LIST_MAX - 1u)) + 1u, first = (lpack >> RT_LIST_BITS) << 3;
                         if (lpack == RT_LPACK_EMPTY) {
                             running = false;
                             ts.best = -1;
                             cq.best = -1;
                             fin = true;
                         } else if (lpack != RT_LPACK_NONE) {
-                            for (uint32_t b = (pc - 1u) >> 3; b > 0u; --b) {
-                                const uint32_t k = pc - 8u * b < 8u ? pc - 8u * b : 8u;
-                                const int v = ~(int)(((first + 8u * b) << 3) | (k - 1u));
-                                if (COOP) {
+                            const ListRange lr = list_range(lpack);
+                            if (COOP) { /* the group's stack, by its first lane (coop_round: the first block on top) */
+                                const auto push = [&](int v) {
                                     if (lane == gbase) gst[cq.sp] = v;
                                     ++cq.sp;
-                                } else {
-                                    stk.push(v);
-                                }
-                            }
-                            const int n0 = ~(int)((first << 3) | ((pc < 8u ? pc : 8u) - 1u));
-                            if (COOP) { /* coop_round: the list's first block on top */
-                                if (lane == gbase) gst[cq.sp] = n0;
-                                ++cq.sp;
+                                };
+                                push(list_leaves(lr.count, lr.first, push));
                             } else {
-                                ts.node = n0;
+                                ts.node = list_leaves(lr.count, lr.first, [&](int v) { stk.push(v); });
                             }
                         } else if (COOP) { /* no list: the tree, from the root's children */
                             if (!coop_root(rq0, rq1, rq2, rq3, cq, gst, qd, lane == gbase)) {
@@ -434,29 +455,13 @@ __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
                 bool sample_done = true;
                 const bool mesh_hit = (COOP ? cq.best : ts.best) >= 0;
                 if (mesh_hit) { /* mesh hit: the light samples' draws, no bounce (rtcommon.h:411-421) */
-                    for (uint32_t l = 0; l < nl; ++l) {
-                        (void)frand(seed);
-                        (void)frand(seed);
-                    }
+                    light_draws(seed, nl);
                 } else { /* the enclosing box (rtcommon.h:425-466) */
                     const float hd = intersect_box(qo, qd, RT_SMALL_F, bw, bh, bw);
                     if (depth == 0) ++st_box;
                     if (hd > RT_SMALL_F && hd < kInf) {
                         const V3 hp = v3(qo.x + qd.x * hd, qo.y + qd.y * hd, qo.z + qd.z * hd);
-                        const V3 hn = box_normal(hp, bw, bh, bw);
-                        for (uint32_t l = 0; l < nl; ++l) {
-                            (void)frand(seed);
-                            (void)frand(seed);
-                        }
-                        const float r1 = frand(seed);
-                        const float r2 = frand(seed);
-                        const float ct = rt_sqrtf(1.0f - r1);
-                        const float st = rt_sqrtf(1.0f - ct * ct);
-                        const float phi = RT_M_2PI_F * r2;
-                        float sphi, cphi;
-                        rt_sincosf(phi, &sphi, &cphi);
-                        qd = shading_to_world(v3(cphi * st, sphi * st, ct), hn);
-                        qo = hp;
+                        box_bounce(seed, nl, hp, box_normal(hp, bw, bh, bw), qo, qd);
                         ++depth;
                         if (depth <= a.max_depth) {
                             sample_done = false;
@@ -479,9 +484,7 @@ __device__ __forceinline__ void seed_pass(const RtTriLaunch &a, int *s_stack)
                     }
                 }
                 if (sample_done) {
-                    /* the sample's mesh-hit depth (0xff: only the box), as k_chain_seeds stores it */
-                    if (a.split_hit_depth && lane == gbase)
-                        a.split_hit_depth[(size_t)pslot * spp + sample] = mesh_hit ? (uint8_t)depth : (uint8_t)0xffu;
+                    if (lane == gbase) seed_sample_end(a, pslot, sample, mesh_hit, depth);
                     ++sample;
                     next = true;
                 }
@@ -743,7 +746,6 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
     const float4 *__restrict__ tris = reinterpret_cast<const float4 *>(a.tris);
     const int eslot = sub < ne ? s_slot[sub] : 0;
     const uint32_t spp = a.sample_rate * a.sample_rate, fine = a.split_fine, nseed = a.split_nseed;
-    const uint32_t plane = a.Wpad * a.Hpad;
     const uint32_t tiles_x = (a.W + 7u) >> 3;
     const uint32_t n_items = box_items(a);
     const uint32_t nl = a.n_lights;
@@ -757,13 +759,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
     uint32_t bnext = 0, bend = 0;
     Seed seed = {0u, 0u};
     V3 qo = v3(0.0f, 0.0f, 0.0f), qd = v3(0.0f, 0.0f, 1.0f);
-    TravState ts;
-    ts.node = 0;
-    ts.best = -1;
-    ts.best_orig = -1;
-    ts.best_t = kInf;
-    ts.inv = qo;
-    ts.oi = qo;
+    TravState ts = trav_idle();
     uint32_t st_steps = 0, st_box = 0, st_t0 = 0, q_steps = 0;
     unsigned long long *const guard = a.counters + RT_CNT_GUARD;
     /* a query of the tree starts at the lane's edge of the cut; false: no lane of the group
@@ -790,9 +786,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
                 pslot = a.split_seed_slot ? item : p;
                 x = p % a.W;
                 yl = p / a.W;
-                const uint32_t slot = global_row(a, yl) * a.Wpad + x;
-                seed.x = a.seeds[slot];
-                seed.y = a.seeds[plane + slot];
+                seed = load_seed(a, seed_slot(a, x, yl));
                 sample = 0;
                 if (a.split_restart) { /* a repaired pixel: from its first missed chunk, whose seed the
                                           jump gives (every sample before it hit the mesh) */
@@ -825,29 +819,13 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
                 fin = false;
                 bool sample_done = true;
                 if (ghit) { /* mesh hit: the light samples' draws, no bounce (rtcommon.h:411-421) */
-                    for (uint32_t l = 0; l < nl; ++l) {
-                        (void)frand(seed);
-                        (void)frand(seed);
-                    }
+                    light_draws(seed, nl);
                 } else { /* the enclosing box (rtcommon.h:425-466) */
                     const float hd = group_box(qo, qd, RT_SMALL_F, bw, bh, bw, sub, gbase);
                     if (depth == 0) ++st_box;
                     if (hd > RT_SMALL_F && hd < kInf) {
                         const V3 hp = v3(qo.x + qd.x * hd, qo.y + qd.y * hd, qo.z + qd.z * hd);
-                        const V3 hn = box_normal_signs(hp, bw, bh, bw);
-                        for (uint32_t l = 0; l < nl; ++l) {
-                            (void)frand(seed);
-                            (void)frand(seed);
-                        }
-                        const float r1 = frand(seed);
-                        const float r2 = frand(seed);
-                        const float ct = rt_sqrtf(1.0f - r1);
-                        const float st = rt_sqrtf(1.0f - ct * ct);
-                        const float phi = RT_M_2PI_F * r2;
-                        float sphi, cphi;
-                        rt_sincosf(phi, &sphi, &cphi);
-                        qd = shading_to_world(v3(cphi * st, sphi * st, ct), hn);
-                        qo = hp;
+                        box_bounce(seed, nl, hp, box_normal_signs(hp, bw, bh, bw), qo, qd);
                         ++depth;
                         if (depth <= a.max_depth) {
                             sample_done = false;
@@ -856,8 +834,8 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
                     }
                 }
                 if (sample_done) {
-                    if (!RUNS && a.split_hit_depth && lane == gbase) /* (not the repair pass: NULL there) */
-                        a.split_hit_depth[(size_t)pslot * spp + sample] = ghit ? (uint8_t)depth : (uint8_t)0xffu;
+                    /* (not the repair pass: split_hit_depth is NULL there) */
+                    if (!RUNS && lane == gbase) seed_sample_end(a, pslot, sample, ghit, depth);
                     ++sample;
                     next = true;
                 }
@@ -880,15 +858,11 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
                 if ((uint32_t)sub < runmax) {
                     const uint32_t s = sample + (uint32_t)sub;
                     Seed sc = sl;
-                    const uint32_t sx = s / a.sample_rate, sy = s % a.sample_rate;
-                    const float fa = (float)x + strat_rand(sc, (int)sx, (int)a.sample_rate);
-                    const uint32_t y = global_row(a, yl);
-                    const float fb = (float)y + strat_rand(sc, (int)sy, (int)a.sample_rate);
-                    const V3 o = v3(a.cam.position.x, a.cam.position.y, a.cam.position.z);
-                    const V3 dd = camera_dir(a.cam, fa - hw, fb - hh);
-                    const uint32_t pc = (lpack & (RT_LIST_MAX - 1u)) + 1u, first = (lpack >> RT_LIST_BITS) << 3;
-                    for (uint32_t t = 0; t < pc && !hit; ++t) {
-                        const uint32_t r = first + t;
+                    V3 o, dd;
+                    camera_ray(a, sc, x, global_row(a, yl), s / a.sample_rate, s % a.sample_rate, hw, hh, o, dd);
+                    const ListRange lr = list_range(lpack);
+                    for (uint32_t t = 0; t < lr.count && !hit; ++t) {
+                        const uint32_t r = lr.first + t;
                         float tt = 0.0f;
                         const bool h = mt_test(o, dd, tris[3 * r], tris[3 * r + 1], tris[3 * r + 2], tt);
                         hit = h && !(tt < RT_SMALL_F) && tt <= kInf; /* the closest-hit acceptance */
@@ -914,20 +888,11 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
             }
             if (next && !run_on) {
                 next = false;
-                if ((sample == spp || sample % fine == 0u) && lane == gbase) {
-                    const uint32_t c = sample == spp ? nseed - 1u : sample / fine;
-                    reinterpret_cast<uint2 *>(a.split_seed)[(size_t)pslot * nseed + c] = make_uint2(seed.x, seed.y);
-                }
+                if (lane == gbase)
+                    (void)seed_sample_next(a, pslot, x, yl, sample, seed, st_t0, st_steps, st_box,
+                                           1u + (uint32_t)RT_SPLIT_BOX);
                 if (sample == spp) {
                     have = false;
-                    if (a.pixel_stats && lane == gbase) {
-                        uint32_t *ps = a.pixel_stats + 8 * ((size_t)yl * a.W + x);
-                        ps[0] = st_t0;
-                        ps[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-                        ps[2] = st_steps;
-                        ps[3] = st_box;
-                        ps[4] = 1u + (uint32_t)RT_SPLIT_BOX;
-                    }
                 } else {
                     /* strat_rand twice (rng.h:45-47): the two draws, then the divisions on two lanes */
                     const float f1 = frand(seed), f2 = frand(seed);
@@ -953,11 +918,11 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_chain_seeds(RtTriLa
                     ghit = false;
                     fin = true;
                 } else if (depth == 0 && lpack != RT_LPACK_NONE) { /* the list's triangles in runs over the lanes */
-                    const uint32_t pc = (lpack & (RT_LIST_MAX - 1u)) + 1u, first = (lpack >> RT_LIST_BITS) << 3;
-                    const uint32_t bs = (pc + (uint32_t)G - 1u) / (uint32_t)G, s0 = (uint32_t)sub * bs;
-                    live = s0 < pc;
-                    const uint32_t cnt = live ? (pc - s0 < bs ? pc - s0 : bs) : 1u;
-                    ts.node = ~(int)(((first + s0) << 3) | (cnt - 1u));
+                    const ListRange lr = list_range(lpack);
+                    const uint32_t bs = (lr.count + (uint32_t)G - 1u) / (uint32_t)G, s0 = (uint32_t)sub * bs;
+                    live = s0 < lr.count;
+                    const uint32_t cnt = live ? (lr.count - s0 < bs ? lr.count - s0 : bs) : 1u;
+                    ts.node = ~(int)(((lr.first + s0) << 3) | (cnt - 1u));
                 } else if (!start_tree()) { /* misses every subtree's box: no mesh hit, at once */
                     running = false;
                     ghit = false;
@@ -1041,23 +1006,12 @@ __global__ __launch_bounds__(RT_BLOCK) void k_split_finish(RtTriLaunch a)
                 }
             }
         }
-        const float nf = (float)spp;
-        float4 px = make_float4(acc_x / nf, acc_y / nf, acc_z / nf, 0.0f / nf);
-        float4 *dst = reinterpret_cast<float4 *>(a.out) + p;
-        if (a.progressive > 0) {
-            const float4 old = *dst;
-            const float t = 1.0f / (float)a.progressive;
-            px.x = old.x + (px.x - old.x) * t;
-            px.y = old.y + (px.y - old.y) * t;
-            px.z = old.z + (px.z - old.z) * t;
-            px.w = old.w + (px.w - old.w) * t;
-        }
-        *dst = px;
+        write_pixel(reinterpret_cast<float4 *>(a.out) + p, pixel_mean(acc_x, acc_y, acc_z, (float)spp),
+                    a.progressive > 0, 1.0f / (float)a.progressive);
         const uint32_t x = p % a.W, yl = p / a.W;
-        const uint32_t slot = global_row(a, yl) * a.Wpad + x;
+        const uint32_t slot = seed_slot(a, x, yl);
         const uint2 sd = reinterpret_cast<const uint2 *>(a.split_seed)[(size_t)p * a.split_nseed + a.split_nseed - 1u];
-        a.seeds[slot] = sd.x;
-        a.seeds[a.Wpad * a.Hpad + slot] = sd.y;
+        store_seed(a, slot, sd.x, sd.y);
     }
 }
 
@@ -1097,23 +1051,13 @@ __global__ __launch_bounds__(RT_BLOCK) void k_split_finish_list(RtTriLaunch a)
             }
         }
         if (lane != 0u) continue;
-        const float nf = (float)spp;
-        float4 px = make_float4(acc_x / nf, acc_y / nf, acc_z / nf, 0.0f / nf);
-        float4 *dst = reinterpret_cast<float4 *>(a.out) + p;
-        if (a.progressive > 0) {
-            const float4 old = *dst;
-            const float t = 1.0f / (float)a.progressive;
-            px.x = old.x + (px.x - old.x) * t;
-            px.y = old.y + (px.y - old.y) * t;
-            px.z = old.z + (px.z - old.z) * t;
-            px.w = old.w + (px.w - old.w) * t;
-        }
-        *dst = px;
+        write_pixel(reinterpret_cast<float4 *>(a.out) + p, pixel_mean(acc_x, acc_y, acc_z, (float)spp),
+                    a.progressive > 0, 1.0f / (float)a.progressive);
         const uint32_t x = p % a.W, yl = p / a.W;
-        const uint32_t slot = global_row(a, yl) * a.Wpad + x;
-        const uint2 sd = reinterpret_cast<const uint2 *>(a.split_seed)[(size_t)(a.split_seed_slot ? i : p) * a.split_nseed + a.split_nseed - 1u];
-        a.seeds[slot] = sd.x;
-        a.seeds[a.Wpad * a.Hpad + slot] = sd.y;
+        const uint32_t slot = seed_slot(a, x, yl);
+        const uint2 sd = reinterpret_cast<const uint2 *>(
+            a.split_seed)[(size_t)(a.split_seed_slot ? i : p) * a.split_nseed + a.split_nseed - 1u];
+        store_seed(a, slot, sd.x, sd.y);
     }
 }
 

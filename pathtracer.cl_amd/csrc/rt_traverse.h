@@ -2,7 +2,8 @@
  * rt_traverse.h — the per-lane ray queries of the gfx950 kernels: the reference's
  * ray/triangle test, the LDS traversal stack with its global spill tail, and the
  * resumable traversal of the 4-wide trees (full-precision and compressed nodes) with
- * the linear loop beside them.  Shared by rt_tris.hip and rt_split.hip (the render
+ * the linear loop beside them; a query's idle state (trav_idle) and a candidate list as
+ * the traversal's virtual leaves (list_leaves).  Shared by rt_tris.hip and rt_split.hip (the render
  * kernels), rt_spheres.hip (the batch ray queries), rt_sched.hip (the cost probe),
  * rt_lists.hip and rt_features.hip (the first-hit feature kernel); everything here has
  * internal linkage.
@@ -200,6 +201,32 @@ __device__ __forceinline__ void trav_begin(TravState &s, Stack &stk, V3 o, V3 d,
     s.best_orig = -1;
     s.best_t = tmax;
     stk.sp = 0;
+}
+
+/* the state of a lane without a query */
+__device__ __forceinline__ TravState trav_idle()
+{
+    TravState s;
+    s.node = 0;
+    s.best = -1;
+    s.best_orig = -1;
+    s.best_t = kInf;
+    s.inv = v3(0.0f, 0.0f, 0.0f);
+    s.oi = s.inv;
+    return s;
+}
+
+/* A candidate list (`count` records from slot `first`, a multiple of 8: rt_kernel_util.h
+   list_range) as virtual leaves of at most 8 records: the later blocks pushed, last first, the
+   first block returned — a per-lane query's cursor, a cooperative one's top entry. */
+template <class Push>
+__device__ __forceinline__ int list_leaves(uint32_t count, uint32_t first, Push push)
+{
+    for (uint32_t b = (count - 1u) >> 3; b > 0u; --b) {
+        const uint32_t k = count - 8u * b < 8u ? count - 8u * b : 8u;
+        push(~(int)(((first + 8u * b) << 3) | (k - 1u)));
+    }
+    return ~(int)((first << 3) | ((count < 8u ? count : 8u) - 1u));
 }
 
 /* Half `hi` of a word of two f16 values, widened to f32 (exact; folds into the

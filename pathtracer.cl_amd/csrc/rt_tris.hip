@@ -53,6 +53,23 @@ __device__ __forceinline__ bool segment_misses_box(V3 o, V3 d, float tmin, float
     return tn > tf;
 }
 
+/* A traversal step's counts (trav_step's TravCounts) in a lane's counters and in its pixel's
+   measured cost: the records visited in a counting launch, the trav_step calls otherwise
+   (pixel_iter) */
+template <bool COUNT>
+__device__ __forceinline__ void count_step(unsigned long long (&cnt)[RT_N_COUNTERS], unsigned long long &pix_steps,
+                                           const TravCounts &tc)
+{
+    if (COUNT) {
+        cnt[2] += tc.nodes;
+        cnt[3] += tc.tests;
+        cnt[4] += tc.leaves;
+        pix_steps += tc.nodes + tc.leaves;
+    } else {
+        ++pix_steps;
+    }
+}
+
 /* ======================================================================== */
 /* Triangle kernel: raytrace_tris + trace_path_tri (rtcommon.h:371-470).     */
 
@@ -128,7 +145,6 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
     const float4 *__restrict__ tris = reinterpret_cast<const float4 *>(a.tris);
     float4 *__restrict__ out = reinterpret_cast<float4 *>(a.out);
     const uint32_t spp = a.sample_rate * a.sample_rate;
-    const uint32_t plane = a.Wpad * a.Hpad;
     const uint32_t tiles_x = (a.W + 7u) >> 3;
     const uint32_t tiles_y = (a.Hl + 7u) >> 3;
     const uint32_t n_items = tiles_x * tiles_y * 64u;
@@ -166,13 +182,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
     bool fin = false;     /* the lane's query completed: ts.best / ts.best_t hold its result */
     const ShadowCut sc_cut = {a.shadow_cut_lo, RT_NO_SHADOW_CACHE ? 0u : a.shadow_cut_hi - a.shadow_cut_lo,
                               (int)a.shadow_root};
-    TravState ts;
-    ts.node = 0;
-    ts.best = -1;
-    ts.best_orig = -1;
-    ts.best_t = kInf;
-    ts.inv = qo;
-    ts.oi = qo;
+    TravState ts = trav_idle();
     unsigned long long cnt[RT_N_COUNTERS] = {};
     const unsigned long long t_k0 = COUNT ? wave_clock() : 0ull;
     /* counting launches: this pixel's start clock, queries and traversal steps */
@@ -197,233 +207,218 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
         const unsigned long long t_d0 = (COUNT || RT_PLAIN_PIXEL_STATS) ? wave_clock() : 0ull;
         /* ---- D: advance the path (trace_path_tri, rtcommon.h:378-468) ---- */
         for (int redo_pass = 0;; ++redo_pass) {
-        if (fin) {
-            fin = false;
-            bool want_shadow = false, seg_done = false, sample_done = false;
-            if (mode == M_CLOSEST) {
-                ++cnt[0];
-                if (COUNT || RT_PLAIN_PIXEL_STATS) ++pix_q;
-                bool surface = true;
-                if (ts.best >= 0) {
-                    const float qt = ts.best_t;
-                    hp = v3(qo.x + qd.x * qt, qo.y + qd.y * qt, qo.z + qd.z * qt);
-                    /* the unnormalised normal (rtcommon.h:389): written to LDS at the accept, the
-                       same float operations on the same record (kept in registers instead it
-                       measured 8 % slower, r01; a second fetch of the edges here is one more
-                       dependent round trip per mesh hit) */
-                    if (TRAV == RT_TRAV_BVH4Q) {
-                        hn = v3(st_hn[0], st_hn[RT_BLOCK], st_hn[2 * RT_BLOCK]);
+            if (fin) {
+                fin = false;
+                bool want_shadow = false, seg_done = false, sample_done = false;
+                if (mode == M_CLOSEST) {
+                    ++cnt[0];
+                    if (COUNT || RT_PLAIN_PIXEL_STATS) ++pix_q;
+                    bool surface = true;
+                    if (ts.best >= 0) {
+                        const float qt = ts.best_t;
+                        hp = v3(qo.x + qd.x * qt, qo.y + qd.y * qt, qo.z + qd.z * qt);
+                        /* the unnormalised normal (rtcommon.h:389): written to LDS at the accept, the
+                           same float operations on the same record (kept in registers instead it
+                           measured 8 % slower, r01; a second fetch of the edges here is one more
+                           dependent round trip per mesh hit) */
+                        if (TRAV == RT_TRAV_BVH4Q) {
+                            hn = v3(st_hn[0], st_hn[RT_BLOCK], st_hn[2 * RT_BLOCK]);
+                        } else {
+                            const float4 e1 = tris[3 * ts.best + 1];
+                            const float4 e2 = tris[3 * ts.best + 2];
+                            hn = cross3(v3(e2.x, e2.y, e2.z), v3(e1.x, e1.y, e1.z)); /* unnormalised, rtcommon.h:389 */
+                        }
+                        tri_hit = true;
                     } else {
-                        const float4 e1 = tris[3 * ts.best + 1];
-                        const float4 e2 = tris[3 * ts.best + 2];
-                        hn = cross3(v3(e2.x, e2.y, e2.z), v3(e1.x, e1.y, e1.z)); /* unnormalised, rtcommon.h:389 */
+                        if (SPLIT && depth == 0 && a.split_spec && a.split_which == RT_SPLIT_MESH &&
+                            sample / a.split_chunk + 1u < a.split_chunks) {
+                            /* a speculated pixel's camera ray missed the mesh: its later chunks started
+                               from wrong seeds — listed once for the repair pass, which restarts at the
+                               first such chunk (rare path) */
+                            const uint32_t p = yl * a.W + x;
+                            if (atomicMin(a.split_dirty + p, sample / a.split_chunk) == ~0u)
+                                a.split_repair[(uint32_t)atomicAdd(a.counters + RT_CNT_REPAIR, 1ull)] = p;
+                        }
+                        /* the enclosing box (rtcommon.h:427-433); ray.tmax is still INF */
+                        const float hd = intersect_box(qo, qd, RT_SMALL_F, bw, bh, bw);
+                        if (hd > RT_SMALL_F && hd < kInf) {
+                            hp = v3(qo.x + qd.x * hd, qo.y + qd.y * hd, qo.z + qd.z * hd);
+                            hn = box_normal(hp, bw, bh, bw);
+                            tri_hit = false;
+                        } else {
+                            surface = false;
+                            sample_done = true; /* path terminates (rtcommon.h:463-466) */
+                        }
                     }
-                    tri_hit = true;
+                    if (surface) { /* sample_direct_illumination_tri, rtcommon.h:78-105 */
+                        /* the shadow-ray origin (so) becomes the query origin */
+                        qo = v3(hp.x + hn.x * RT_SMALL_F, hp.y + hn.y * RT_SMALL_F, hp.z + hn.z * RT_SMALL_F);
+                        direct = v3(0.0f, 0.0f, 0.0f);
+                        light = 0;
+                        if (n_lights > 0) want_shadow = true;
+                        else seg_done = true;
+                    }
                 } else {
-                    if (SPLIT && depth == 0 && a.split_spec && a.split_which == RT_SPLIT_MESH &&
-                        sample / a.split_chunk + 1u < a.split_chunks) {
-                        /* a speculated pixel's camera ray missed the mesh: its later chunks started
-                           from wrong seeds — listed once for the repair pass, which restarts at the
-                           first such chunk (rare path) */
-                        const uint32_t p = yl * a.W + x;
-                        if (atomicMin(a.split_dirty + p, sample / a.split_chunk) == ~0u)
-                            a.split_repair[(uint32_t)atomicAdd(a.counters + RT_CNT_REPAIR, 1ull)] = p;
+                    ++cnt[1];
+                    if (COUNT || RT_PLAIN_PIXEL_STATS) ++pix_q;
+                    /* the shadow cache: an unoccluded answer from a mesh hit (-1, from the full traversal;
+                       not the -2 of a ray answered without one) leaves the pixel no cut node to start at */
+                    if (!RT_NO_SHADOW_CACHE && tri_hit && ts.best == -1) *st_entry = 0;
+                    if (ts.best < 0) { /* unoccluded: rtcommon.h:93-101 */
+                        const float cw = qd.x * hn.x + qd.y * hn.y + qd.z * hn.z;
+                        if (cw > 0) {
+                            direct.x += s_light[light * 8 + 4] * cw;
+                            direct.y += s_light[light * 8 + 5] * cw;
+                            direct.z += s_light[light * 8 + 6] * cw;
+                        }
                     }
-                    /* the enclosing box (rtcommon.h:427-433); ray.tmax is still INF */
-                    const float hd = intersect_box(qo, qd, RT_SMALL_F, bw, bh, bw);
-                    if (hd > RT_SMALL_F && hd < kInf) {
-                        hp = v3(qo.x + qd.x * hd, qo.y + qd.y * hd, qo.z + qd.z * hd);
-                        hn = box_normal(hp, bw, bh, bw);
-                        tri_hit = false;
-                    } else {
-                        surface = false;
-                        sample_done = true; /* path terminates (rtcommon.h:463-466) */
-                    }
-                }
-                if (surface) { /* sample_direct_illumination_tri, rtcommon.h:78-105 */
-                    /* the shadow-ray origin (so) becomes the query origin */
-                    qo = v3(hp.x + hn.x * RT_SMALL_F, hp.y + hn.y * RT_SMALL_F, hp.z + hn.z * RT_SMALL_F);
-                    direct = v3(0.0f, 0.0f, 0.0f);
-                    light = 0;
-                    if (n_lights > 0) want_shadow = true;
+                    ++light;
+                    if (light < n_lights) want_shadow = true;
                     else seg_done = true;
                 }
-            } else {
-                ++cnt[1];
-                if (COUNT || RT_PLAIN_PIXEL_STATS) ++pix_q;
-                /* the shadow cache: an unoccluded answer from a mesh hit (-1, from the full traversal;
-                   not the -2 of a ray answered without one) leaves the pixel no cut node to start at */
-                if (!RT_NO_SHADOW_CACHE && tri_hit && ts.best == -1) *st_entry = 0;
-                if (ts.best < 0) { /* unoccluded: rtcommon.h:93-101 */
-                    const float cw = qd.x * hn.x + qd.y * hn.y + qd.z * hn.z;
-                    if (cw > 0) {
-                        direct.x += s_light[light * 8 + 4] * cw;
-                        direct.y += s_light[light * 8 + 5] * cw;
-                        direct.z += s_light[light * 8 + 6] * cw;
+                bool bounce = false;
+                if (seg_done) {
+                    const float scale = 1.0f * RT_M_1_PI_F;
+                    V3 prop = v3(PROP_GET(0), PROP_GET(1), PROP_GET(2));
+                    if (tri_hit) { /* rtcommon.h:411-421: no bounce off triangles */
+                        col_x += prop.x * direct.x * scale * 0.7f;
+                        col_y += prop.y * direct.y * scale * 0.7f;
+                        col_z += prop.z * direct.z * scale * 0.7f;
+                        sample_done = true;
+                    } else { /* rtcommon.h:435-461: albedo 0.7, Lambert bounce (drawn even at the last depth) */
+                        prop.x *= 0.7f;
+                        prop.y *= 0.7f;
+                        prop.z *= 0.7f;
+                        col_x += prop.x * direct.x * scale;
+                        col_y += prop.y * direct.y * scale;
+                        col_z += prop.z * direct.z * scale;
+                        PROP_SET(0, prop.x);
+                        PROP_SET(1, prop.y);
+                        PROP_SET(2, prop.z);
+                        qo = hp;
+                        bounce = true;
                     }
                 }
-                ++light;
-                if (light < n_lights) want_shadow = true;
-                else seg_done = true;
-            }
-            bool bounce = false;
-            if (seg_done) {
-                const float scale = 1.0f * RT_M_1_PI_F;
-                V3 prop = v3(PROP_GET(0), PROP_GET(1), PROP_GET(2));
-                if (tri_hit) { /* rtcommon.h:411-421: no bounce off triangles */
-                    col_x += prop.x * direct.x * scale * 0.7f;
-                    col_y += prop.y * direct.y * scale * 0.7f;
-                    col_z += prop.z * direct.z * scale * 0.7f;
-                    sample_done = true;
-                } else { /* rtcommon.h:435-461: albedo 0.7, Lambert bounce (drawn even at the last depth) */
-                    prop.x *= 0.7f;
-                    prop.y *= 0.7f;
-                    prop.z *= 0.7f;
-                    col_x += prop.x * direct.x * scale;
-                    col_y += prop.y * direct.y * scale;
-                    col_z += prop.z * direct.z * scale;
-                    PROP_SET(0, prop.x);
-                    PROP_SET(1, prop.y);
-                    PROP_SET(2, prop.z);
-                    qo = hp;
-                    bounce = true;
-                }
-            }
-            /* Next direction, light sample or Lambert bounce, through ONE code path: both
-               draw r1 then r2 (rtcommon.h:92, :459), build (cos(phi) st, sin(phi) st, ct)
-               with phi = 2 pi r2 and st = sqrt(1 - ct^2), and rotate it about an axis
-               (shading_to_world) — sphereEmissiveRadiance (materials.h:232-271) about the
-               direction to the light with ct = 1 + r1 (cos_max - 1), cos_sample_hemisphere
-               (materials.h:21-35) about the normal with ct = sqrt(1 - r1).  Only ct and the
-               axis differ, so lanes of both kinds share the sin/cos and the frame. */
-            if (want_shadow || bounce) {
-                const float r1 = frand(seed);
-                const float r2 = frand(seed);
-                V3 axis = hn;
-                float ct = 0.0f;
-                V3 lc = hn;
-                float lr = 0.0f;
-                if (want_shadow) {
-                    lc = v3(s_light[light * 8 + 0], s_light[light * 8 + 1], s_light[light * 8 + 2]);
-                    lr = s_light[light * 8 + 3];
-                    V3 dir = v3(lc.x - qo.x, lc.y - qo.y, lc.z - qo.z);
-                    const float inv = rt_rsqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-                    dir.x *= inv;
-                    dir.y *= inv;
-                    dir.z *= inv;
-                    const float sin_max = lr * inv;
-                    const float cos_max = rt_sqrtf(1.0f - sin_max * sin_max);
-                    ct = 1.0f + r1 * (cos_max - 1.0f);
-                    axis = dir;
-                } else {
-                    ct = rt_sqrtf(1.0f - r1);
-                }
-                const float st = rt_sqrtf(1.0f - ct * ct);
-                const float phi = RT_M_2PI_F * r2;
-                float sphi, cphi;
-                rt_sincosf(phi, &sphi, &cphi);
-                qd = shading_to_world(v3(cphi * st, sphi * st, ct), axis);
-                if (want_shadow) {
-                    stmax = intersect_sphere(qo, qd, RT_SMALL_F, lc, lr) - RT_SMALL_F;
-                    mode = M_SHADOW;
-                } else {
-                    ++depth;
-                    if (depth > a.max_depth) sample_done = true;
-                    else mode = M_CLOSEST;
-                }
-            }
-            if (SPLIT && sample_done) { /* the sample's radiance, summed in order by k_split_finish */
-                hit_depth = 0; /* read per task: its first sample's */
-                float *dst = a.split_col + ((size_t)sample * (a.W * a.Hl) + (yl * a.W + x)) * 3u;
-                dst[0] = col_x;
-                dst[1] = col_y;
-                dst[2] = col_z;
-                ++sample;
-                mode = (sample >= spp || sample % a.split_chunk == 0u) ? M_IDLE : M_NEWSAMPLE;
-                if (a.pixel_iter && mode == M_IDLE) /* the chunk task's finish */
-                    a.pixel_iter[(size_t)a.W * a.Hl * a.split_chunks + (size_t)(yl * a.W + x) * a.split_chunks +
-                                 (sample - 1u) / a.split_chunk] = (uint32_t)pix_steps;
-                if (sample >= spp && !a.split_seed_slot) /* the pixel's final seed, from its last chunk's own draws
-                                                            (a slotted long chain's: from its seed pass) */
-                    reinterpret_cast<uint2 *>(a.split_seed)[(size_t)(yl * a.W + x) * a.split_nseed + a.split_nseed - 1u] =
-                        make_uint2(seed.x, seed.y);
-                if (mode == M_IDLE) {
-                    pclass = -1;
-                    if (COUNT && a.pixel_stats) { /* diagnostics: the pixel's queries and steps over its chunks */
-                        uint32_t *ps = a.pixel_stats + 8 * ((size_t)yl * a.W + x);
-                        atomicAdd(ps + 5, (uint32_t)pix_q);
-                        atomicAdd(ps + 6, (uint32_t)pix_steps);
+                /* Next direction, light sample or Lambert bounce, through ONE code path: both
+                   draw r1 then r2 (rtcommon.h:92, :459), build (cos(phi) st, sin(phi) st, ct)
+                   with phi = 2 pi r2 and st = sqrt(1 - ct^2), and rotate it about an axis
+                   (shading_to_world) — sphereEmissiveRadiance (materials.h:232-271) about the
+                   direction to the light with ct = 1 + r1 (cos_max - 1), cos_sample_hemisphere
+                   (materials.h:21-35) about the normal with ct = sqrt(1 - r1).  Only ct and the
+                   axis differ, so lanes of both kinds share the sin/cos and the frame. */
+                if (want_shadow || bounce) {
+                    const float r1 = frand(seed);
+                    const float r2 = frand(seed);
+                    V3 axis = hn;
+                    float ct = 0.0f;
+                    V3 lc = hn;
+                    float lr = 0.0f;
+                    if (want_shadow) {
+                        lc = v3(s_light[light * 8 + 0], s_light[light * 8 + 1], s_light[light * 8 + 2]);
+                        lr = s_light[light * 8 + 3];
+                        V3 dir = v3(lc.x - qo.x, lc.y - qo.y, lc.z - qo.z);
+                        const float inv = rt_rsqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
+                        dir.x *= inv;
+                        dir.y *= inv;
+                        dir.z *= inv;
+                        const float sin_max = lr * inv;
+                        const float cos_max = rt_sqrtf(1.0f - sin_max * sin_max);
+                        ct = 1.0f + r1 * (cos_max - 1.0f);
+                        axis = dir;
+                    } else {
+                        ct = rt_sqrtf(1.0f - r1);
+                    }
+                    const float st = rt_sqrtf(1.0f - ct * ct);
+                    const float phi = RT_M_2PI_F * r2;
+                    float sphi, cphi;
+                    rt_sincosf(phi, &sphi, &cphi);
+                    qd = shading_to_world(v3(cphi * st, sphi * st, ct), axis);
+                    if (want_shadow) {
+                        stmax = intersect_sphere(qo, qd, RT_SMALL_F, lc, lr) - RT_SMALL_F;
+                        mode = M_SHADOW;
+                    } else {
+                        ++depth;
+                        if (depth > a.max_depth) sample_done = true;
+                        else mode = M_CLOSEST;
                     }
                 }
-            } else if (sample_done) {
-                ACC_SET(0, ACC_GET(0) + col_x);
-                ACC_SET(1, ACC_GET(1) + col_y);
-                ACC_SET(2, ACC_GET(2) + col_z);
-                ++sample;
-                mode = M_NEWSAMPLE;
-                if (sample >= spp) { /* raytracer.cl:234-242 */
-                    {
-                        const float n = (float)spp;
-                        const float acc_x = ACC_GET(0), acc_y = ACC_GET(1), acc_z = ACC_GET(2);
-                        float4 p = make_float4(acc_x / n, acc_y / n, acc_z / n, 0.0f / n);
-                        float4 *dst = out + ((size_t)yl * a.W + x);
-                        if (a.progressive > 0) {
-                            const float4 old = *dst;
-                            const float t = mix_t;
-                            p.x = old.x + (p.x - old.x) * t;
-                            p.y = old.y + (p.y - old.y) * t;
-                            p.z = old.z + (p.z - old.z) * t;
-                            p.w = old.w + (p.w - old.w) * t;
+                if (SPLIT && sample_done) { /* the sample's radiance, summed in order by k_split_finish */
+                    hit_depth = 0; /* read per task: its first sample's */
+                    float *dst = a.split_col + ((size_t)sample * (a.W * a.Hl) + (yl * a.W + x)) * 3u;
+                    dst[0] = col_x;
+                    dst[1] = col_y;
+                    dst[2] = col_z;
+                    ++sample;
+                    mode = (sample >= spp || sample % a.split_chunk == 0u) ? M_IDLE : M_NEWSAMPLE;
+                    if (a.pixel_iter && mode == M_IDLE) /* the chunk task's finish */
+                        a.pixel_iter[(size_t)a.W * a.Hl * a.split_chunks + (size_t)(yl * a.W + x) * a.split_chunks +
+                                     (sample - 1u) / a.split_chunk] = (uint32_t)pix_steps;
+                    if (sample >= spp && !a.split_seed_slot) /* the pixel's final seed, from its last chunk's own draws
+                                                                (a slotted long chain's: from its seed pass) */
+                        reinterpret_cast<uint2 *>(a.split_seed)[(size_t)(yl * a.W + x) * a.split_nseed + a.split_nseed - 1u] =
+                            make_uint2(seed.x, seed.y);
+                    if (mode == M_IDLE) {
+                        pclass = -1;
+                        if (COUNT && a.pixel_stats) { /* diagnostics: the pixel's queries and steps over its chunks */
+                            uint32_t *ps = pixel_stats_rec(a, x, yl);
+                            atomicAdd(ps + 5, (uint32_t)pix_q);
+                            atomicAdd(ps + 6, (uint32_t)pix_steps);
                         }
-                        *dst = p;
                     }
-                    const uint32_t slot = global_row(a, yl) * a.Wpad + x;
-                    a.seeds[slot] = seed.x;
-                    a.seeds[plane + slot] = seed.y;
-                    if (a.pixel_iter) a.pixel_iter[a.W * a.Hl + yl * a.W + x] = (uint32_t)pix_steps;
-                    mode = M_IDLE;
-                    pclass = -1;
-                    if ((COUNT || RT_PLAIN_PIXEL_STATS) && a.pixel_stats) { /* diagnostics (RT_PIXEL_STATS) */
-                        uint32_t *ps = a.pixel_stats + 8 * ((size_t)yl * a.W + x);
-                        ps[0] = pix_rt0;
-                        ps[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-                        ps[2] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_q : 0u;
-                        ps[3] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_steps : 0u;
-                        ps[4] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_d >> 6) : 0u;
-                        ps[5] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_ab >> 6) : 0u;
-                        ps[6] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_c >> 6) : 0u;
-                        ps[7] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_it : 0u;
-                    }
-                    if (COUNT && !RT_DIAG_MIX && !RT_DIAG_RAYSPLIT && !RT_DIAG_SHCACHE && !RT_DIAG_INLINE) {
-                        const unsigned long long dt = wave_clock() - pix_t0;
-                        cnt[10] = dt > cnt[10] ? dt : cnt[10];
-                        cnt[11] = pix_q > cnt[11] ? pix_q : cnt[11];
-                        cnt[12] = pix_steps > cnt[12] ? pix_steps : cnt[12];
+                } else if (sample_done) {
+                    ACC_SET(0, ACC_GET(0) + col_x);
+                    ACC_SET(1, ACC_GET(1) + col_y);
+                    ACC_SET(2, ACC_GET(2) + col_z);
+                    ++sample;
+                    mode = M_NEWSAMPLE;
+                    if (sample >= spp) { /* raytracer.cl:234-242 */
+                        write_pixel(out + ((size_t)yl * a.W + x),
+                                    pixel_mean(ACC_GET(0), ACC_GET(1), ACC_GET(2), (float)spp), a.progressive > 0, mix_t);
+                        store_seed(a, seed_slot(a, x, yl), seed.x, seed.y);
+                        if (a.pixel_iter) a.pixel_iter[a.W * a.Hl + yl * a.W + x] = (uint32_t)pix_steps;
+                        mode = M_IDLE;
+                        pclass = -1;
+                        if ((COUNT || RT_PLAIN_PIXEL_STATS) && a.pixel_stats) { /* diagnostics (RT_PIXEL_STATS) */
+                            uint32_t *ps = pixel_stats_rec(a, x, yl);
+                            ps[0] = pix_rt0;
+                            ps[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+                            ps[2] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_q : 0u;
+                            ps[3] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_steps : 0u;
+                            ps[4] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_d >> 6) : 0u;
+                            ps[5] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_ab >> 6) : 0u;
+                            ps[6] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)(pix_c >> 6) : 0u;
+                            ps[7] = (COUNT || RT_PLAIN_PIXEL_STATS) ? (uint32_t)pix_it : 0u;
+                        }
+                        if (COUNT && !RT_DIAG_MIX && !RT_DIAG_RAYSPLIT && !RT_DIAG_SHCACHE && !RT_DIAG_INLINE) {
+                            const unsigned long long dt = wave_clock() - pix_t0;
+                            cnt[10] = dt > cnt[10] ? dt : cnt[10];
+                            cnt[11] = pix_q > cnt[11] ? pix_q : cnt[11];
+                            cnt[12] = pix_steps > cnt[12] ? pix_steps : cnt[12];
+                        }
                     }
                 }
             }
-        }
-        /* a shadow ray just issued whose answer is known without a traversal (the C-phase rule
-           below: tmax <= tmin, or cos(wi) <= 0) is answered here and the path advanced again in
-           this pass, instead of after a whole stepping round (-3.9 %, profiles/r01n) */
-        const float cw_q = qd.x * hn.x + qd.y * hn.y + qd.z * hn.z;
-        const bool issued = mode == M_SHADOW && !fin && !running;
-        const bool need_trav = stmax > RT_SMALL_F && cw_q > 0;
-        /* likewise a long chain's box segment (split_hit_depth): no triangle accepted */
-        const bool known_miss = SPLIT && mode == M_CLOSEST && !fin && !running && (int)depth < hit_depth;
-        /* and a box-path query (a bounce off the box, or a shadow ray leaving it) whose segment misses
-           the mesh's padded bounds: no triangle accepted, whatever the traversal would visit */
-        bool off_mesh = false;
-        if (!SPLIT && redo_pass < kOffMeshRedo && a.mesh_bounds && !tri_hit && !fin && !running &&
-            ((mode == M_SHADOW && need_trav) || (mode == M_CLOSEST && depth > 0)))
-            off_mesh = segment_misses_box(qo, qd, RT_SMALL_F, mode == M_SHADOW ? stmax : kInf, a.mesh_lo, a.mesh_hi);
-        const bool redo = (issued && !need_trav) || known_miss || off_mesh;
-        if (!__any(redo)) break;
-        if (redo) {
-            ts.best = -2; /* no hit, without a traversal */
-            fin = true;
-            ++cnt[RT_CNT_SKIPPED];
-        }
+            /* a shadow ray just issued whose answer is known without a traversal (the C-phase rule
+               below: tmax <= tmin, or cos(wi) <= 0) is answered here and the path advanced again in
+               this pass, instead of after a whole stepping round (-3.9 %, profiles/r01n) */
+            const float cw_q = qd.x * hn.x + qd.y * hn.y + qd.z * hn.z;
+            const bool issued = mode == M_SHADOW && !fin && !running;
+            const bool need_trav = stmax > RT_SMALL_F && cw_q > 0;
+            /* likewise a long chain's box segment (split_hit_depth): no triangle accepted */
+            const bool known_miss = SPLIT && mode == M_CLOSEST && !fin && !running && (int)depth < hit_depth;
+            /* and a box-path query (a bounce off the box, or a shadow ray leaving it) whose segment misses
+               the mesh's padded bounds: no triangle accepted, whatever the traversal would visit */
+            bool off_mesh = false;
+            if (!SPLIT && redo_pass < kOffMeshRedo && a.mesh_bounds && !tri_hit && !fin && !running &&
+                ((mode == M_SHADOW && need_trav) || (mode == M_CLOSEST && depth > 0)))
+                off_mesh = segment_misses_box(qo, qd, RT_SMALL_F, mode == M_SHADOW ? stmax : kInf, a.mesh_lo, a.mesh_hi);
+            const bool redo = (issued && !need_trav) || known_miss || off_mesh;
+            if (!__any(redo)) break;
+            if (redo) {
+                ts.best = -2; /* no hit, without a traversal */
+                fin = true;
+                ++cnt[RT_CNT_SKIPPED];
+            }
         }
 
         const unsigned long long t_d1 = (COUNT || RT_PLAIN_PIXEL_STATS) ? wave_clock() : 0ull;
@@ -469,10 +464,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                             chunk = tile % a.split_chunks;
                             tile = tile / a.split_chunks;
                         }
-                        if (a.tile_order) tile = a.tile_order[tile];
-                        x = (tile % tiles_x) * 8u + (in & 7u);
-                        yl = (tile / tiles_x) * 8u + (in >> 3);
-                        take = x < a.W && yl < a.Hl;
+                        take = tile_pixel(a, a.tile_order, tile, in, tiles_x, x, yl);
                         sbase = yl * a.W + x;
                         if (SPLIT && take && a.split_which == RT_SPLIT_MESH)
                             take = a.pixel_class[(size_t)yl * a.W + x] == -1;
@@ -488,10 +480,10 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                     if (SPLIT && take && a.split_spec && a.split_which == RT_SPLIT_MESH) {
                         /* a speculated mesh pixel: the chunk's first seed jumped ahead from the
                            frame seed (split_spec_draws numbers per sample before it) */
-                        const uint32_t slot = global_row(a, yl) * a.Wpad + x;
+                        const Seed fs = load_seed(a, seed_slot(a, x, yl));
                         const uint32_t k = chunk * a.split_chunk * a.split_spec_draws;
-                        seed.x = mwc_jump<36969u>(a.seeds[slot], k, a.split_spec_mul[2 * chunk]);
-                        seed.y = mwc_jump<18000u>(a.seeds[plane + slot], k, a.split_spec_mul[2 * chunk + 1]);
+                        seed.x = mwc_jump<36969u>(fs.x, k, a.split_spec_mul[2 * chunk]);
+                        seed.y = mwc_jump<18000u>(fs.y, k, a.split_spec_mul[2 * chunk + 1]);
                     } else if (SPLIT && take) { /* the chunk's first seed, from the seed pass */
                         const uint2 sd = reinterpret_cast<const uint2 *>(
                             a.split_seed)[(size_t)sbase * a.split_nseed + chunk * a.split_chunk / a.split_fine];
@@ -507,10 +499,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         mode = M_NEWSAMPLE;
                         pix_q = pix_steps = 0;
                     } else if (take) {
-                        const uint32_t slot = global_row(a, yl) * a.Wpad + x;
-                        /* raytracer.cl:207-209: unshifted seed slot */
-                        seed.x = a.seeds[slot];
-                        seed.y = a.seeds[plane + slot];
+                        seed = load_seed(a, seed_slot(a, x, yl));
                         if (a.pixel_iter) a.pixel_iter[yl * a.W + x] = 0u;
                         if ((COUNT || RT_PLAIN_PIXEL_STATS) && a.pixel_stats)
                             pix_rt0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
@@ -519,7 +508,6 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         ACC_SET(0, 0.0f);
                         ACC_SET(1, 0.0f);
                         ACC_SET(2, 0.0f);
-                        const float acc_x = 0.0f, acc_y = 0.0f, acc_z = 0.0f;
                         sample = 0;
                         /* some of the probe's rays missed the mesh: box paths, long chains */
                         pclass = a.pixel_class ? a.pixel_class[(size_t)yl * a.W + x] : -1;
@@ -529,18 +517,8 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         } else if (spp > 0) {
                             mode = M_NEWSAMPLE;
                         } else { /* no samples: 0/0 pixels, seeds untouched (raytracer.cl:234-242) */
-                            const float n = 0.0f;
-                            float4 p = make_float4(acc_x / n, acc_y / n, acc_z / n, 0.0f / n);
-                            float4 *dst = out + ((size_t)yl * a.W + x);
-                            if (a.progressive > 0) {
-                                const float4 old = *dst;
-                                const float t = mix_t;
-                                p.x = old.x + (p.x - old.x) * t;
-                                p.y = old.y + (p.y - old.y) * t;
-                                p.z = old.z + (p.z - old.z) * t;
-                                p.w = old.w + (p.w - old.w) * t;
-                            }
-                            *dst = p;
+                            write_pixel(out + ((size_t)yl * a.W + x), pixel_mean(0.0f, 0.0f, 0.0f, 0.0f),
+                                        a.progressive > 0, mix_t);
                         }
                     }
                 }
@@ -562,12 +540,8 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
             /* (a long chain's box segment, split_hit_depth, is answered without a query as before) */
             const bool inl = INL && TRAV == RT_TRAV_BVH4Q && inline_k && pass < inline_passes && lpack < RT_LPACK_EMPTY &&
                              !(SPLIT && hit_depth > 0);
-            const uint32_t sx = sample / a.sample_rate, sy = sample % a.sample_rate;
-            const float fa = (float)x + strat_rand(seed, (int)sx, (int)a.sample_rate);
-            const uint32_t y = global_row(a, yl);
-            const float fb = (float)y + strat_rand(seed, (int)sy, (int)a.sample_rate);
-            qo = v3(a.cam.position.x, a.cam.position.y, a.cam.position.z);
-            qd = camera_dir(a.cam, fa - hw, fb - hh);
+            camera_ray(a, seed, x, global_row(a, yl), sample / a.sample_rate, sample % a.sample_rate, hw, hh, qo,
+                       qd);
             PROP_SET(0, 1.0f);
             PROP_SET(1, 1.0f);
             PROP_SET(2, 1.0f);
@@ -576,13 +550,9 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
             mode = M_CLOSEST;
             if (INL && TRAV == RT_TRAV_BVH4Q && inline_k && __any(inl)) {
                 if (inl) { /* the list as virtual leaves: its first block the cursor, the later ones stacked */
-                    const uint32_t pc = (lpack & (RT_LIST_MAX - 1u)) + 1u, first = (lpack >> RT_LIST_BITS) << 3;
+                    const ListRange lr = list_range(lpack);
                     trav_begin(ts, stk, qo, qd, kInf);
-                    for (uint32_t b = (pc - 1u) >> 3; b > 0u; --b) {
-                        const uint32_t k = pc - 8u * b < 8u ? pc - 8u * b : 8u;
-                        stk.push(~(int)(((first + 8u * b) << 3) | (k - 1u)));
-                    }
-                    ts.node = ~(int)((first << 3) | ((pc < 8u ? pc : 8u) - 1u));
+                    ts.node = list_leaves(lr.count, lr.first, [&](int v) { stk.push(v); });
                     running = true;
                 }
                 for (uint32_t i = 0; i < inline_k; ++i) {
@@ -596,14 +566,7 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                         }
                         /* steps of the pixel's measured cost and tests of a counting launch like the
                            loop's; lane_slots (cnt[5]) stays the loop's */
-                        if (COUNT) {
-                            cnt[2] += tc.nodes;
-                            cnt[3] += tc.tests;
-                            cnt[4] += tc.leaves;
-                            pix_steps += tc.nodes + tc.leaves;
-                        } else {
-                            ++pix_steps;
-                        }
+                        count_step<COUNT>(cnt, pix_steps, tc);
                     }
                     if (!__any(inl && running)) break;
                 }
@@ -653,17 +616,13 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                     running = true;
                     if (!shadow && depth == 0) { /* a camera ray: the pixel's candidate list */
                         const uint32_t lpack = s_list[threadIdx.x];
-                        const uint32_t pc = (lpack & (RT_LIST_MAX - 1u)) + 1u, first = (lpack >> RT_LIST_BITS) << 3;
                         if (lpack == RT_LPACK_EMPTY) {
                             running = false;
                             ts.best = -1;
                             fin = true;
                         } else if (lpack != RT_LPACK_NONE) {
-                            for (uint32_t b = (pc - 1u) >> 3; b > 0u; --b) {
-                                const uint32_t k = pc - 8u * b < 8u ? pc - 8u * b : 8u;
-                                stk.push(~(int)(((first + 8u * b) << 3) | (k - 1u)));
-                            }
-                            ts.node = ~(int)((first << 3) | ((pc < 8u ? pc : 8u) - 1u));
+                            const ListRange lr = list_range(lpack);
+                            ts.node = list_leaves(lr.count, lr.first, [&](int v) { stk.push(v); });
                         }
                     }
                 }
@@ -711,17 +670,10 @@ __global__ __launch_bounds__(RT_BLOCK, RT_TRIS_WAVES) void k_tris(RtTriLaunch a)
                             fin = true;
                             if (COUNT && RT_DIAG_SHCACHE && sc_try) ++cnt[11]; /* (a try only ends a query occluded) */
                         }
-                        if (COUNT) {
-                            cnt[2] += tc.nodes;
-                            cnt[3] += tc.tests;
-                            cnt[4] += tc.leaves;
-                            pix_steps += tc.nodes + tc.leaves;
-                            if (RT_DIAG_RAYSPLIT) {
-                                const int k = shadow ? (tri_hit ? 10 : 11) : (depth == 0 ? 12 : -1);
-                                if (k >= 0) cnt[k] += tc.nodes + tc.leaves;
-                            }
-                        } else {
-                            ++pix_steps; /* (the measured cost, pixel_iter: trav_step calls) */
+                        count_step<COUNT>(cnt, pix_steps, tc);
+                        if (COUNT && RT_DIAG_RAYSPLIT) {
+                            const int k = shadow ? (tri_hit ? 10 : 11) : (depth == 0 ? 12 : -1);
+                            if (k >= 0) cnt[k] += tc.nodes + tc.leaves;
                         }
                     }
                     if (COUNT) ++cnt[5];

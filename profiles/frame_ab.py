@@ -4,7 +4,10 @@ kernel time of --frames frames of the same view (the first --skip dropped: sched
 the frames' bits compared across builds.
 
     python profiles/frame_ab.py LABEL=path.so LABEL= LABEL=?K=V ... [--config bunny|dragon|spheres] [--rounds 3] [--frames 20]
-    (LABEL= with an empty path: the in-tree build; ?K=V+K2=V2 after the path: environment of that child)
+        [--tile STRIPE,N,R]
+    (LABEL= with an empty path: the in-tree build; ?K=V+K2=V2 after the path: environment of that child;
+    --tile: rank R's tile of N ranks' interleaved STRIPE-row stripes, as rayTrace(..., tile=...) takes it — a
+    many-sample tile renders in the sample-split form, reported as split_chunks > 0)
 """
 import argparse
 import hashlib
@@ -42,15 +45,18 @@ def child(args):
     rt.setMaxPathDepth(6)
     Wp, Hp = sc.padded_dims(W, H)
     seeds = sc.default_seeds(Wp, Hp)
-    out = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
+    tile = tuple(int(v) for v in args.tile.split(",")) if args.tile else None
+    rows = H if tile is None else sum(1 for y in range(H) if (y // tile[0]) % tile[1] == tile[2])
+    out = torch.zeros(W * rows * 4, dtype=torch.float32, device="cuda:0")
     ms = []
     for _ in range(args.frames):
         rt.setSeeds(Wp, Hp, seeds)  # every frame the same (progression 0 from the same seeds)
-        rt.rayTrace(out, W, H, 0, kernel=kernel)
+        rt.rayTrace(out, W, H, 0, kernel=kernel, tile=tile)
         ms.append(rt.lastKernelMs())
     h = hashlib.sha1(out.cpu().numpy().tobytes()).hexdigest()
     ms = ms[args.skip:]
-    print(json.dumps({"median_ms": statistics.median(ms), "min_ms": min(ms), "sha1": h}), flush=True)
+    print(json.dumps({"median_ms": statistics.median(ms), "min_ms": min(ms), "sha1": h,
+                      "split_chunks": rt.renderInfo().get("split_chunks", 0)}), flush=True)
 
 
 def main():
@@ -60,6 +66,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--skip", type=int, default=3)
+    ap.add_argument("--tile", default="")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default="")
     args = ap.parse_args()
@@ -75,7 +82,7 @@ def main():
                 k, _, v = kv.partition("=")
                 env[k] = v
             r = subprocess.run([sys.executable, "-u", __file__, "--child", "--lib", path, "--config", args.config,
-                                "--frames", str(args.frames), "--skip", str(args.skip)],
+                                "--frames", str(args.frames), "--skip", str(args.skip), "--tile", args.tile],
                                capture_output=True, text=True, timeout=600, env=env)
             if r.returncode != 0:
                 print(r.stderr[-2000:], file=sys.stderr)
@@ -83,10 +90,11 @@ def main():
             line = json.loads(r.stdout.strip().split("\n")[-1])
             res.setdefault(label, []).append(line)
             print(f"round {rnd + 1} {label}: median {line['median_ms']:.4f} ms min {line['min_ms']:.4f}", flush=True)
-    out = {lab: {"median_ms": statistics.median(x["median_ms"] for x in v), "min_ms": min(x["min_ms"] for x in v)}
+    out = {lab: {"median_ms": statistics.median(x["median_ms"] for x in v), "min_ms": min(x["min_ms"] for x in v),
+                 "round_medians_ms": [x["median_ms"] for x in v], "split_chunks": v[0]["split_chunks"]}
            for lab, v in res.items()}
     out["bit_identical"] = len({x["sha1"] for v in res.values() for x in v}) == 1
-    print(json.dumps({"config": args.config, **out}))
+    print(json.dumps({"config": args.config, "tile": args.tile or None, **out}))
 
 
 if __name__ == "__main__":
