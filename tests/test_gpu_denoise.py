@@ -4,13 +4,12 @@ its argument checks, its effect on a 1-spp frame, and ProgressiveViewHIP::setDen
 rt_render CLI.  Run on the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import features_ref as fr
-from conftest import ROOT, bits
+import view_ref as vr
+from conftest import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -203,26 +202,25 @@ def test_denoise_quality(pt, golden, golden_meta):
 def test_progressive_view_denoise(view, oracle, tmp_path, pt):
     """ProgressiveViewHIP::setDenoise through the rt_render CLI: 4 displays, a key press, 2 more
     displays.  With the denoiser on, rawPixels() of every displayed frame equals pixels() of the
-    same events with it off, bit for bit, and pixels() equals denoise(raw, features)."""
+    same events with it off, bit for bit, and pixels() equals denoise(raw, features), as
+    tests/view_ref.py recomposes it."""
     rt, _ = view
     W, H = 64, 48
-    exe = ROOT / "pathtracer.cl_amd" / "rt_render"
-    common = [str(exe), "--width", str(W), "--height", str(H), "--mesh", "2000", "--events", "d,d,d,d,l,d,d",
-              "--max-progression", "8"]
-    off, on, raw, feats = (tmp_path / n for n in ("off.f32", "on.f32", "raw.f32", "feat.f32"))
-    subprocess.run(common + ["--frames-out", str(off)], check=True, timeout=120, capture_output=True)
-    subprocess.run(common + ["--denoise", "--frames-out", str(on), "--raw-frames-out", str(raw), "--features-out",
-                             str(feats)], check=True, timeout=120, capture_output=True)
+    events = "d,d,d,d,l,d,d"
+    common = ["--mesh", "2000", "--events", events, "--max-progression", "8"]
+    flags = vr.Flags(denoise=True)
+    off = vr.run_view(tmp_path, common, ("shown",))
+    on = vr.run_view(tmp_path, common + flags.cli())
     px = W * H * 4
-    f_off, f_on, f_raw, f_feat = (np.fromfile(p, np.float32) for p in (off, on, raw, feats))
+    f_off, f_on, f_raw, f_feat = off["shown"], on["shown"], on["raw"], on["feat"]
     assert f_off.size == 6 * px and f_on.size == 6 * px and f_raw.size == 6 * px and f_feat.size == 12 * px
     assert np.array_equal(bits(f_raw), bits(f_off))
     assert not np.array_equal(bits(f_on), bits(f_off))
+    assert [l["progression"] for l in on["lines"] if l.get("rendered")] == [0, 1, 2, 3, 1, 2]
     feat_views = [f_feat[2 * px * k:2 * px * (k + 1)] for k in range(6)]
     assert np.array_equal(bits(feat_views[0]), bits(feat_views[3]))      # one view ...
     assert not np.array_equal(bits(feat_views[3]), bits(feat_views[4]))  # ... the key press moved the camera
-    for k in range(6):
-        src = np.ascontiguousarray(f_raw[px * k:px * (k + 1)])
-        out = np.zeros(px, np.float32)
-        rt.denoise(src, np.ascontiguousarray(feat_views[k]), out, W, H)
+    exp = vr.displayed(rt, pt.scenes, flags, events, f_raw, f_feat, W, H, max_progression=8)
+    assert len(exp.frames) == 6
+    for k, out in enumerate(exp.frames):
         assert np.array_equal(bits(out), bits(f_on[px * k:px * (k + 1)])), f"displayed frame {k}"

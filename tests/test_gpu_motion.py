@@ -5,23 +5,21 @@ vacuous; ProgressiveViewHIP::setMotionCarry through the rt_render CLI; and its e
 of 1-spp frames.  Run on the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
-import json
-import subprocess
-
 import numpy as np
 import pytest
 
 import features_ref as fr
 import motion_ref as mr
 import refit_ref as rr
+import render_state as rs
 import temporal_ref as tr
 import tree_cases as tc
-from conftest import ROOT, bits
+import view_ref as vr
+from conftest import bits
 from test_motion_host import small_move
 
 pytestmark = pytest.mark.gpu
 
-CASE = "tris_64x48_sr1"
 F = np.float32
 TARGET = (0.0, -4.0, 0.0)
 EL0, AZ0, DIST = 40.0, 105.0, 5.0  # the golden view
@@ -237,76 +235,33 @@ def test_warp_argument_checks(pt, rt, mesh, moved):
 
 
 def test_render_state_untouched(pt, golden, golden_meta):
-    """tests/test_gpu_temporal.py's test of the same name with the new calls: the golden progressive
-    frames with rt_warp_features and rt_mesh_pose in between — device tensors on a side stream behind a
-    render enqueued without a wait, host buffers on the context's stream — are the frames, seeds,
-    counter totals, render info and rt_read of the sequence without them."""
+    """The golden progressive frames with rt_warp_features and rt_mesh_pose in between — device tensors
+    on a side stream behind a render enqueued without a wait, host buffers on the context's stream — are
+    the frames, seeds, counter totals, render info and rt_read of the sequence without them
+    (tests/render_state.py)."""
     import torch
 
-    g, m = golden(CASE), golden_meta["cases"][CASE]
-    W, H = m["W"], m["H"]
-    verts, idx = g["verts"], g["idx"]
-
-    def tracer():
-        t = pt.RayTracer(0)
-        t.setSpheres(g["spheres"].view(pt._abi.SPHERE_DTYPE))
-        t.setCamera(g["camera"])
-        t.setSampleRate(m["sample_rate"])
-        t.setMaxPathDepth(m["max_depth"])
-        t.setNDRange(m["nd_y"])
-        t.setMesh(verts, idx)
-        t.setSeeds(m["Wpad"], m["Hpad"], g["seeds_in"])
-        t.setCounting(True)
-        return t
-
-    def totals(t):
-        c = t.counterTotals()
-        return {k: v for k, v in c.items() if "clocks" not in k and k != "lane_slots"}
-
-    def info(t):
-        return {k: v for k, v in t.renderInfo().items() if k != "schedule_host_ms"}
-
-    plain = tracer()
-    frame = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
-    for p in range(m["frames"]):
-        plain.rayTrace(frame, W, H, p, kernel=2, sync=False)
-    plain.synchronize()
-    exp_totals, exp_seeds, exp_ms, exp_info = totals(plain), plain.getSeeds(), plain.lastKernelMs(), info(plain)
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    plain.close()
-
-    t = tracer()
-    feat = np.zeros(2 * W * H * 4, F)
-    t.renderFeatures(feat, W, H, kernel=2)
-    prev = rr.shrink(verts)
-    exp = mr.warp(feat, idx, verts, prev)
-    frame.zero_()
-    dfeat, dprev = torch.from_numpy(feat).cuda(), torch.from_numpy(prev).cuda()
-    douts = [torch.zeros_like(dfeat) for _ in range(m["frames"])]
-    host_out = np.zeros_like(feat)
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    for p in range(m["frames"]):
-        t.rayTrace(frame, W, H, p, kernel=2, sync=False)
-        t.warpFeatures(dfeat, dprev, douts[p], W, H, stream=side.cuda_stream, sync=False)
-        if p == 1:  # and host buffers on the context's own stream
-            t.warpFeatures(feat, prev, host_out, W, H)
-            assert np.array_equal(bits(t.meshPose()), bits(verts))
-    t.synchronize()
-    torch.cuda.synchronize()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    back = np.zeros(W * H * 4, F)
-    t.read(back)
-    assert np.array_equal(bits(back), bits(g["frames"][-1]))
-    assert np.array_equal(t.getSeeds(), exp_seeds) and np.array_equal(exp_seeds, g["seeds_out"])
-    got_totals = totals(t)
-    assert got_totals == exp_totals and got_totals["renders"] == m["frames"] and got_totals["rays_closest"] > 0
-    assert (t.lastKernelMs() > 0.0) == (exp_ms > 0.0)
-    assert info(t) == exp_info
+    with rs.untouched(pt, golden, golden_meta) as (t, frame, g, m):
+        W, H = m["W"], m["H"]
+        verts, idx = g["verts"], g["idx"]
+        feat = np.zeros(2 * W * H * 4, F)
+        t.renderFeatures(feat, W, H, kernel=2)
+        prev = rr.shrink(verts)
+        exp = mr.warp(feat, idx, verts, prev)
+        dfeat, dprev = torch.from_numpy(feat).cuda(), torch.from_numpy(prev).cuda()
+        douts = [torch.zeros_like(dfeat) for _ in range(m["frames"])]
+        host_out = np.zeros_like(feat)
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        for p in range(m["frames"]):
+            t.rayTrace(frame, W, H, p, kernel=2, sync=False)
+            t.warpFeatures(dfeat, dprev, douts[p], W, H, stream=side.cuda_stream, sync=False)
+            if p == 1:  # and host buffers on the context's own stream
+                t.warpFeatures(feat, prev, host_out, W, H)
+                assert np.array_equal(bits(t.meshPose()), bits(verts))
     for d in douts:
         assert np.array_equal(bits(d.cpu().numpy()), bits(exp))
     assert np.array_equal(bits(host_out), bits(exp))
-    t.close()
 
 
 def test_not_vacuous(rt, mesh, moved):
@@ -355,62 +310,42 @@ SHOWN = [(0, AZ0, 0), (0, AZ0, 1), (1, AZ0, 1), (2, AZ0 + 3.0, 1), (2, AZ0 + 3.0
 def test_progressive_view_motion_carry(denoise, rt, pt, mesh, tmp_path):
     """ProgressiveViewHIP::setMotionCarry through the rt_render CLI: two displays, a mesh update, a
     display, another update and a key press, two displays.  With --motion-carry every displayed frame is
-    the recomposition of warpFeatures / reproject / temporalMerge (/ denoise) through the Python API;
-    without it the history is dropped at every update, as before; the accumulation buffers of both runs
-    are the same; and the runs differ exactly from the first display after an update on."""
+    the recomposition of warpFeatures / reproject / temporalMerge (/ denoise) through the Python API
+    (tests/view_ref.py); without it the history is dropped at every update, as before; the accumulation
+    buffers of both runs are the same; and the runs differ exactly from the first display after an
+    update on."""
     W, H = 64, 48
     px = W * H * 4
     verts, idx = mesh
-    poses = [verts, small_move(verts), rr.wobble(verts)]
+    poses = np.stack([verts, small_move(verts), rr.wobble(verts)]).astype(F)
     pfile = tmp_path / "poses.f32"
-    np.concatenate([p.reshape(-1) for p in poses]).astype(F).tofile(pfile)
-    exe = ROOT / "pathtracer.cl_amd" / "rt_render"
-    common = [str(exe), "--width", str(W), "--height", str(H), "--mesh", "2000", "--poses", str(pfile), "--events", EVENTS,
-              "--temporal"] + (["--denoise"] if denoise else [])
+    poses.tofile(pfile)
+    flags = vr.Flags(temporal=True, denoise=denoise, motion_carry=True)
+    variants = {"off": flags.without("motion_carry"), "on": flags}
     runs = {}
-    for name, extra in (("off", []), ("on", ["--motion-carry"])):
-        files = {k: tmp_path / f"{name}_{k}.f32" for k in ("shown", "raw", "feat")}
-        r = subprocess.run(common + extra + ["--frames-out", str(files["shown"]), "--raw-frames-out", str(files["raw"]),
-                                             "--features-out", str(files["feat"])], check=True, timeout=120, capture_output=True,
-                           text=True)
-        runs[name] = {k: np.fromfile(f, F) for k, f in files.items()}
-        lines = [json.loads(l) for l in r.stdout.splitlines()]
+    for name, fl in variants.items():
+        runs[name] = run = vr.run_view(tmp_path, ["--mesh", "2000", "--poses", str(pfile), "--events", EVENTS] + fl.cli())
+        lines = run["lines"]
         ups = [l for l in lines if l.get("event", "").startswith("p:")]
         assert len(ups) == 2 and all(l["mesh_update"] in ("refit", "rebuilt") and l["progression"] == 0 for l in ups)
         assert all("mesh_update" not in l for l in lines if l not in ups)
+        pose, seen = 0, []
+        for l in lines:
+            if l in ups:
+                pose = int(l["event"][2:])
+            if l.get("rendered"):
+                seen.append((pose, l["azimuth"], l["progression"]))
+        assert seen == SHOWN
     on, off = runs["on"], runs["off"]
     assert on["shown"].size == off["shown"].size == on["raw"].size == len(SHOWN) * px and on["feat"].size == 2 * len(SHOWN) * px
     assert np.array_equal(bits(on["raw"]), bits(off["raw"])) and np.array_equal(bits(on["feat"]), bits(off["feat"]))
     for name, run in runs.items():
-        hist = hl = pfeat = pcam = None
-        for k, (pose, az, prog) in enumerate(SHOWN):
-            cur = np.ascontiguousarray(run["raw"][px * k:px * (k + 1)])
-            feat = np.ascontiguousarray(run["feat"][2 * px * k:2 * px * (k + 1)])
-            cam = pt.scenes.camera_spherical(W, target=TARGET, elevation=EL0, azimuth=az, distance=DIST)
-            new_pose = k > 0 and pose != SHOWN[k - 1][0]
-            new_view = k > 0 and (new_pose or az != SHOWN[k - 1][1])
-            if hist is None or (new_pose and name == "off"):  # no history, or dropped with the old geometry
-                car, cl = np.zeros(px, F), np.zeros(W * H, F)
-            elif new_view:
-                car, cl = np.zeros(px, F), np.zeros(W * H, F)
-                cfeat, cap = feat, 32.0
-                if new_pose:  # the features in the pose the kept frame was displayed in
-                    rt.setMesh(verts, idx)
-                    rt.updateMesh(poses[pose])
-                    cfeat = np.zeros_like(feat)
-                    rt.warpFeatures(feat, poses[SHOWN[k - 1][0]], cfeat, W, H)
-                    cap = min(32.0, MOTION_CAP)
-                rt.reproject(hist, hl, pfeat, pcam, cfeat, car, cl, W, H, max_history=cap)
-            hist, hl = np.zeros(px, F), np.zeros(W * H, F)
-            rt.temporalMerge(car, cl, cur, max(prog, 1), hist, hl, W, H)
-            disp = hist
-            if denoise:
-                disp = np.zeros(px, F)
-                rt.denoise(hist, feat, disp, W, H)
+        exp = vr.displayed(rt, pt.scenes, variants[name], EVENTS, run["raw"], run["feat"], W, H, mesh=mesh, poses=poses)
+        assert len(exp.frames) == len(SHOWN)
+        for k, disp in enumerate(exp.frames):
             assert np.array_equal(bits(run["shown"][px * k:px * (k + 1)]), bits(disp)), f"{name}: displayed frame {k}"
-            pfeat, pcam = feat, cam
         if name == "on":
-            assert (hl > 2).mean() > 0.3  # the last view's two frames on top of what was carried into it
+            assert (exp.lengths[-1] > 2).mean() > 0.3  # the last view's two frames on top of what was carried into it
     for k in range(len(SHOWN)):
         same = np.array_equal(bits(on["shown"][px * k:px * (k + 1)]), bits(off["shown"][px * k:px * (k + 1)]))
         assert same == (k < 2), f"displayed frame {k} against the run without --motion-carry"

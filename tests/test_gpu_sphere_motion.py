@@ -6,8 +6,7 @@ dragged sphere of 1-spp frames.  Run on the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
 import ctypes
-import json
-import subprocess
+from dataclasses import replace
 
 import numpy as np
 import pytest
@@ -16,7 +15,7 @@ import features_ref as fr
 import sphere_motion_ref as sm
 import temporal_ref as tr
 import view_ref as vr
-from conftest import ROOT, bits
+from conftest import bits
 from test_sphere_motion_host import MOVES, moved_scene
 
 pytestmark = pytest.mark.gpu
@@ -277,148 +276,6 @@ VIEW_FLAGS = {
 }
 
 
-def recompose(rt, scenes, fl: vr.Flags, sphere_carry, events, raw, feats, width, height, spheres0, cap=SPHERE_CAP):
-    """The frames `rt_render --events` displayed in a sphere view, in order: view_ref.displayed's state
-    machine (the header's, event by event) with the o event and setSphereCarry, the stages run on `rt`.
-    Until the first key press the camera is the one the application set (main.cpp's)."""
-    w, h = width, height
-    az, el, orbiting = F(105.0), F(40.0), False
-    realloc, progression = True, 0
-    feat_dirty, carry, have_hist, mom_valid = True, False, False, False
-    spheres_pending, shown_valid, shown_spheres = False, False, None
-    feat = hist_cam = colour = moments = mom = last_raw = None
-    cur_spheres = spheres0.copy()
-    offsets = np.zeros((len(spheres0), 4), F)  # the o events so far, summed in float32 as the CLI does
-    taken = [0, 0]
-    shown = []
-
-    def restart():
-        nonlocal progression, carry
-        progression, carry = 0, True
-
-    def drop():
-        nonlocal have_hist, spheres_pending, mom_valid
-        have_hist = spheres_pending = mom_valid = False
-
-    def trace():
-        nonlocal feat, feat_dirty, carry, have_hist, mom_valid, spheres_pending, hist_cam, colour, moments, mom, last_raw
-        nonlocal shown_valid, shown_spheres
-        px = w * h
-        cur = np.ascontiguousarray(raw[taken[0]:taken[0] + 4 * px])
-        feat_now = np.ascontiguousarray(feats[taken[1]:taken[1] + 8 * px])
-        assert cur.size == 4 * px and feat_now.size == 8 * px, "the run displayed fewer frames than its events say"
-        taken[0] += 4 * px
-        taken[1] += 8 * px
-        n = max(progression, 1)
-        if fl.variance_guided:
-            n_mom = n if mom_valid else 1
-            new = np.zeros(4 * px, F)
-            rt.momentsAccumulate(last_raw if n_mom > 1 else None, cur, n_mom, mom if n_mom > 1 else None, new, w, h)
-            mom, mom_valid = new, True
-        hist_feat = feat
-        if feat_dirty:
-            carry = True
-            feat, feat_dirty = feat_now, False
-        else:
-            assert np.array_equal(bits(feat), bits(feat_now))
-        active = [(colour, cur)] + ([(moments, mom)] if fl.variance_guided else [])
-        if orbiting:
-            cam = scenes.camera_spherical(w, target=vr.TARGET, elevation=float(el), azimuth=float(az), distance=5.0)
-        else:
-            cam = scenes.camera_spherical(w, **scenes.MAIN_CAMERA)
-        judged = fl.history_trust and have_hist
-        if not have_hist:
-            for hs, _ in active:
-                hs.carried[:], hs.carried_len[:] = 0.0, 0.0
-        elif carry:
-            cur_feat, hcap = feat, fl.max_history
-            if spheres_pending:
-                rt.setSpheres(cur_spheres)
-                cur_feat = np.zeros_like(feat)
-                rt.warpFeaturesSpheres(feat, shown_spheres, cur_feat, w, h)
-                hcap = min(fl.max_history, cap)
-            for hs, _ in active:
-                rt.reproject(hs.kept, colour.kept_len, hist_feat, hist_cam, cur_feat, hs.carried, hs.carried_len, w, h,
-                             max_history=hcap)
-        spheres_pending = carry = False
-        trusted = None
-        if judged:
-            trusted = np.zeros(px, F)
-            rt.historyTrust(colour.carried, colour.carried_len, cur, n, feat, trusted, w, h, tolerance=fl.tolerance)
-        for hs, src in active:
-            hs.kept, hs.kept_len = np.zeros(4 * px, F), np.zeros(px, F)
-            rt.temporalMerge(hs.carried, trusted if judged else hs.carried_len, src, n, hs.kept, hs.kept_len, w, h,
-                             max_history=fl.max_history)
-        hist_cam, have_hist = cam, True
-        disp = colour.kept
-        if fl.variance_guided:
-            var, out = np.zeros(px, F), np.zeros(4 * px, F)
-            rt.variance(disp, moments.kept, colour.kept_len, feat, var, w, h)
-            rt.denoiseVar(disp, var, feat, out, None, w, h, sigma_lum=fl.sigma_lum)
-            disp = out
-        elif fl.denoise:
-            out = np.zeros(4 * px, F)
-            rt.denoise(disp, feat, out, w, h, iterations=fl.iterations)
-            disp = out
-        last_raw = cur
-        shown.append(disp)
-        if sphere_carry:
-            shown_spheres, shown_valid = cur_spheres.copy(), True
-
-    for ev in filter(None, events.split(",")):
-        kind, args = ev[0], ev.split(":")[1:]
-        if ev == "d":
-            if realloc:
-                colour, moments = vr._History(w * h), vr._History(w * h)
-                feat = mom = last_raw = None
-                feat_dirty = True
-                drop()
-                progression, realloc = 0, False
-                trace()
-            else:
-                progression += 1
-                trace()
-        elif ev == "l":
-            az, orbiting = np.fmod(F(az + F(3)), F(360.0)), True
-            feat_dirty = True
-            restart()
-        elif kind == "s":
-            w, h = int(args[0]), int(args[1])
-            realloc = True
-        elif kind == "o":
-            i = int(args[0])
-            d = np.array([float(a) for a in args[1:]] + [0.0] * (5 - len(args)), F)
-            offsets[i] = offsets[i] + d
-            cur_spheres = spheres0.copy()
-            for j in np.flatnonzero((offsets != 0).any(axis=1)):
-                cur_spheres["center"][j] = spheres0["center"][j] + offsets[j, :3]
-                cur_spheres["radius"][j] = spheres0["radius"][j] + offsets[j, 3]
-            carry_spheres = sphere_carry and have_hist and shown_valid and not realloc
-            feat_dirty = True
-            if carry_spheres:
-                spheres_pending = True
-            elif not fl.history_trust:
-                drop()
-            restart()
-            if not carry_spheres and not fl.history_trust:
-                carry = False
-        else:
-            raise ValueError(f"event {ev!r}")
-    assert taken == [raw.size, feats.size], "the run displayed more frames than its events say"
-    return shown
-
-
-def run_view(tmp_path, name, args, outputs=("shown", "raw", "feat")):
-    flag = {"shown": "--frames-out", "raw": "--raw-frames-out", "feat": "--features-out", "f8": "--frames8-out"}
-    files = {k: tmp_path / f"{name}_{k}" for k in outputs}
-    cmd = [str(ROOT / "pathtracer.cl_amd" / "rt_render"), "--width", str(VW), "--height", str(VH)] + args
-    for k in outputs:
-        cmd += [flag[k], str(files[k])]
-    r = subprocess.run(cmd, check=True, timeout=120, capture_output=True, text=True)
-    lines = [json.loads(l) for l in r.stdout.splitlines()]
-    return {k: np.fromfile(f, np.uint32 if k == "f8" else F) for k, f in files.items()}, lines
-
-
 @pytest.mark.parametrize("flags", list(VIEW_FLAGS))
 def test_view_sphere_carry(flags, rt, pt, tmp_path):
     """Two displays, a move of sphere 2, two displays, moves of spheres 2 and 0 (the oldest list is the
@@ -433,27 +290,30 @@ def test_view_sphere_carry(flags, rt, pt, tmp_path):
     outputs = ("shown", "raw", "feat") + (("f8",) if tone else ())
     spheres0 = moved_scene(pt, {})
     px = VW * VH * 4
+    variants = {"off": fl, "on": replace(fl, sphere_carry=True)}
     runs = {}
-    for name, carry_args in (("off", []), ("on", ["--sphere-carry"])):
-        runs[name], lines = run_view(tmp_path, name, ["--events", EVENTS] + fl.cli() + extra + carry_args, outputs)
+    for name, v in variants.items():
+        runs[name] = vr.run_view(tmp_path, ["--events", EVENTS] + v.cli() + extra, outputs, VW, VH)
+        lines = runs[name]["lines"]
         moves = [l for l in lines if l.get("event", "").startswith("o:")]
         assert len(moves) == 3 and all(l["progression"] == 0 and not l["rendered"] for l in moves)
-        assert sum(1 for l in lines if l.get("rendered")) == N_SHOWN
+        sizes = [(l["width"], l["height"]) for l in lines if l.get("rendered")]
+        assert sizes == [(VW, VH)] * 6 + [(48, 40)]
     on, off = runs["on"], runs["off"]
     total = 6 * px + 48 * 40 * 4
     assert on["shown"].size == off["shown"].size == on["raw"].size == total and on["feat"].size == 2 * total
     assert np.array_equal(bits(on["raw"]), bits(off["raw"])) and np.array_equal(bits(on["feat"]), bits(off["feat"]))
     try:
         for name, run in runs.items():
-            exp = recompose(rt, pt.scenes, fl, name == "on", EVENTS, run["raw"], run["feat"], VW, VH, spheres0)
+            exp = vr.displayed(rt, pt.scenes, variants[name], EVENTS, run["raw"], run["feat"], VW, VH, spheres0=spheres0).frames
             assert len(exp) == N_SHOWN
             at = at8 = 0
             exposure = np.zeros(1, F)
-            for k, e in enumerate(exp):
+            for k, (e, (w, h)) in enumerate(zip(exp, sizes)):
                 assert np.array_equal(bits(run["shown"][at:at + e.size]), bits(e)), f"{name}: displayed frame {k}"
                 if tone:  # the last stage reads what is shown; the exposure starts afresh at the reshape
-                    w, h = (VW, VH) if k < 6 else (48, 40)
-                    if k == 6:
+                    assert e.size == 4 * w * h
+                    if k and sizes[k - 1] != (w, h):
                         exposure[:] = 0.0
                     out8 = np.zeros(w * h, np.uint32)
                     rt.meterExposure(e, exposure, w, h)
@@ -473,10 +333,10 @@ def test_view_tris_unchanged(flags, tmp_path):
     with and without --sphere-carry."""
     fl, extra = VIEW_FLAGS[flags]
     outputs = ("shown", "raw") + (("f8",) if "--tonemap" in extra else ())
-    args = ["--mesh", "2000", "--events", "d,d,e:0.3:0:0,d,d"] + fl.cli() + extra
-    off, lines_off = run_view(tmp_path, "off", args, outputs)
-    on, lines_on = run_view(tmp_path, "on", args + ["--sphere-carry"], outputs)
-    assert lines_on == lines_off
+    args = ["--mesh", "2000", "--events", "d,d,e:0.3:0:0,d,d"] + extra
+    off = vr.run_view(tmp_path, args + fl.cli(), outputs, VW, VH)
+    on = vr.run_view(tmp_path, args + replace(fl, sphere_carry=True).cli(), outputs, VW, VH)
+    assert on["lines"] == off["lines"]
     for k in outputs:
         assert on[k].size and np.array_equal(on[k].view(np.uint32), off[k].view(np.uint32)), k
 

@@ -5,14 +5,14 @@ render's state alone; ProgressiveViewHIP::setTemporal through the rt_render CLI;
 an orbit of 1-spp frames.  Run on the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import features_ref as fr
+import render_state as rs
 import temporal_ref as tr
-from conftest import ROOT, bits
+import view_ref as vr
+from conftest import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -359,71 +359,32 @@ def test_not_vacuous(rt, pt):
 def test_render_state_untouched(pt, golden, golden_meta, views):
     """The golden progressive frames with reproject / merge calls in between — host buffers on the
     context's stream, device tensors on a side stream behind a render enqueued without a wait — are
-    the frames, seeds and counter totals of the sequence without those calls; and the side-stream
-    merge saw the frame of the render before it, not the one enqueued after it."""
+    the frames, seeds, counter totals and render info of the sequence without those calls
+    (tests/render_state.py); and the side-stream merge saw the frame of the render before it, not the
+    one enqueued after it."""
     import torch
 
-    g, m = golden(CASE), golden_meta["cases"][CASE]
-    W, H = m["W"], m["H"]
-
-    def tracer():
-        t = pt.RayTracer(0)
-        t.setSpheres(g["spheres"].view(pt._abi.SPHERE_DTYPE))
-        t.setCamera(g["camera"])
-        t.setSampleRate(m["sample_rate"])
-        t.setMaxPathDepth(m["max_depth"])
-        t.setNDRange(m["nd_y"])
-        t.setMesh(g["verts"], g["idx"])
-        t.setSeeds(m["Wpad"], m["Hpad"], g["seeds_in"])
-        t.setCounting(True)
-        return t
-
-    def totals(t):
-        """The counter totals that count work: the clock readings, and the lane slots of the wave
-        schedule, vary from one run of the same sequence to the next."""
-        c = t.counterTotals()
-        return {k: v for k, v in c.items() if "clocks" not in k and k != "lane_slots"}
-
-    plain = tracer()
-    frame = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
-    for p in range(m["frames"]):
-        plain.rayTrace(frame, W, H, p, kernel=2, sync=False)
-    plain.synchronize()
-    exp_totals, exp_seeds, exp_ms = totals(plain), plain.getSeeds(), plain.lastKernelMs()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    plain.close()
-
-    pcam, pfeat = views(W, H, EL0, AZ0)
-    _, cfeat = views(W, H, EL0, AZ0 + 3.0)
-    col, ln = _history(W, H, 13)
-    car, cl = tr.reproject(col, ln, pfeat, pcam, cfeat, W, H)
-    t = tracer()
-    frame.zero_()
-    dcol, dln, dpf, dcf = (torch.from_numpy(a).cuda() for a in (col, ln, pfeat, cfeat))
-    dcar, dcl = torch.zeros_like(dcol), torch.zeros_like(dln)
-    merged = [(torch.zeros_like(dcol), torch.zeros_like(dln)) for _ in range(m["frames"])]
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    host_out, host_len = np.zeros_like(col), np.zeros_like(ln)
-    for p in range(m["frames"]):
-        t.rayTrace(frame, W, H, p, kernel=2, sync=False)
-        if p == 0:
-            t.reproject(dcol, dln, dpf, pcam, dcf, dcar, dcl, W, H, stream=side.cuda_stream, sync=False)
-        t.temporalMerge(dcar, dcl, frame, max(p, 1), merged[p][0], merged[p][1], W, H, stream=side.cuda_stream,
-                        sync=False)
-        if p == 1:  # and host buffers on the context's own stream
-            t.reproject(col, ln, pfeat, pcam, cfeat, host_out, host_len, W, H)
-            t.temporalMerge(host_out, host_len, g["frames"][0], 1.0, host_out, host_len, W, H)
-    t.synchronize()
-    torch.cuda.synchronize()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    back = np.zeros(W * H * 4, F)
-    t.read(back)
-    assert np.array_equal(bits(back), bits(g["frames"][-1]))
-    assert np.array_equal(t.getSeeds(), exp_seeds) and np.array_equal(exp_seeds, g["seeds_out"])
-    got_totals = totals(t)
-    assert got_totals == exp_totals and got_totals["renders"] == m["frames"] and got_totals["rays_closest"] > 0
-    assert (t.lastKernelMs() > 0.0) == (exp_ms > 0.0)
+    with rs.untouched(pt, golden, golden_meta) as (t, frame, g, m):
+        W, H = m["W"], m["H"]
+        pcam, pfeat = views(W, H, EL0, AZ0)
+        _, cfeat = views(W, H, EL0, AZ0 + 3.0)
+        col, ln = _history(W, H, 13)
+        car, cl = tr.reproject(col, ln, pfeat, pcam, cfeat, W, H)
+        dcol, dln, dpf, dcf = (torch.from_numpy(a).cuda() for a in (col, ln, pfeat, cfeat))
+        dcar, dcl = torch.zeros_like(dcol), torch.zeros_like(dln)
+        merged = [(torch.zeros_like(dcol), torch.zeros_like(dln)) for _ in range(m["frames"])]
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        host_out, host_len = np.zeros_like(col), np.zeros_like(ln)
+        for p in range(m["frames"]):
+            t.rayTrace(frame, W, H, p, kernel=2, sync=False)
+            if p == 0:
+                t.reproject(dcol, dln, dpf, pcam, dcf, dcar, dcl, W, H, stream=side.cuda_stream, sync=False)
+            t.temporalMerge(dcar, dcl, frame, max(p, 1), merged[p][0], merged[p][1], W, H, stream=side.cuda_stream,
+                            sync=False)
+            if p == 1:  # and host buffers on the context's own stream
+                t.reproject(col, ln, pfeat, pcam, cfeat, host_out, host_len, W, H)
+                t.temporalMerge(host_out, host_len, g["frames"][0], 1.0, host_out, host_len, W, H)
     assert np.array_equal(bits(dcar.cpu().numpy()), bits(car)) and np.array_equal(bits(dcl.cpu().numpy()), bits(cl))
     for p in range(m["frames"]):
         exp, el = tr.merge(car, cl, g["frames"][p], max(p, 1))
@@ -431,7 +392,6 @@ def test_render_state_untouched(pt, golden, golden_meta, views):
         assert np.array_equal(bits(merged[p][1].cpu().numpy()), bits(el))
     exp, el = tr.merge(car, cl, g["frames"][0], 1.0)
     assert np.array_equal(bits(host_out), bits(exp)) and np.array_equal(bits(host_len), bits(el))
-    t.close()
 
 
 @pytest.mark.parametrize("denoise", [False, True])
@@ -439,49 +399,30 @@ def test_progressive_view_temporal(denoise, rt, pt, tmp_path):
     """ProgressiveViewHIP::setTemporal through the rt_render CLI: two displays, a key press, one
     display, a key press, three displays.  The accumulation buffer of every displayed frame is that
     of the run without --temporal; every displayed frame is the recomposition of reproject /
-    temporalMerge (/ denoise) through the Python API; the display differs from the run without
-    --temporal from the second view on, and only there."""
+    temporalMerge (/ denoise) through the Python API (tests/view_ref.py); the display differs from the
+    run without --temporal from the second view on, and only there."""
     W, H = 64, 48
     px = W * H * 4
-    exe = ROOT / "pathtracer.cl_amd" / "rt_render"
-    common = [str(exe), "--width", str(W), "--height", str(H), "--mesh", "2000", "--events", "d,d,l,d,l,d,d,d"]
-    den = ["--denoise"] if denoise else []
-    plain, off, on, raw, feats = (tmp_path / n for n in ("plain.f32", "off.f32", "on.f32", "raw.f32", "feat.f32"))
-    subprocess.run(common + den + ["--frames-out", str(off)], check=True, timeout=120, capture_output=True)
-    subprocess.run(common + den + ["--temporal", "--frames-out", str(on), "--raw-frames-out", str(raw),
-                                   "--features-out", str(feats)], check=True, timeout=120, capture_output=True)
-    if denoise:
-        subprocess.run(common + ["--frames-out", str(plain)], check=True, timeout=120, capture_output=True)
-    else:
-        plain = off
-    f_plain, f_off, f_on, f_raw, f_feat = (np.fromfile(p, F) for p in (plain, off, on, raw, feats))
-    assert f_plain.size == f_off.size == f_on.size == f_raw.size == 6 * px and f_feat.size == 12 * px
-    assert np.array_equal(bits(f_raw), bits(f_plain))
+    events = "d,d,l,d,l,d,d,d"
+    flags = vr.Flags(temporal=True, denoise=denoise)
+    common = ["--mesh", "2000", "--events", events]
+    off = vr.run_view(tmp_path, common + flags.without("temporal").cli(), ("shown",))
+    on = vr.run_view(tmp_path, common + flags.cli())
+    plain = vr.run_view(tmp_path, common, ("shown",)) if denoise else off
+    assert plain["shown"].size == off["shown"].size == on["shown"].size == on["raw"].size == 6 * px and on["feat"].size == 12 * px
+    assert np.array_equal(bits(on["raw"]), bits(plain["shown"]))
     # (view's azimuth, progression) of the six displayed frames: display() renders progression 0 only
     # after a (re)allocation; after a restart it counts on from 1, whose mix overwrites the buffer
     shown = [(AZ0, 0), (AZ0, 1), (AZ0 + 3.0, 1), (AZ0 + 6.0, 1), (AZ0 + 6.0, 2), (AZ0 + 6.0, 3)]
-    hist = hl = pfeat = pcam = None
-    for k, (az, prog) in enumerate(shown):
-        cur = np.ascontiguousarray(f_raw[px * k:px * (k + 1)])
-        feat = np.ascontiguousarray(f_feat[2 * px * k:2 * px * (k + 1)])
-        cam = pt.scenes.camera_spherical(W, target=TARGET, elevation=EL0, azimuth=az, distance=DIST)
-        if hist is None:
-            car, cl = np.zeros(px, F), np.zeros(W * H, F)
-        elif az != shown[k - 1][0]:  # the first display of a new view
-            car, cl = np.zeros(px, F), np.zeros(W * H, F)
-            rt.reproject(hist, hl, pfeat, pcam, feat, car, cl, W, H)
-        hist, hl = np.zeros(px, F), np.zeros(W * H, F)
-        rt.temporalMerge(car, cl, cur, max(prog, 1), hist, hl, W, H)
-        disp = hist
-        if denoise:
-            disp = np.zeros(px, F)
-            rt.denoise(hist, feat, disp, W, H)
-        got = f_on[px * k:px * (k + 1)]
+    assert [(l["azimuth"], l["progression"]) for l in on["lines"] if l.get("rendered")] == shown
+    exp = vr.displayed(rt, pt.scenes, flags, events, on["raw"], on["feat"], W, H)
+    assert len(exp.frames) == 6
+    for k, disp in enumerate(exp.frames):
+        got = on["shown"][px * k:px * (k + 1)]
         assert np.array_equal(bits(got), bits(disp)), f"displayed frame {k}"
-        same = np.array_equal(bits(got), bits(f_off[px * k:px * (k + 1)]))
+        same = np.array_equal(bits(got), bits(off["shown"][px * k:px * (k + 1)]))
         assert same == (k < 2), f"displayed frame {k} against the run without --temporal"
-        pfeat, pcam = feat, cam
-    assert (hl > 3).mean() > 0.8  # three frames of this view, and what the two views before it left
+    assert (exp.lengths[-1] > 3).mean() > 0.8  # three frames of this view, and what the two views before it left
 
 
 def test_temporal_quality(rt, pt, golden_meta):

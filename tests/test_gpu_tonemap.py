@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import render_state as rs
 import tonemap_ref as tm
 import view_ref as vr
 from conftest import ROOT, bits
@@ -347,78 +348,35 @@ def test_argument_checks(pt, rt):
 
 
 def test_render_state_untouched(pt, golden, golden_meta, oracle):
-    """tests/test_gpu_trust.py's test of the same name with the new calls: the golden progressive frames
-    with rt_meter_exposure and rt_tonemap in between — device tensors on a side stream behind a render
-    enqueued without a wait, host buffers on the context's stream — are the frames, seeds, counter
-    totals, render info and rt_read of the sequence without them."""
+    """The golden progressive frames with rt_meter_exposure and rt_tonemap in between — device tensors on
+    a side stream behind a render enqueued without a wait, host buffers on the context's stream — are
+    the frames, seeds, counter totals, render info and rt_read of the sequence without them
+    (tests/render_state.py)."""
     import torch
 
-    g, m = golden(CASE), golden_meta["cases"][CASE]
-    W, H = m["W"], m["H"]
-
-    def tracer():
-        t = pt.RayTracer(0)
-        t.setSpheres(g["spheres"].view(pt._abi.SPHERE_DTYPE))
-        t.setCamera(g["camera"])
-        t.setSampleRate(m["sample_rate"])
-        t.setMaxPathDepth(m["max_depth"])
-        t.setNDRange(m["nd_y"])
-        t.setMesh(g["verts"], g["idx"])
-        t.setSeeds(m["Wpad"], m["Hpad"], g["seeds_in"])
-        t.setCounting(True)
-        return t
-
-    def totals(t):
-        c = t.counterTotals()
-        return {k: v for k, v in c.items() if "clocks" not in k and k != "lane_slots"}
-
-    def info(t):
-        return {k: v for k, v in t.renderInfo().items() if k != "schedule_host_ms"}
-
-    plain = tracer()
-    frame = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
-    for p in range(m["frames"]):
-        plain.rayTrace(frame, W, H, p, kernel=2, sync=False)
-    plain.synchronize()
-    exp_totals, exp_seeds, exp_ms, exp_info = totals(plain), plain.getSeeds(), plain.lastKernelMs(), info(plain)
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    plain.close()
-
-    t = tracer()
-    src = np.ascontiguousarray(g["frames"][-1], F).reshape(-1)
-    E = tm.exposure(oracle, tm.histogram(src), 0.0)
-    exp = tm.tonemap(oracle, src, W, H, E)
-    frame.zero_()
-    dsrc = torch.from_numpy(src).cuda()
-    des = [torch.zeros(1, dtype=torch.float32, device="cuda:0") for _ in range(m["frames"])]
-    douts = [torch.zeros(W * H, dtype=torch.int32, device="cuda:0") for _ in range(m["frames"])]
-    he, hout = np.zeros(1, F), np.zeros(W * H, U)
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    for p in range(m["frames"]):
-        t.rayTrace(frame, W, H, p, kernel=2, sync=False)
-        t.meterExposure(dsrc, des[p], W, H, stream=side.cuda_stream, sync=False)
-        t.toneMap(dsrc, douts[p], W, H, exposure=des[p], stream=side.cuda_stream, sync=False)
-        if p == 1:  # and host buffers on the context's own stream
-            t.meterExposure(src, he, W, H)
-            t.toneMap(src, hout, W, H, exposure=he)
-    t.synchronize()
-    torch.cuda.synchronize()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    back = np.zeros(W * H * 4, F)
-    t.read(back)
-    assert np.array_equal(bits(back), bits(g["frames"][-1]))
-    assert np.array_equal(t.getSeeds(), exp_seeds) and np.array_equal(exp_seeds, g["seeds_out"])
-    got_totals = totals(t)
-    assert got_totals == exp_totals and got_totals["renders"] == m["frames"] and got_totals["rays_closest"] > 0
-    assert (t.lastKernelMs() > 0.0) == (exp_ms > 0.0)
-    assert info(t) == exp_info
+    with rs.untouched(pt, golden, golden_meta) as (t, frame, g, m):
+        W, H = m["W"], m["H"]
+        src = np.ascontiguousarray(g["frames"][-1], F).reshape(-1)
+        E = tm.exposure(oracle, tm.histogram(src), 0.0)
+        exp = tm.tonemap(oracle, src, W, H, E)
+        dsrc = torch.from_numpy(src).cuda()
+        des = [torch.zeros(1, dtype=torch.float32, device="cuda:0") for _ in range(m["frames"])]
+        douts = [torch.zeros(W * H, dtype=torch.int32, device="cuda:0") for _ in range(m["frames"])]
+        he, hout = np.zeros(1, F), np.zeros(W * H, U)
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        for p in range(m["frames"]):
+            t.rayTrace(frame, W, H, p, kernel=2, sync=False)
+            t.meterExposure(dsrc, des[p], W, H, stream=side.cuda_stream, sync=False)
+            t.toneMap(dsrc, douts[p], W, H, exposure=des[p], stream=side.cuda_stream, sync=False)
+            if p == 1:  # and host buffers on the context's own stream
+                t.meterExposure(src, he, W, H)
+                t.toneMap(src, hout, W, H, exposure=he)
     for d, de in zip(douts, des):
         assert np.array_equal(d.cpu().numpy().view(U), exp)
         assert bits(de.cpu().numpy())[0] == bits(np.array([E], F))[0]
     assert np.array_equal(hout, exp) and bits(he)[0] == bits(np.array([E], F))[0]
     assert np.array_equal(bits(dsrc.cpu().numpy()), bits(src))
-    t.close()
 
 
 # ---- ProgressiveViewHIP through rt_render --events ----------------------------------------------
@@ -436,16 +394,9 @@ def view_runs(pt, tmp_path_factory):
     tmp = tmp_path_factory.mktemp("tonemap_view")
     verts = pt.scenes.make_mesh(2000)[0]
     np.stack([verts, small_move(verts)]).astype(F).tofile(tmp / "poses.f32")
-    runs = {}
-    for name, extra in (("plain", []), ("tone", TONE)):
-        files = {k: tmp / f"{name}_{k}" for k in ("shown", "f8", "elog", "ppm")}
-        cmd = [str(ROOT / "pathtracer.cl_amd" / "rt_render"), "--width", str(VW), "--height", str(VH), "--mesh", "2000",
-               "--poses", str(tmp / "poses.f32"), "--events", EVENTS] + ALL_ON.cli() + extra + ["--frames-out", str(files["shown"])]
-        if extra:
-            cmd += ["--frames8-out", str(files["f8"]), "--exposure-log", str(files["elog"]), "--ppm", str(files["ppm"])]
-        r = subprocess.run(cmd, check=True, timeout=120, capture_output=True, text=True)
-        runs[name] = dict(files=files, lines=[json.loads(l) for l in r.stdout.splitlines()], shown=np.fromfile(files["shown"], F))
-    return runs
+    args = ["--mesh", "2000", "--poses", str(tmp / "poses.f32"), "--events", EVENTS] + ALL_ON.cli()
+    return {"plain": vr.run_view(tmp, args, ("shown",), VW, VH),
+            "tone": vr.run_view(tmp, args + TONE, ("shown", "f8", "elog", "ppm"), VW, VH)}
 
 
 def test_progressive_view_tone_map(view_runs, oracle):
@@ -459,8 +410,8 @@ def test_progressive_view_tone_map(view_runs, oracle):
     assert np.array_equal(bits(plain["shown"]), bits(tone["shown"]))
     sizes = [(l["width"], l["height"]) for l in tone["lines"] if l.get("rendered")]
     assert sizes == [(VW, VH)] * 6 + [(TW, TH)] * 2
-    f8 = np.fromfile(tone["files"]["f8"], U)
-    log = [int(l, 16) for l in tone["files"]["elog"].read_text().split()]
+    f8 = tone["f8"]
+    log = [int(l, 16) for l in tone["elog"].read_text().split()]
     assert f8.size == sum(w * h for w, h in sizes) and len(log) == len(sizes)
     at = at8 = 0
     prev, exposures = F(0.0), []
@@ -481,7 +432,7 @@ def test_progressive_view_tone_map(view_runs, oracle):
     second = tone["shown"][4 * VW * VH:8 * VW * VH]
     assert exposures[1] != float(tm.exposure(oracle, tm.histogram(second), 0.0, rate=0.25))
     # the PPM: binary P6, top row first
-    raw = tone["files"]["ppm"].read_bytes()
+    raw = tone["ppm"].read_bytes()
     head = f"P6\n{TW} {TH}\n255\n".encode()
     assert raw.startswith(head) and len(raw) == len(head) + 3 * TW * TH
     rgb = np.frombuffer(raw[len(head):], np.uint8).reshape(TH, TW, 3)

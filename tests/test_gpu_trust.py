@@ -7,15 +7,16 @@ the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
 import ctypes
-import json
-import subprocess
+from dataclasses import replace
 
 import numpy as np
 import pytest
 
+import render_state as rs
 import trust_cases as tc
 import trust_ref as tref
-from conftest import ROOT, bits
+import view_ref as vr
+from conftest import bits
 from test_trust_host import EXPECTED, GAIN_B, R_AT_REST
 
 pytestmark = pytest.mark.gpu
@@ -120,75 +121,30 @@ def test_argument_checks(pt, view):
 
 
 def test_render_state_untouched(pt, golden, golden_meta, oracle):
-    """tests/test_gpu_motion.py's test of the same name with the new call: the golden progressive frames
-    with rt_history_trust in between — device tensors on a side stream behind a render enqueued without
-    a wait, host buffers on the context's stream — are the frames, seeds, counter totals, render info
-    and rt_read of the sequence without it."""
+    """The golden progressive frames with rt_history_trust in between — device tensors on a side stream
+    behind a render enqueued without a wait, host buffers on the context's stream — are the frames,
+    seeds, counter totals, render info and rt_read of the sequence without it (tests/render_state.py)."""
     import torch
 
-    g, m = golden(CASE), golden_meta["cases"][CASE]
-    W, H = m["W"], m["H"]
-    verts, idx = g["verts"], g["idx"]
-
-    def tracer():
-        t = pt.RayTracer(0)
-        t.setSpheres(g["spheres"].view(pt._abi.SPHERE_DTYPE))
-        t.setCamera(g["camera"])
-        t.setSampleRate(m["sample_rate"])
-        t.setMaxPathDepth(m["max_depth"])
-        t.setNDRange(m["nd_y"])
-        t.setMesh(verts, idx)
-        t.setSeeds(m["Wpad"], m["Hpad"], g["seeds_in"])
-        t.setCounting(True)
-        return t
-
-    def totals(t):
-        c = t.counterTotals()
-        return {k: v for k, v in c.items() if "clocks" not in k and k != "lane_slots"}
-
-    def info(t):
-        return {k: v for k, v in t.renderInfo().items() if k != "schedule_host_ms"}
-
-    plain = tracer()
-    frame = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
-    for p in range(m["frames"]):
-        plain.rayTrace(frame, W, H, p, kernel=2, sync=False)
-    plain.synchronize()
-    exp_totals, exp_seeds, exp_ms, exp_info = totals(plain), plain.getSeeds(), plain.lastKernelMs(), info(plain)
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    plain.close()
-
-    t = tracer()
-    feat0 = np.zeros(2 * W * H * 4, F)
-    t.renderFeatures(feat0, W, H, kernel=2)
-    hist, ln, cur, feat = tc.golden_inputs(g, feat0, W, H)
-    exp = tref.trust(oracle, hist, ln, cur, 2.0, feat, W, H, tolerance=TOL)
-    frame.zero_()
-    dhist, dln, dcur, dfeat = (torch.from_numpy(a).cuda() for a in (hist, ln, cur, feat))
-    douts = [torch.zeros_like(dln) for _ in range(m["frames"])]
-    host_out = np.zeros_like(ln)
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    for p in range(m["frames"]):
-        t.rayTrace(frame, W, H, p, kernel=2, sync=False)
-        t.historyTrust(dhist, dln, dcur, 2.0, dfeat, douts[p], W, H, stream=side.cuda_stream, sync=False)
-        if p == 1:  # and host buffers on the context's own stream
-            t.historyTrust(hist, ln, cur, 2.0, feat, host_out, W, H)
-    t.synchronize()
-    torch.cuda.synchronize()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    back = np.zeros(W * H * 4, F)
-    t.read(back)
-    assert np.array_equal(bits(back), bits(g["frames"][-1]))
-    assert np.array_equal(t.getSeeds(), exp_seeds) and np.array_equal(exp_seeds, g["seeds_out"])
-    got_totals = totals(t)
-    assert got_totals == exp_totals and got_totals["renders"] == m["frames"] and got_totals["rays_closest"] > 0
-    assert (t.lastKernelMs() > 0.0) == (exp_ms > 0.0)
-    assert info(t) == exp_info
+    with rs.untouched(pt, golden, golden_meta) as (t, frame, g, m):
+        W, H = m["W"], m["H"]
+        feat0 = np.zeros(2 * W * H * 4, F)
+        t.renderFeatures(feat0, W, H, kernel=2)
+        hist, ln, cur, feat = tc.golden_inputs(g, feat0, W, H)
+        exp = tref.trust(oracle, hist, ln, cur, 2.0, feat, W, H, tolerance=TOL)
+        dhist, dln, dcur, dfeat = (torch.from_numpy(a).cuda() for a in (hist, ln, cur, feat))
+        douts = [torch.zeros_like(dln) for _ in range(m["frames"])]
+        host_out = np.zeros_like(ln)
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        for p in range(m["frames"]):
+            t.rayTrace(frame, W, H, p, kernel=2, sync=False)
+            t.historyTrust(dhist, dln, dcur, 2.0, dfeat, douts[p], W, H, stream=side.cuda_stream, sync=False)
+            if p == 1:  # and host buffers on the context's own stream
+                t.historyTrust(hist, ln, cur, 2.0, feat, host_out, W, H)
     for d in douts:
         assert np.array_equal(bits(d.cpu().numpy()), bits(exp))
     assert np.array_equal(bits(host_out), bits(exp))
-    t.close()
 
 
 # ---- ProgressiveViewHIP through rt_render --events ----------------------------------------------
@@ -198,17 +154,25 @@ EV_LIGHT = "d,d,e:0.4:0:0,d,d"     # the light moves by 0.4 in x between the sec
 PROGRESSION = [0, 1, 1, 2]
 
 
-def _run(tmp_path, name, events, extra, denoise):
-    W, H = 64, 48
-    exe = ROOT / "pathtracer.cl_amd" / "rt_render"
-    files = {k: tmp_path / f"{name}_{k}.f32" for k in ("shown", "raw", "feat")}
-    cmd = [str(exe), "--width", str(W), "--height", str(H), "--mesh", "2000", "--events", events, "--temporal"] + \
-          (["--denoise"] if denoise else []) + extra + \
-          ["--frames-out", str(files["shown"]), "--raw-frames-out", str(files["raw"]), "--features-out", str(files["feat"])]
-    r = subprocess.run(cmd, check=True, timeout=120, capture_output=True, text=True)
-    run = {k: np.fromfile(f, F) for k, f in files.items()}
-    run["lines"] = [json.loads(l) for l in r.stdout.splitlines()]
+def _run(tmp_path, events, flags):
+    run = vr.run_view(tmp_path, ["--mesh", "2000", "--events", events] + flags.cli())
+    assert [l["progression"] for l in run["lines"] if l.get("rendered")] == PROGRESSION
     return run
+
+
+class _RestatedTrust:
+    """A tracer whose historyTrust is the restatement of rt_history_trust; it counts, call by call, the
+    pixels whose history that shortened."""
+
+    def __init__(self, rt, oracle):
+        self.rt, self.oracle, self.shortened = rt, oracle, []
+
+    def __getattr__(self, name):
+        return getattr(self.rt, name)
+
+    def historyTrust(self, car, cl, cur, n, feat, out, w, h, tolerance):
+        out[:] = tref.trust(self.oracle, car, cl, cur, n, feat, w, h, tolerance=tolerance)
+        self.shortened.append(int((out < cl).sum()))
 
 
 @pytest.mark.parametrize("denoise", [False, True])
@@ -217,51 +181,33 @@ def test_progressive_view_history_trust(denoise, view, pt, oracle, tmp_path):
     bit for bit (no light move: sceneChanged itself treats the history differently).  Across a light
     move, --temporal alone drops the history (sceneChanged), --history-trust keeps and judges it: every
     displayed frame of both runs is the recomposition of reproject / the restatement of rt_history_trust
-    / temporalMerge (/ denoise), the accumulation buffers of both runs are the same, and the runs differ
-    exactly from the first display after the move on."""
-    rt = view[0]
+    / temporalMerge (/ denoise) (tests/view_ref.py), the accumulation buffers of both runs are the same,
+    and the runs differ exactly from the first display after the move on."""
     W, H = 64, 48
     px = W * H * 4
-    plain = _run(tmp_path, "plain", EV_PLAIN, [], denoise)
-    allin = _run(tmp_path, "inf", EV_PLAIN, ["--history-trust", "inf"], denoise)
+    base = vr.Flags(temporal=True, denoise=denoise)
+    plain = _run(tmp_path, EV_PLAIN, base)
+    allin = _run(tmp_path, EV_PLAIN, replace(base, history_trust=True, tolerance=float("inf")))
     assert plain["shown"].size == 4 * px
     for k in ("shown", "raw", "feat"):
         assert np.array_equal(bits(plain[k]), bits(allin[k])), k
-    runs = {"off": _run(tmp_path, "off", EV_LIGHT, [], denoise),
-            "on": _run(tmp_path, "on", EV_LIGHT, ["--history-trust", str(TOL)], denoise)}
+    variants = {"off": base, "on": replace(base, history_trust=True, tolerance=TOL)}
+    runs = {name: _run(tmp_path, EV_LIGHT, fl) for name, fl in variants.items()}
     on, off = runs["on"], runs["off"]
     assert on["shown"].size == off["shown"].size == 4 * px and on["feat"].size == 8 * px
     assert np.array_equal(bits(on["raw"]), bits(off["raw"])) and np.array_equal(bits(on["feat"]), bits(off["feat"]))
     moved = [l for l in on["lines"] if l.get("event", "").startswith("e:")]
     assert len(moved) == 1 and moved[0]["progression"] == 0 and not moved[0]["rendered"]
     assert not np.array_equal(bits(on["raw"][px:2 * px]), bits(on["raw"][2 * px:3 * px]))  # the light did move
-    cam = pt.scenes.camera_spherical(W, **pt.scenes.PLY_CAMERA)
-    shortened = 0
+    rt = _RestatedTrust(view[0], oracle)
     for name, run in runs.items():
-        hist = hl = pfeat = None
-        car, cl = np.zeros(px, F), np.zeros(W * H, F)
-        for k, prog in enumerate(PROGRESSION):
-            cur = np.ascontiguousarray(run["raw"][px * k:px * (k + 1)])
-            feat = np.ascontiguousarray(run["feat"][2 * px * k:2 * px * (k + 1)])
-            n = max(prog, 1)
-            if k == 2:  # the first display after the move
-                car, cl = np.zeros(px, F), np.zeros(W * H, F)
-                if name == "on":  # the history is kept and carried (the same camera)
-                    rt.reproject(hist, hl, pfeat, cam, feat, car, cl, W, H)
-            tl = cl
-            if name == "on" and hist is not None:
-                tl = tref.trust(oracle, car, cl, cur, n, feat, W, H, tolerance=TOL)
-                if k >= 2:
-                    shortened += int((tl < cl).sum())
-            hist, hl = np.zeros(px, F), np.zeros(W * H, F)
-            rt.temporalMerge(car, tl, cur, n, hist, hl, W, H)
-            disp = hist
-            if denoise:
-                disp = np.zeros(px, F)
-                rt.denoise(hist, feat, disp, W, H)
+        exp = vr.displayed(rt, pt.scenes, variants[name], EV_LIGHT, run["raw"], run["feat"], W, H)
+        assert len(exp.frames) == 4
+        for k, disp in enumerate(exp.frames):
             assert np.array_equal(bits(run["shown"][px * k:px * (k + 1)]), bits(disp)), f"{name}: displayed frame {k}"
-            pfeat = feat
-    assert shortened > 100  # the test did shorten histories in the frames after the move
+    # judged at every display that has a history, the three after the first, and only with the flag;
+    # the test did shorten histories in the frames after the move
+    assert len(rt.shortened) == 3 and sum(rt.shortened[1:]) > 100
     for k in range(4):
         same = np.array_equal(bits(on["shown"][px * k:px * (k + 1)]), bits(off["shown"][px * k:px * (k + 1)]))
         assert same == (k < 2), f"displayed frame {k} against the run without --history-trust"
@@ -272,12 +218,13 @@ def test_progressive_view_moments_take_the_trusted_length(tmp_path):
     displays the frames of the run without the flag bit for bit, and across the light move a finite
     tolerance changes what is displayed from the first display after the move on."""
     px = 64 * 48 * 4
-    vg = ["--variance-guided"]
-    plain = _run(tmp_path, "vplain", EV_PLAIN, vg, False)
-    allin = _run(tmp_path, "vinf", EV_PLAIN, vg + ["--history-trust", "inf"], False)
+    vg = vr.Flags(temporal=True, variance_guided=True)
+    trust_all = replace(vg, history_trust=True, tolerance=float("inf"))
+    plain = _run(tmp_path, EV_PLAIN, vg)
+    allin = _run(tmp_path, EV_PLAIN, trust_all)
     assert plain["shown"].size == 4 * px and np.array_equal(bits(plain["shown"]), bits(allin["shown"]))
-    kept = _run(tmp_path, "vkept", EV_LIGHT, vg + ["--history-trust", "inf"], False)
-    on = _run(tmp_path, "von", EV_LIGHT, vg + ["--history-trust", str(TOL)], False)
+    kept = _run(tmp_path, EV_LIGHT, trust_all)
+    on = _run(tmp_path, EV_LIGHT, replace(trust_all, tolerance=TOL))
     assert np.array_equal(bits(on["raw"]), bits(kept["raw"])) and np.isfinite(on["shown"]).all()
     for k in range(4):
         same = np.array_equal(bits(on["shown"][px * k:px * (k + 1)]), bits(kept["shown"][px * k:px * (k + 1)]))

@@ -5,22 +5,23 @@ ProgressiveViewHIP::setVarianceGuided through the rt_render CLI; and its effect 
 Run on the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
-import subprocess
+from dataclasses import replace
 
 import numpy as np
 import pytest
 
 import features_ref as fr
+import render_state as rs
 import variance_ref as vr
-from conftest import ROOT, bits
+import view_ref
+from conftest import bits
 
 pytestmark = pytest.mark.gpu
 
 CASE = "tris_64x48_sr1"
 F = np.float32
 W0, H0 = 64, 48
-TARGET = (0.0, -4.0, 0.0)
-EL0, AZ0, DIST = 40.0, 105.0, 5.0  # the golden view
+AZ0 = 105.0  # the golden view's azimuth, where the view starts
 # (w, h) -> window origin in the golden view: the small windows straddle the mesh's silhouette
 WINDOWS = {(1, 1): (20, 20), (5, 3): (8, 30), (37, 29): (3, 9), (64, 48): (0, 0)}
 SIZES = list(WINDOWS)
@@ -331,72 +332,35 @@ def test_device_tensors_on_a_side_stream(view, oracle):
 def test_render_state_untouched(pt, golden, golden_meta, view, oracle):
     """The golden progressive frames with the three calls in between — device tensors on a side
     stream behind a render enqueued without a wait, host buffers on the context's stream — are the
-    frames, seeds and counter totals of the sequence without those calls; and every side-stream call
-    saw the frame of the render before it, not the one enqueued after it."""
+    frames, seeds, counter totals and render info of the sequence without those calls
+    (tests/render_state.py); and every side-stream call saw the frame of the render before it, not the
+    one enqueued after it."""
     import torch
 
     _, feat = view
-    g, m = golden(CASE), golden_meta["cases"][CASE]
-    W, H, n_frames = m["W"], m["H"], m["frames"]
-
-    def tracer():
-        t = pt.RayTracer(0)
-        t.setSpheres(g["spheres"].view(pt._abi.SPHERE_DTYPE))
-        t.setCamera(g["camera"])
-        t.setSampleRate(m["sample_rate"])
-        t.setMaxPathDepth(m["max_depth"])
-        t.setNDRange(m["nd_y"])
-        t.setMesh(g["verts"], g["idx"])
-        t.setSeeds(m["Wpad"], m["Hpad"], g["seeds_in"])
-        t.setCounting(True)
-        return t
-
-    def totals(t):
-        c = t.counterTotals()  # (the clock readings and the lane slots vary from run to run)
-        return {k: v for k, v in c.items() if "clocks" not in k and k != "lane_slots"}
-
-    plain = tracer()
-    frame = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
-    for p in range(n_frames):
-        plain.rayTrace(frame, W, H, p, kernel=2, sync=False)
-    plain.synchronize()
-    exp_totals, exp_seeds, exp_ms = totals(plain), plain.getSeeds(), plain.lastKernelMs()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    plain.close()
-
-    frames = [np.ascontiguousarray(fm) for fm in g["frames"]]
-    t = tracer()
-    frame.zero_()
-    dfeat = torch.from_numpy(feat).cuda()
-    dprevs = [torch.from_numpy(frames[max(p - 1, 0)]).cuda() for p in range(n_frames)]  # the buffer before frame p
-    dmom = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
-    dlens = [torch.full((W * H,), float(max(p, 1)), dtype=torch.float32, device="cuda:0") for p in range(n_frames)]
-    dvars = [torch.zeros(W * H, dtype=torch.float32, device="cuda:0") for _ in range(n_frames)]
-    douts = [torch.zeros_like(frame) for _ in range(n_frames)]
-    side = torch.cuda.Stream()
-    torch.cuda.synchronize()
-    st = side.cuda_stream
-    h_mom, h_var, h_out = np.zeros(W * H * 4, F), np.zeros(W * H, F), np.zeros(W * H * 4, F)
-    for p in range(n_frames):
-        t.rayTrace(frame, W, H, p, kernel=2, sync=False)
-        n = max(p, 1)
-        t.momentsAccumulate(dprevs[p], frame, n, dmom, dmom, W, H, stream=st, sync=False)
-        t.variance(frame, dmom, dlens[p], dfeat, dvars[p], W, H, min_len=2.0, stream=st, sync=False)
-        t.denoiseVar(frame, dvars[p], dfeat, douts[p], None, W, H, stream=st, sync=False)
-        if p == 1:  # and host buffers on the context's own stream
-            t.momentsAccumulate(None, frames[0], 1, None, h_mom, W, H)
-            t.variance(frames[0], h_mom, np.ones(W * H, F), feat, h_var, W, H)
-            t.denoiseVar(frames[0], h_var, feat, h_out, None, W, H)
-    t.synchronize()
-    torch.cuda.synchronize()
-    assert np.array_equal(bits(frame.cpu().numpy()), bits(g["frames"][-1]))
-    back = np.zeros(W * H * 4, F)
-    t.read(back)
-    assert np.array_equal(bits(back), bits(g["frames"][-1]))
-    assert np.array_equal(t.getSeeds(), exp_seeds) and np.array_equal(exp_seeds, g["seeds_out"])
-    got_totals = totals(t)
-    assert got_totals == exp_totals and got_totals["renders"] == n_frames and got_totals["rays_closest"] > 0
-    assert (t.lastKernelMs() > 0.0) == (exp_ms > 0.0)
+    with rs.untouched(pt, golden, golden_meta) as (t, frame, g, m):
+        W, H, n_frames = m["W"], m["H"], m["frames"]
+        frames = [np.ascontiguousarray(fm) for fm in g["frames"]]
+        dfeat = torch.from_numpy(feat).cuda()
+        dprevs = [torch.from_numpy(frames[max(p - 1, 0)]).cuda() for p in range(n_frames)]  # the buffer before frame p
+        dmom = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda:0")
+        dlens = [torch.full((W * H,), float(max(p, 1)), dtype=torch.float32, device="cuda:0") for p in range(n_frames)]
+        dvars = [torch.zeros(W * H, dtype=torch.float32, device="cuda:0") for _ in range(n_frames)]
+        douts = [torch.zeros_like(frame) for _ in range(n_frames)]
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        st = side.cuda_stream
+        h_mom, h_var, h_out = np.zeros(W * H * 4, F), np.zeros(W * H, F), np.zeros(W * H * 4, F)
+        for p in range(n_frames):
+            t.rayTrace(frame, W, H, p, kernel=2, sync=False)
+            n = max(p, 1)
+            t.momentsAccumulate(dprevs[p], frame, n, dmom, dmom, W, H, stream=st, sync=False)
+            t.variance(frame, dmom, dlens[p], dfeat, dvars[p], W, H, min_len=2.0, stream=st, sync=False)
+            t.denoiseVar(frame, dvars[p], dfeat, douts[p], None, W, H, stream=st, sync=False)
+            if p == 1:  # and host buffers on the context's own stream
+                t.momentsAccumulate(None, frames[0], 1, None, h_mom, W, H)
+                t.variance(frames[0], h_mom, np.ones(W * H, F), feat, h_var, W, H)
+                t.denoiseVar(frames[0], h_var, feat, h_out, None, W, H)
     mom = None
     for p in range(n_frames):
         n = max(p, 1)
@@ -410,7 +374,6 @@ def test_render_state_untouched(pt, golden, golden_meta, view, oracle):
     e_var = vr.variance(oracle, frames[0], e_mom, np.ones(W * H, F), feat, W, H)
     assert np.array_equal(bits(h_mom), bits(e_mom)) and np.array_equal(bits(h_var), bits(e_var))
     assert np.array_equal(bits(h_out), bits(vr.denoise_var(oracle, frames[0], e_var, feat, W, H)[0]))
-    t.close()
 
 
 # ---- the view, through the CLI ---------------------------------------------------------------
@@ -420,58 +383,31 @@ def test_progressive_view_variance_guided(temporal, view, pt, tmp_path):
     """ProgressiveViewHIP::setVarianceGuided through the rt_render CLI: three displays, a key press,
     two displays.  The accumulation buffer of every displayed frame is that of the run without the
     flag; every displayed frame is the recomposition of momentsAccumulate / (reproject / temporalMerge
-    of colour and moments /) variance / denoiseVar through the Python API; the display differs from
-    the --denoise run's."""
+    of colour and moments, with one plane of lengths /) variance / denoiseVar through the Python API
+    (tests/view_ref.py); the display differs from the --denoise run's."""
     rt, _ = view
     W, H = 64, 48
     px = W * H * 4
-    exe = ROOT / "pathtracer.cl_amd" / "rt_render"
-    common = [str(exe), "--width", str(W), "--height", str(H), "--mesh", "2000", "--events", "d,d,d,l,d,d"]
-    tmp = ["--temporal"] if temporal else []
-    plain, den, on, raw, feats = (tmp_path / n for n in ("plain.f32", "den.f32", "on.f32", "raw.f32", "feat.f32"))
-    subprocess.run(common + ["--frames-out", str(plain)], check=True, timeout=120, capture_output=True)
-    subprocess.run(common + tmp + ["--denoise", "--frames-out", str(den)], check=True, timeout=120, capture_output=True)
-    subprocess.run(common + tmp + ["--variance-guided", "--frames-out", str(on), "--raw-frames-out", str(raw),
-                                   "--features-out", str(feats)], check=True, timeout=120, capture_output=True)
-    f_plain, f_den, f_on, f_raw, f_feat = (np.fromfile(p, F) for p in (plain, den, on, raw, feats))
-    assert f_plain.size == f_den.size == f_on.size == f_raw.size == 5 * px and f_feat.size == 10 * px
-    assert np.array_equal(bits(f_raw), bits(f_plain))
+    events = "d,d,d,l,d,d"
+    flags = view_ref.Flags(variance_guided=True, temporal=temporal)
+    common = ["--mesh", "2000", "--events", events]
+    plain = view_ref.run_view(tmp_path, common, ("shown",))
+    den = view_ref.run_view(tmp_path, common + replace(flags, variance_guided=False, denoise=True).cli(), ("shown",))
+    on = view_ref.run_view(tmp_path, common + flags.cli())
+    assert plain["shown"].size == den["shown"].size == on["shown"].size == on["raw"].size == 5 * px and on["feat"].size == 10 * px
+    assert np.array_equal(bits(on["raw"]), bits(plain["shown"]))
     # (view's azimuth, progression) of the five displayed frames: display() renders progression 0 only
     # after a (re)allocation; after a restart it counts on from 1, whose mix overwrites the buffer
     shown = [(AZ0, 0), (AZ0, 1), (AZ0, 2), (AZ0 + 3.0, 1), (AZ0 + 3.0, 2)]
-    mom = hist = hl = mhist = pfeat = pcam = None
-    for k, (az, prog) in enumerate(shown):
-        n = max(prog, 1)
-        cur = np.ascontiguousarray(f_raw[px * k:px * (k + 1)])
-        prev = np.ascontiguousarray(f_raw[px * (k - 1):px * k]) if n > 1 else None
-        feat = np.ascontiguousarray(f_feat[2 * px * k:2 * px * (k + 1)])
-        cam = pt.scenes.camera_spherical(W, target=TARGET, elevation=EL0, azimuth=az, distance=DIST)
-        new_mom = np.zeros(px, F)
-        rt.momentsAccumulate(prev, cur, n, mom if n > 1 else None, new_mom, W, H)
-        mom = new_mom
-        if temporal:
-            if hist is None or az != shown[k - 1][0]:  # the first display of a view
-                car, cl, mcar, mcl = np.zeros(px, F), np.zeros(W * H, F), np.zeros(px, F), np.zeros(W * H, F)
-                if hist is not None:
-                    rt.reproject(hist, hl, pfeat, pcam, feat, car, cl, W, H)
-                    rt.reproject(mhist, hl, pfeat, pcam, feat, mcar, mcl, W, H)
-                    assert np.array_equal(bits(mcl), bits(cl))  # the moments' lengths are the colour's
-            hist, hl, mhist, ml = np.zeros(px, F), np.zeros(W * H, F), np.zeros(px, F), np.zeros(W * H, F)
-            rt.temporalMerge(car, cl, cur, n, hist, hl, W, H)
-            rt.temporalMerge(mcar, mcl, mom, n, mhist, ml, W, H)
-            assert np.array_equal(bits(ml), bits(hl))
-            disp, dmom, ln = hist, mhist, hl
-            pfeat, pcam = feat, cam
-        else:
-            disp, dmom, ln = cur, mom, np.full(W * H, n, F)
-        var, out = np.zeros(W * H, F), np.zeros(px, F)
-        rt.variance(disp, dmom, ln, feat, var, W, H)
-        rt.denoiseVar(disp, var, feat, out, None, W, H)
-        got = f_on[px * k:px * (k + 1)]
+    assert [(l["azimuth"], l["progression"]) for l in on["lines"] if l.get("rendered")] == shown
+    exp = view_ref.displayed(rt, pt.scenes, flags, events, on["raw"], on["feat"], W, H)
+    assert len(exp.frames) == 5
+    for k, out in enumerate(exp.frames):
+        got = on["shown"][px * k:px * (k + 1)]
         assert np.array_equal(bits(got), bits(out)), f"displayed frame {k}"
-        assert not np.array_equal(bits(got), bits(f_den[px * k:px * (k + 1)])), f"displayed frame {k} against --denoise"
+        assert not np.array_equal(bits(got), bits(den["shown"][px * k:px * (k + 1)])), f"displayed frame {k} against --denoise"
     if temporal:
-        assert (hl > 2).mean() > 0.8  # two frames of this view, and what the view before it left
+        assert (exp.lengths[-1] > 2).mean() > 0.8  # two frames of this view, and what the view before it left
 
 
 # ---- quality ---------------------------------------------------------------------------------

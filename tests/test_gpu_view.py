@@ -1,19 +1,17 @@
 """GPU: ProgressiveViewHIP with every display stage on at once — the temporal carry, the
 motion carry, the history trust and a filter — through the rt_render CLI, against the one restatement
 of the view's display chain (tests/view_ref.py).  The tests of the single features (test_gpu_denoise,
-_temporal, _variance, _motion, _trust) each restate the chain for their own flag.  Run on the MI355X box
-with `pytest -m gpu`."""
+_temporal, _variance, _motion, _trust, _sphere_motion) recompose through the same restatement, each
+with its own flag, events and assertions.  Run on the MI355X box with `pytest -m gpu`."""
 from __future__ import annotations
 
-import json
-import subprocess
 from dataclasses import replace
 
 import numpy as np
 import pytest
 
 import view_ref as vr
-from conftest import ROOT, bits
+from conftest import bits
 from test_gpu_trust import TOL
 from test_motion_host import small_move
 
@@ -57,13 +55,8 @@ def run(poses, tmp_path_factory):
 
     def get(flags):
         if flags not in cache:
-            files = {k: tmp / f"{len(cache)}_{k}.f32" for k in ("shown", "raw", "feat")}
-            cmd = [str(ROOT / "pathtracer.cl_amd" / "rt_render"), "--width", str(W), "--height", str(H), "--mesh", "2000",
-                   "--poses", str(tmp / "poses.f32"), "--events", EVENTS] + flags.cli() + \
-                  ["--frames-out", str(files["shown"]), "--raw-frames-out", str(files["raw"]), "--features-out", str(files["feat"])]
-            r = subprocess.run(cmd, check=True, timeout=120, capture_output=True, text=True)
-            cache[flags] = {k: np.fromfile(f, F) for k, f in files.items()}
-            cache[flags]["lines"] = [json.loads(l) for l in r.stdout.splitlines()]
+            cache[flags] = vr.run_view(tmp, ["--mesh", "2000", "--poses", str(tmp / "poses.f32"), "--events", EVENTS] + flags.cli(),
+                                       width=W, height=H)
         return cache[flags]
 
     return get
@@ -90,7 +83,7 @@ def test_progressive_view_all_stages(filter_flag, run, rt, pt, mesh, poses):
         got = run(fl)
         assert got["shown"].size == N_SHOWN * PX and got["feat"].size == 2 * N_SHOWN * PX
         assert np.array_equal(bits(got["raw"]), bits(plain["shown"])), fl
-        exp = vr.displayed(rt, pt.scenes, fl, EVENTS, got["raw"], got["feat"], W, H, mesh=mesh, poses=poses)
+        exp = vr.displayed(rt, pt.scenes, fl, EVENTS, got["raw"], got["feat"], W, H, mesh=mesh, poses=poses).frames
         assert len(exp) == N_SHOWN
         for k in range(N_SHOWN):
             assert np.array_equal(bits(frame(got, k)), bits(exp[k])), f"{fl}: displayed frame {k}"
