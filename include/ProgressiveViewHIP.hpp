@@ -92,6 +92,17 @@
  *                    pixels() is what it was without the stage.  The exposure starts afresh ("none") at a
  *                    (re)allocation and when the stage is switched on; restart(), updateMesh() and
  *                    sceneChanged() keep it.  Off (the default), nothing changes, allocation included.
+ *   setConverge(on, params, minFrames)  (no counterpart in the reference) refine until converged (DESIGN.md
+ *                    §4.17): every traced display meters what the stages above chose to show, before any
+ *                    filter — the accumulation buffer, or with setTemporal the merged history — against the
+ *                    variance of its luminance (rt_variance, from the view's moments, which are then kept
+ *                    whether setVarianceGuided is on or not) with rt_noise_meter, and reads the sixteen
+ *                    bytes of stats back with the frame.  Once at least minFrames frames are in the view's
+ *                    moments, a pixel was counted and the level is at or under params.threshold, the view
+ *                    is converged(): that display() returns false and later ones trace nothing, until
+ *                    restart(), a key, a drag, a reshape, updateMesh or sceneChanged() — which then ask for
+ *                    a redisplay as they do after maxProgression.  What is displayed does not change.  Off
+ *                    (the default), nothing changes, allocation included.
  *   setFloatReadback(on)  with setToneMap: off, display() reads back only the 8-bit frame (a quarter of
  *                    the bytes) and pixels() keeps its last contents — those of the last display with the
  *                    readback on, zeros before any; rawPixels() still fetches the accumulation buffer.  On
@@ -133,11 +144,11 @@ public:
             progression_ = 0;
             trace();
             realloc_ = false;
-            again = maxProgression_ > 0;
-        } else if (progression_ < maxProgression_) {
+            again = maxProgression_ > 0 && !converged_;
+        } else if (progression_ < maxProgression_ && !converged_) {
             ++progression_;
             trace();
-            again = true;
+            again = !converged_; /* the display that converges posts no redisplay */
         }
         return again;
     }
@@ -171,7 +182,8 @@ public:
 
     bool restart()
     {
-        const bool post = progression_ >= maxProgression_;
+        const bool post = progression_ >= maxProgression_ || converged_;
+        converged_ = false;
         progression_ = 0;
         carry_ = true;
         return post;
@@ -285,6 +297,27 @@ public:
         varParams_ = params;
     }
     bool varianceGuided() const { return varGuided_; }
+    /* (no counterpart in the reference) refine until converged: see the file comment */
+    void setConverge(bool on, const rt_noise_params &params = RayTracerHIP::noiseDefaults(), unsigned minFrames = 8)
+    {
+        if (on && !momentsWanted()) { /* no moments are kept: as setVarianceGuided(true) from off */
+            featDirty_ = true;
+            dropHistory();
+        }
+        converge_ = on;
+        convergeParams_ = params;
+        convergeMinFrames_ = minFrames;
+        converged_ = false; /* the next traced display decides afresh */
+    }
+    /* whether the last traced display found the view converged: display() traces no more until a
+       restart(), a reallocation, updateMesh or sceneChanged */
+    bool converged() const { return converged_; }
+    /* the noise meter's figures of the last traced display with setConverge on (zeros before one) */
+    const rt_noise_stats &noiseStats() const { return noiseStats_; }
+    /* With setConverge: also compute the per-tile noise map at every traced display and read it back
+       into noiseMap(): ceil(W/8) ceil(H/8) pairs (mean, max), row-major, bottom tile row first. */
+    void setNoiseMapReadback(bool on) { noiseMapReadback_ = on; }
+    const std::vector<float> &noiseMap() const { return noiseMap_; }
 
     /* (no counterpart in the reference) the tone-mapped 8-bit display output */
     void setToneMap(bool on, const rt_tonemap_params &params = RayTracerHIP::toneMapDefaults(), bool autoExposure = true,
@@ -398,7 +431,11 @@ private:
         History moments;
         /* setToneMap: the RGBA8 frame (W*H words) and the metered exposure (one float; 0: none yet) */
         DeviceFloats tone8, exposure;
+        /* setConverge: the meter's stats (four words) and, with setNoiseMapReadback, the tile pairs */
+        DeviceFloats noiseStats, noiseTiles;
     };
+    /* setVarianceGuided or setConverge: the view keeps the accumulation copy, the moments and the variance plane */
+    bool momentsWanted() const { return varGuided_ || converge_; }
 
     /* What earlier frames left is no longer valid: the next display starts the history afresh (and
        the moments, unless the caller keeps them). */
@@ -415,6 +452,10 @@ private:
         buf_->dev.need((size_t)width_ * height_ * 4, "framebuffer");
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
         pbo8_.clear();
+        noiseMap_.clear();
+        noiseStats_ = rt_noise_stats{};
+        converged_ = false;
+        frames_ = 0;
         exposureReset_ = true;
         featDirty_ = true;
         dropHistory();
@@ -437,18 +478,18 @@ private:
         featDirty_ = false;
         return temporal_ ? b.featPrev.p : b.feat.p;
     }
-    /* The merged frame of this display into the colour history's kept pair; with setVarianceGuided the
-       view's moments go the same way into theirs.  Both take their lengths from the colour history:
+    /* The merged frame of this display into the colour history's kept pair; with kept moments (setVarianceGuided,
+       setConverge) the view's moments go the same way into theirs.  Both take their lengths from the colour history:
        they keep one length. */
     void mergeTemporal(const float *histFeat, float n)
     {
         Buffers &b = *buf_;
         const size_t px = (size_t)width_ * height_;
         b.colour.need(px, "history buffer");
-        if (varGuided_) b.moments.need(px, "moments history buffer");
+        if (momentsWanted()) b.moments.need(px, "moments history buffer");
         const History *const hist[] = {&b.colour, &b.moments}; /* the active ones, and what this display merges into each */
         const float *const cur[] = {b.dev.p, b.mom.p};
-        const int nHist = varGuided_ ? 2 : 1;
+        const int nHist = momentsWanted() ? 2 : 1;
         const rt_camera cam = rt_.getCamera(width_);
         const bool judged = trust_ && haveHist_; /* a history exists: it is judged at every display */
         if (!haveHist_) { /* after a (re)allocation or a drop: no history anywhere */
@@ -511,7 +552,7 @@ private:
                                  hipDeviceSynchronize() != hipSuccess))
             throw std::runtime_error("ProgressiveViewHIP: accumulation copy failed");
     }
-    /* setVarianceGuided without setTemporal: one view, n frames everywhere */
+    /* kept moments without setTemporal: one view, n frames everywhere */
     const float *constantLengths(float n)
     {
         const size_t px = (size_t)width_ * height_;
@@ -539,6 +580,18 @@ private:
         }
         rt_.toneMap(shown, exposure, reinterpret_cast<uint32_t *>(b.tone8.p), width_, height_, toneParams_, true);
     }
+    size_t noiseTileCount() const { return (size_t)((width_ + 7u) / 8u) * ((height_ + 7u) / 8u); }
+    /* setConverge: meter what stage (6) chose to show, before any filter, with the variance plane just
+       estimated for it; the stats (and with setNoiseMapReadback the tile pairs) stay on the device
+       until the frame's readback. */
+    void meterShown(const float *shown, bool sync)
+    {
+        Buffers &b = *buf_;
+        b.noiseStats.need(sizeof(rt_noise_stats) / sizeof(float), "noise stats");
+        if (noiseMapReadback_) b.noiseTiles.need(2 * noiseTileCount(), "noise tile map");
+        rt_.noiseMeter(shown, b.var.p, reinterpret_cast<rt_noise_stats *>(b.noiseStats.p), noiseMapReadback_ ? b.noiseTiles.p : nullptr,
+                       nullptr, width_, height_, convergeParams_, true, sync);
+    }
     /* One traced display, whatever is switched on: render, then compose what is shown from the
        accumulation buffer, which every stage only reads. */
     void trace()
@@ -546,15 +599,17 @@ private:
         Buffers &b = *buf_;
         const size_t px = (size_t)width_ * height_;
         const float n = (float)(progression_ > 1 ? progression_ : 1);
-        if (varGuided_) keepAccumulation();
+        if (momentsWanted()) keepAccumulation();
         rt_.rayTrace(b.dev.p, width_, height_, progression_, kernel_, true);
-        if (varGuided_) {
+        if (momentsWanted()) {
             b.mom.need(4 * px, "moments buffer");
             /* (without valid moments, after it was switched on in mid-accumulation: start from this frame) */
-            rt_.momentsAccumulate(b.accPrev.p, b.dev.p, momValid_ ? n : 1.0f, b.mom.p, b.mom.p, width_, height_, true);
+            const float nMom = momValid_ ? n : 1.0f;
+            rt_.momentsAccumulate(b.accPrev.p, b.dev.p, nMom, b.mom.p, b.mom.p, width_, height_, true);
             momValid_ = true;
+            frames_ = nMom == 1.0f ? 1u : frames_ + 1u; /* the frames in the view's own moments */
         }
-        const float *histFeat = varGuided_ || denoise_ || temporal_ ? refreshFeatures() : nullptr;
+        const float *histFeat = momentsWanted() || denoise_ || temporal_ ? refreshFeatures() : nullptr;
         /* what is displayed, its moments and its history lengths */
         const float *shown = b.dev.p, *moments = b.mom.p, *len = nullptr;
         if (temporal_) {
@@ -562,13 +617,16 @@ private:
             shown = b.colour.kept.rgba();
             moments = b.moments.kept.rgba();
             len = b.colour.kept.len();
-        } else if (varGuided_) {
+        } else if (momentsWanted()) {
             len = constantLengths(n);
         }
         if (varGuided_ || denoise_) b.den.need(4 * px, "denoised framebuffer");
-        if (varGuided_) { /* in place of setDenoise's filter, whether that is on or not */
+        if (momentsWanted()) {
             b.var.need(px, "variance buffer");
             rt_.variance(shown, moments, len, b.feat.p, b.var.p, width_, height_, varParams_, true);
+        }
+        if (converge_) meterShown(shown, /*sync=*/!varGuided_ && !denoise_); /* (a filter's call waits for the stream) */
+        if (varGuided_) { /* in place of setDenoise's filter, whether that is on or not */
             rt_.denoiseVar(shown, b.var.p, b.feat.p, b.den.p, nullptr, width_, height_, varParams_, true);
             shown = b.den.p;
         } else if (denoise_) {
@@ -586,6 +644,15 @@ private:
             pbo8_.resize(px);
             if (hipMemcpy(pbo8_.data(), b.tone8.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: 8-bit frame readback failed");
+        }
+        if (converge_) { /* the meter's sixteen bytes, and the decision they allow */
+            bool ok = hipMemcpy(&noiseStats_, b.noiseStats.p, sizeof noiseStats_, hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && noiseMapReadback_) {
+                noiseMap_.resize(2 * noiseTileCount());
+                ok = hipMemcpy(noiseMap_.data(), b.noiseTiles.p, noiseMap_.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+            }
+            if (!ok) throw std::runtime_error("ProgressiveViewHIP: noise stats readback failed");
+            converged_ = frames_ >= convergeMinFrames_ && noiseStats_.counted > 0 && noiseStats_.level <= convergeParams_.threshold;
         }
         if (sphereCarry_ && kernel_ != RT_KERNEL_TRIS) { /* the spheres this frame was displayed with */
             shownSpheres_ = rt_.spheres();
@@ -614,6 +681,12 @@ private:
     rt_denoise_params denoiseParams_ = RayTracerHIP::denoiseDefaults();
     bool varGuided_ = false, momValid_ = false;
     rt_denoise_var_params varParams_ = RayTracerHIP::denoiseVarDefaults();
+    /* setConverge: on; whether the last traced display converged; the frames in the view's moments */
+    bool converge_ = false, converged_ = false, noiseMapReadback_ = false;
+    unsigned convergeMinFrames_ = 8, frames_ = 0;
+    rt_noise_params convergeParams_ = RayTracerHIP::noiseDefaults();
+    rt_noise_stats noiseStats_{};
+    std::vector<float> noiseMap_;
     bool toneMap_ = false, autoExposure_ = true, exposureReset_ = true, floatReadback_ = true;
     rt_tonemap_params toneParams_ = RayTracerHIP::toneMapDefaults();
     rt_meter_params meterParams_ = RayTracerHIP::meterDefaults();

@@ -437,6 +437,32 @@ public:
         check(rt_last_tonemap_ms(ctx_, meter ? &ms : nullptr, meter ? nullptr : &ms), "lastToneMapMs");
         return ms;
     }
+    /* (no counterpart in the reference) the noise meter */
+    static rt_noise_params noiseDefaults()
+    {
+        rt_noise_params p;
+        rt_noise_defaults(&p);
+        return p;
+    }
+    /* Meter the RGBA32F frame with the variance plane of its luminance (variance's output): *stats_out
+       the level and the counts; tiles_out: NULL, or ceil(W/8) ceil(H/8) pairs (mean, max); hist_out: NULL,
+       or RT_METER_BINS counts.  sync = false (device buffers): enqueued on the tracer's stream without a wait. */
+    void noiseMeter(const float *rgba, const float *var, rt_noise_stats *stats_out, float *tiles_out, uint32_t *hist_out,
+                    unsigned width, unsigned height, const rt_noise_params &params = noiseDefaults(), bool on_device = false,
+                    bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_noise_meter(ctx_, rgba, var, stats_out, tiles_out, hist_out, width, height, &params, flags)
+                   : rt_noise_meter_async(ctx_, rgba, var, stats_out, tiles_out, hist_out, width, height, &params, flags, nullptr),
+              "noiseMeter");
+    }
+    /* Device time of the last noise meter, ms. */
+    float lastNoiseMs() const
+    {
+        float ms = 0.0f;
+        check(rt_last_noise_ms(ctx_, &ms), "lastNoiseMs");
+        return ms;
+    }
 
     rt_counters counters() const
     {

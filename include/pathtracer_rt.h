@@ -615,6 +615,54 @@ int rt_tonemap_async(rt_ctx *ctx, const float *rgba, const float *exposure, uint
    asked for has not run. */
 int rt_last_tonemap_ms(const rt_ctx *ctx, float *meter_ms, float *tonemap_ms);
 
+/* ---- the noise meter: how good is the frame on screen?  The variance plane of a
+   frame's luminance (rt_variance's output, or rt_denoise_var's out_var) reduced to a histogram of the
+   relative standard error, a per-tile map and one figure a host can act on.  The rules of the calls
+   above hold: display only, no render state is changed, both inputs are only read, the same stream
+   ordering, arithmetic that a float32 restatement reproduces to the bit (no contraction, IEEE division
+   and square root, rt_math.h's rt_maxf; lum as above).  `flags` takes RT_OUT_DEVICE only: with it every
+   buffer of a call is a device pointer, stats_out included (the figure then stays on the device, as the
+   meter's exposure does); without it every buffer is host memory and the library stages them. ---- */
+typedef struct rt_noise_params {
+    float percentile; /* the share of the counted pixels whose error the level bounds, in (0, 1] */
+    float threshold;  /* the relative error `below` counts against; >= 0 */
+    float lum_floor;  /* added to the luminance under the error, so that black pixels count; > 0, finite */
+} rt_noise_params;
+typedef struct rt_noise_stats {
+    float level;      /* an upper bound of the percentile's relative error: its bin's upper edge */
+    uint32_t counted; /* the valid pixels */
+    uint32_t skipped; /* width height - counted */
+    uint32_t below;   /* the pixels in bins whose upper edge is <= threshold */
+} rt_noise_stats;
+int rt_noise_defaults(rt_noise_params *p); /* 0.95f, 0.05f, 1e-3f */
+/* Per pixel p: L = lum(rgba_p), v = var_p.  The pixel is valid when v >= 0, v is finite and L is
+   finite; any other is skipped and joins no bin and no tile figure.  For a valid pixel Lp = L > 0 ? L
+   : 0, e = rt_sqrtf(v) / (Lp + lum_floor) (one square root, one add, one division), u = bits(e) &
+   0x7fffffff, bin min(max((int)(u >> 19) - 1776, 0), 383): rt_meter_exposure's RT_METER_BINS bins, so
+   e = 0 is in bin 0 and anything from 2^8 upward in bin 383.  hist_out: NULL, or RT_METER_BINS counts.
+   tiles_out: NULL, or ceil(width / 8) x ceil(height / 8) pairs (mean, max), row-major, one for each
+   8x8 tile: with j = (y & 7) 8 + (x & 7) and a_j = e for a valid pixel inside the frame, else 0.0f,
+   the sum is lane 0's after the butterfly a_j = a_j + a_(j ^ (1 << k)), k = 0..5, all lanes at once
+   (the additions commute: every lane holds the same bits), the maximum lane 0's after the same
+   butterfly with a_j = rt_maxf(a_j, a_(j ^ (1 << k))); mean = sum / (float)n_valid, one division, and
+   with n_valid == 0 both are 0.0f.
+   The statistic, from the counts n_i in index order: N = sum n_i (uint64), counted = N, skipped =
+   width height - N.  N == 0: level = 0.0f, below = 0.  Else r = min((uint64)((double)percentile
+   (double)N), N - 1), i the first bin whose running count exceeds r, level = that bin's upper edge
+   u2f((i + 1777) << 19), +INFINITY for bin 383; below = the sum of n_i over the bins whose upper edge
+   is <= threshold.  The level is at most 17/16 of the true percentile where that lies in [2^-16, 2^8).
+   Null rgba, var, stats_out or params, an empty frame, percentile outside (0, 1], threshold negative
+   or NaN, lum_floor not positive and finite, an output overlapping an input or another output:
+   RT_ERR_ARG. */
+int rt_noise_meter(rt_ctx *ctx, const float *rgba, const float *var, rt_noise_stats *stats_out, float *tiles_out,
+                   uint32_t *hist_out, uint32_t width, uint32_t height, const rt_noise_params *params, int flags);
+int rt_noise_meter_async(rt_ctx *ctx, const float *rgba, const float *var, rt_noise_stats *stats_out, float *tiles_out,
+                         uint32_t *hist_out, uint32_t width, uint32_t height, const rt_noise_params *params, int flags,
+                         void *hip_stream);
+/* Device time of the last noise meter (the histogram's reset, both kernels; HIP events of its own), ms.
+   RT_ERR_STATE when it has not run. */
+int rt_last_noise_ms(const rt_ctx *ctx, float *ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

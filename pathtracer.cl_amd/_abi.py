@@ -206,6 +206,15 @@ class RtMeterParams(ctypes.Structure):
                 ("e_max", ctypes.c_float), ("rate", ctypes.c_float)]
 
 
+class RtNoiseParams(ctypes.Structure):
+    _fields_ = [("percentile", ctypes.c_float), ("threshold", ctypes.c_float), ("lum_floor", ctypes.c_float)]
+
+
+class RtNoiseStats(ctypes.Structure):
+    _fields_ = [("level", ctypes.c_float), ("counted", ctypes.c_uint32), ("skipped", ctypes.c_uint32),
+                ("below", ctypes.c_uint32)]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -302,6 +311,11 @@ SIGNATURES = {
     "rt_tonemap": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTonemapParams), _i32]),
     "rt_tonemap_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTonemapParams), _i32, _vp]),
     "rt_last_tonemap_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    # the noise meter (csrc/rt_noise.hip)
+    "rt_noise_defaults": (_i32, [ctypes.POINTER(RtNoiseParams)]),
+    "rt_noise_meter": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtNoiseParams), _i32]),
+    "rt_noise_meter_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtNoiseParams), _i32, _vp]),
+    "rt_last_noise_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

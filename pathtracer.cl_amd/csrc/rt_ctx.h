@@ -104,7 +104,7 @@ static_assert((kCounterBytes + kWorkWords * sizeof(uint32_t)) % sizeof(unsigned 
 constexpr bool kLightCone = true;
 
 /* the display-side stages with a kernel time of their own (rt_display.cpp) */
-enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_METER, RT_ST_TONEMAP, RT_ST_WARP_SPH, RT_ST_COUNT };
+enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_METER, RT_ST_TONEMAP, RT_ST_WARP_SPH, RT_ST_NOISE, RT_ST_COUNT };
 
 struct rt_ctx {
     int device = 0;
@@ -304,6 +304,7 @@ struct rt_ctx {
     DevBuf<float> d_var_tmp[2]; /* ... and their variance planes */
     DevBuf<float> d_dn_stage;   /* host buffers' staging */
     DevBuf<uint32_t> d_meter_hist; /* rt_meter_exposure without hist_out: the meter's RT_METER_BINS counts */
+    DevBuf<uint32_t> d_noise_hist; /* rt_noise_meter without hist_out, likewise */
     struct StageTime {
         Event e0, e1;
         bool have = false;

@@ -2,8 +2,8 @@
  * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
  * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
  * §4.10), the trust of the carried history (rt_temporal.hip, §4.14), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13) and of moved spheres on the earlier ones (§4.16), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
- * (rt_filter.hip, §4.9 and §4.11), the meter and the tone map to 8 bits (rt_tonemap.hip, §4.15), with
- * their kernel times.  Every call runs through one driver
+ * (rt_filter.hip, §4.9 and §4.11), the meter and the tone map to 8 bits (rt_tonemap.hip, §4.15) and the
+ * noise meter (rt_noise.hip, §4.17), with their kernel times.  Every call runs through one driver
  * (AuxCall).
  */
 #include <cmath>
@@ -730,6 +730,77 @@ try {
     if (meter_ms)
         if (const int r = stage_ms(c, RT_ST_METER, meter_ms)) return r;
     return tonemap_ms ? stage_ms(c, RT_ST_TONEMAP, tonemap_ms) : RT_OK;
+} RT_CATCH(err_of(c))
+
+/* ---- the noise meter ------------------------------------- */
+
+int rt_noise_defaults(rt_noise_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->percentile = 0.95f;
+    p->threshold = 0.05f;
+    p->lum_floor = 1e-3f;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_noise_meter_async(rt_ctx *c, const float *rgba, const float *var, rt_noise_stats *stats_out, float *tiles_out,
+                         uint32_t *hist_out, uint32_t W, uint32_t H, const rt_noise_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!rgba || !var || !stats_out || !prm) return fail(c, RT_ERR_ARG, "rt_noise_meter: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_noise_meter: flags other than RT_OUT_DEVICE");
+    if (!(prm->percentile > 0.0f && prm->percentile <= 1.0f)) return fail(c, RT_ERR_ARG, "rt_noise_meter: percentile outside (0, 1]");
+    if (!(prm->threshold >= 0.0f)) return fail(c, RT_ERR_ARG, "rt_noise_meter: threshold negative or NaN");
+    if (!(prm->lum_floor > 0.0f && prm->lum_floor < rt_inff()))
+        return fail(c, RT_ERR_ARG, "rt_noise_meter: lum_floor is not positive and finite");
+    const size_t px = (size_t)W * H, tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    /* every output apart from both inputs and from the other outputs (addresses of one kind: all host or all device) */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } buf[] = {{rgba, 4 * px * sizeof(float)},          {var, px * sizeof(float)},
+               {stats_out, sizeof(rt_noise_stats)},     {tiles_out, 2 * tiles * sizeof(float)},
+               {hist_out, RT_METER_BINS * sizeof(uint32_t)}};
+    for (int o = 2; o < 5; ++o)
+        for (int i = 0; i < o; ++i) {
+            const uintptr_t a = (uintptr_t)buf[o].p, b = (uintptr_t)buf[i].p;
+            if (a && b && a < b + buf[i].bytes && b < a + buf[o].bytes)
+                return fail(c, RT_ERR_ARG, "rt_noise_meter: an output overlaps an input or another output");
+        }
+    AuxCall x = {c, RT_ST_NOISE};
+    if (const int r = x.open(stream, flags)) return r;
+    /* staged: the frame, the variance plane, then the words of the stats, the counts and the tile pairs */
+    constexpr size_t kStatWords = sizeof(rt_noise_stats) / sizeof(float);
+    const Plane pl[] = {{rgba, nullptr, 0, 4 * px},
+                        {var, nullptr, 4 * px, px},
+                        {nullptr, reinterpret_cast<float *>(stats_out), 5 * px, kStatWords},
+                        {nullptr, reinterpret_cast<float *>(hist_out), 5 * px + kStatWords, RT_METER_BINS},
+                        {nullptr, tiles_out, 5 * px + kStatWords + RT_METER_BINS, 2 * tiles}};
+    if (!x.host && !hist_out) HIPCHK(c, c->d_noise_hist.reserve(RT_METER_BINS)); /* (allocated once, never grown) */
+    if (const int r = x.begin(pl, 5, 5 * px + kStatWords + RT_METER_BINS + 2 * tiles)) return r;
+    uint32_t *hist = x.host || hist_out ? reinterpret_cast<uint32_t *>(x.at(3, reinterpret_cast<float *>(hist_out)))
+                                        : c->d_noise_hist.p;
+    float *dtiles = tiles_out ? x.at(4, tiles_out) : nullptr;
+    int e = rt_launch_noise_hist(x.at(0, rgba), x.at(1, var), W, H, prm->lum_floor, hist, dtiles, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "noise histogram kernel launch");
+    e = rt_launch_noise_stat(hist, W, H, prm->percentile, prm->threshold,
+                             reinterpret_cast<rt_noise_stats *>(x.at(2, reinterpret_cast<float *>(stats_out))), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "noise statistic kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_noise_meter(rt_ctx *c, const float *rgba, const float *var, rt_noise_stats *stats_out, float *tiles_out,
+                   uint32_t *hist_out, uint32_t W, uint32_t H, const rt_noise_params *prm, int flags)
+try {
+    return finish_sync(c, rt_noise_meter_async(c, rgba, var, stats_out, tiles_out, hist_out, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_noise_ms(const rt_ctx *c, float *ms)
+try {
+    if (!c || !ms) return RT_ERR_ARG;
+    if (!c->stage_time[RT_ST_NOISE].have) return RT_ERR_STATE;
+    return stage_ms(c, RT_ST_NOISE, ms);
 } RT_CATCH(err_of(c))
 
 } /* extern "C" */

@@ -183,7 +183,8 @@ int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, v
 size_t rt_refit_nbox_bytes(void);
 
 /* ---- the render kernels' launch structs and launchers (rt_tris.hip, rt_split.hip, rt_spheres.hip,
-   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_motion.hip, rt_filter.hip, rt_tonemap.hip) ---- */
+   rt_lists.hip, rt_sched.hip, rt_features.hip, rt_temporal.hip, rt_motion.hip, rt_filter.hip, rt_tonemap.hip,
+   rt_noise.hip) ---- */
 #ifndef RT_QHEADS
 #define RT_QHEADS 8 /* heads of the multi-head pixel queue (k_tris mq_take) */
 #endif
@@ -495,5 +496,14 @@ struct RtToneLaunch {
     float exposure_fixed, iw;
 };
 int rt_launch_tonemap(const RtToneLaunch &a, void *stream);
+/* -- rt_noise.hip -- */
+/* The noise meter: device buffers.  hist (RT_METER_BINS words) is zeroed on the stream
+   and then counted into; tiles: NULL, or ceil(W/8) ceil(H/8) pairs of floats.  The statistic reads hist
+   and writes *stats. */
+struct rt_noise_stats; /* pathtracer_rt.h */
+int rt_launch_noise_hist(const float *rgba, const float *var, uint32_t W, uint32_t H, float lum_floor, uint32_t *hist,
+                         float *tiles, void *stream);
+int rt_launch_noise_stat(const uint32_t *hist, uint32_t W, uint32_t H, float percentile, float threshold,
+                         rt_noise_stats *stats, void *stream);
 
 #endif /* RT_INTERNAL_H */

@@ -47,6 +47,11 @@
  *              [--ppm FILE] (binary P6 of the final shown 8-bit frame, top row first: flipped like the PFM)
  *              [--frames8-out FILE] (with --events: every displayed RGBA8 frame, appended as W*H words)
  *              [--exposure-log FILE] (with --events: per displayed frame the bits of its exposure, one hex word a line))
+ *             [--converge [THRESHOLD]]   (with --events: the view refines until converged
+ *              (ProgressiveViewHIP::setConverge: the noise meter's level at or under THRESHOLD, default
+ *              rt_noise_defaults'); the event lines gain "converged") [--converge-percentile Q] [--converge-min-frames N]
+ *              [--noise-log FILE] (per traced display one line: the level's bits in hex, counted, skipped, below,
+ *              converged 0 / 1) [--noise-map-out FILE] (the tile planes of the traced displays, appended as float pairs)
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -149,7 +154,8 @@ int usage()
                          "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
                          "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--sphere-carry [MAXHIST]] (--events o:I:DX:DY:DZ[:DR] moves sphere I) [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
-                         "[--ppm f] [--frames8-out f] [--exposure-log f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
+                         "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
+                         "[--noise-log f] [--noise-map-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
 
@@ -217,6 +223,10 @@ int main(int argc, char **argv)
     rt_tonemap_params tone_params = RayTracerHIP::toneMapDefaults();
     rt_meter_params meter_params = RayTracerHIP::meterDefaults();
     rt_trust_params trust_params = RayTracerHIP::trustDefaults();
+    bool converge = false;
+    rt_noise_params noise_params = RayTracerHIP::noiseDefaults();
+    unsigned converge_min_frames = 8;
+    std::string noise_log, noise_map_out;
     float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
@@ -278,8 +288,17 @@ int main(int argc, char **argv)
             if ((v = optional_number(argc, argv, i))) var_params.sigma_lum = (float)std::atof(v);
             continue;
         }
+        if (a == "--converge") { /* an optional threshold follows */
+            converge = true;
+            if ((v = optional_number(argc, argv, i))) noise_params.threshold = (float)std::atof(v);
+            continue;
+        }
         if (!(v = next())) return usage();
         if (a == "--scene") scene = v;
+        else if (a == "--converge-percentile") noise_params.percentile = (float)std::atof(v);
+        else if (a == "--converge-min-frames") converge_min_frames = (unsigned)std::atoi(v);
+        else if (a == "--noise-log") noise_log = v;
+        else if (a == "--noise-map-out") noise_map_out = v;
         else if (a == "--denoised") den_raw = v;
         else if (a == "--denoised-pfm") den_pfm = v;
         else if (a == "--features-out") feat_out = v;
@@ -354,6 +373,14 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --variance-guided needs --events (it follows a view's progressive frames)\n");
         return 2;
     }
+    if (converge && events.empty()) {
+        std::fprintf(stderr, "rt_render: --converge needs --events (it follows a view's progressive frames)\n");
+        return 2;
+    }
+    if (!converge && (!noise_log.empty() || !noise_map_out.empty())) {
+        std::fprintf(stderr, "rt_render: --noise-log / --noise-map-out need --converge (nothing is metered without it)\n");
+        return 2;
+    }
     try {
         RayTracerHIP rt(device);
         add_scene(rt, ply);
@@ -390,6 +417,8 @@ int main(int argc, char **argv)
             if (trust) view.setHistoryTrust(true, trust_params);
             if (sphere_carry) view.setSphereCarry(true, sphere_max_history);
             if (tonemap) view.setToneMap(true, tone_params, auto_exposure, meter_params);
+            if (converge) view.setConverge(true, noise_params, converge_min_frames);
+            if (!noise_map_out.empty()) view.setNoiseMapReadback(true);
             rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
             SphereOffsets sphere_offsets{};            /* the o events so far */
             std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
@@ -412,6 +441,9 @@ int main(int argc, char **argv)
             FILE *f8 = frames8_out.empty() ? nullptr : std::fopen(frames8_out.c_str(), "wb");
             FILE *fe = exposure_log.empty() ? nullptr : std::fopen(exposure_log.c_str(), "w");
             if ((!frames8_out.empty() && !f8) || (!exposure_log.empty() && !fe)) return 1;
+            FILE *fn = noise_log.empty() ? nullptr : std::fopen(noise_log.c_str(), "w");
+            FILE *fm = noise_map_out.empty() ? nullptr : std::fopen(noise_map_out.c_str(), "wb");
+            if ((!noise_log.empty() && !fn) || (!noise_map_out.empty() && !fm)) return 1;
             size_t pos = 0;
             while (pos <= events.size()) {
                 const size_t end = std::min(events.find(',', pos), events.size());
@@ -432,6 +464,13 @@ int main(int argc, char **argv)
                         std::memcpy(&u, &e, 4);
                         std::fprintf(fe, "%08x\n", u);
                     }
+                    if (traced && fn) {
+                        const rt_noise_stats &ns = view.noiseStats();
+                        uint32_t u;
+                        std::memcpy(&u, &ns.level, 4);
+                        std::fprintf(fn, "%08x %u %u %u %d\n", u, ns.counted, ns.skipped, ns.below, view.converged() ? 1 : 0);
+                    }
+                    if (traced && fm && !append(fm, view.noiseMap())) return 1;
                     if (traced && ff) {
                         std::vector<float> ft((size_t)view.width() * view.height() * 8);
                         rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
@@ -476,6 +515,7 @@ int main(int argc, char **argv)
                             ev.c_str(), traced ? "true" : "false", post ? "true" : "false", view.progression(),
                             view.azimuth(), view.elevation(), view.width(), view.height());
                 if (mesh_update) std::printf(", \"mesh_update\": \"%s\"", mesh_update);
+                if (converge) std::printf(", \"converged\": %s", view.converged() ? "true" : "false");
                 std::printf("}\n");
             }
             if (fo) std::fclose(fo);
@@ -483,6 +523,8 @@ int main(int argc, char **argv)
             if (ff) std::fclose(ff);
             if (f8) std::fclose(f8);
             if (fe) std::fclose(fe);
+            if (fn) std::fclose(fn);
+            if (fm) std::fclose(fm);
             if (!ppm.empty() && (view.pixels8().empty() || !write_ppm(ppm, view.pixels8(), view.width(), view.height()))) return 1;
             std::printf("{\"progression\": %u, \"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, "
                         "\"height\": %u}\n",

@@ -661,6 +661,64 @@ class RayTracer:
         self._check(self._lib.rt_last_tonemap_ms(self._h, a, b), "rt_last_tonemap_ms")
         return ms.value
 
+    # ---- the noise meter (pathtracer_rt.h) ----
+    def noiseDefaults(self) -> dict:
+        prm = _abi.RtNoiseParams()
+        self._check(self._lib.rt_noise_defaults(ctypes.byref(prm)), "rt_noise_defaults")
+        return dict(percentile=prm.percentile, threshold=prm.threshold, lum_floor=prm.lum_floor)
+
+    def noiseMeter(self, rgba, var, width: int, height: int, percentile: float | None = None,
+                   threshold: float | None = None, lum_floor: float | None = None, tiles=None, hist=None, stats=None,
+                   stream=None, sync: bool = True):
+        """Meter the RGBA32F frame `rgba` with the variance plane of its luminance `var` (W*H floats,
+        `variance`): the relative standard error sqrt(var) / (max(lum, 0) + lum_floor) per pixel, its
+        histogram into `hist` (None, or 384 uint32 / int32 words), per 8x8 tile its (mean, max) into
+        `tiles` (None, or ceil(W/8) ceil(H/8) pairs of float32).  Returns the stats as a dict: `level`
+        (np.float32, an upper bound of the error at `percentile`), `counted`, `skipped`, `below` (the
+        pixels in bins at or under `threshold`).  None for a parameter: the library's default.  All
+        numpy arrays or all torch CUDA tensors; the inputs are only read.  `stats` (4 uint32 / int32
+        words of the buffers' kind) receives the struct's words as well; with sync=False it must be
+        given, nothing is read back and None is returned."""
+        px = int(width) * int(height)
+        n_tiles = ((int(width) + 7) // 8) * ((int(height) + 7) // 8)
+        flags = [self._frame_buffer(rgba, px * 4, "frame"), self._frame_buffer(var, px, "variance")]
+        if tiles is not None:
+            flags.append(self._frame_buffer(tiles, 2 * n_tiles, "tile map"))
+        if hist is not None:
+            flags.append(self._word_buffer(hist, _abi.RT_METER_BINS, "histogram"))
+        if stats is not None:
+            flags.append(self._word_buffer(stats, 4, "stats"))
+        if len(set(flags)) != 1:
+            raise ValueError("noiseMeter: the buffers must all be host arrays or all device tensors")
+        if stats is None:
+            if not sync:
+                raise ValueError("noiseMeter: sync=False needs a stats buffer")
+            if flags[0]:
+                import torch
+
+                stats = torch.zeros(4, dtype=torch.int32, device=rgba.device)
+            else:
+                stats = np.zeros(4, np.uint32)
+        d = self.noiseDefaults()
+        for k, v in (("percentile", percentile), ("threshold", threshold), ("lum_floor", lum_floor)):
+            if v is not None:
+                d[k] = float(v)
+        prm = _abi.RtNoiseParams(d["percentile"], d["threshold"], d["lum_floor"])
+        args = (self._h, _abi.ptr(rgba), _abi.ptr(var), _abi.ptr(stats), _abi.ptr(tiles), _abi.ptr(hist), int(width),
+                int(height), ctypes.byref(prm), flags[0])
+        self._aux_call("rt_noise_meter", args, stream, sync)
+        if not sync:
+            return None
+        w = stats if isinstance(stats, np.ndarray) else stats.cpu().numpy()
+        w = np.ascontiguousarray(w).view(np.uint32)
+        return dict(level=w[:1].view(np.float32)[0], counted=int(w[1]), skipped=int(w[2]), below=int(w[3]))
+
+    def lastNoiseMs(self) -> float:
+        """Device time of the last noise meter, ms."""
+        ms = ctypes.c_float()
+        self._check(self._lib.rt_last_noise_ms(self._h, ctypes.byref(ms)), "rt_last_noise_ms")
+        return ms.value
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
