@@ -1,12 +1,22 @@
 /*
- * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime): first-hit
- * features (rt_features.hip), temporal reprojection and merge (rt_temporal.hip,
- * §4.10), the trust of the carried history (rt_temporal.hip, §4.14), the features of a moving mesh in an earlier pose (rt_motion.hip, §4.13) and of moved spheres on the earlier ones (§4.16), the edge-avoiding denoiser, luminance moments, variance and the variance-guided filter
- * (rt_filter.hip, §4.9 and §4.11), the meter and the tone map to 8 bits (rt_tonemap.hip, §4.15) and the
- * noise meter (rt_noise.hip, §4.17), with their kernel times.  Every call runs through one driver
- * (AuxCall).
+ * rt_display.cpp — the display-side stages of a context (librtmi.so host runtime), with their
+ * kernel times:
+ *
+ *   first-hit features                                        rt_features.hip   DESIGN.md §4.9
+ *   the edge-avoiding denoiser                                rt_filter.hip     §4.9
+ *   temporal reprojection and merge                           rt_temporal.hip   §4.10
+ *   luminance moments, variance, the variance-guided filter   rt_filter.hip     §4.11
+ *   the features of a moving mesh in an earlier pose          rt_motion.hip     §4.13
+ *   the trust of the carried history                          rt_temporal.hip   §4.14
+ *   the meter and the tone map to 8 bits                      rt_tonemap.hip    §4.15
+ *   the features of moved spheres on the earlier ones         rt_motion.hip     §4.16
+ *   the noise meter                                           rt_noise.hip      §4.17
+ *
+ * Every call runs through one driver (AuxCall), which also lays out the staging area of a call on
+ * host buffers.
  */
 #include <cmath>
+#include <initializer_list>
 
 #include "rt_ctx.h"
 #include "rt_math.h"
@@ -45,12 +55,13 @@ int ensure_dev(rt_ctx *c, DevBuf<float> &buf, size_t floats)
 
 bool frame_ok(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H < (1ull << 28); }
 
-/* One plane of a call's staging area (host buffers only): `floats` floats at `off`, uploaded from
-   `up` before the kernels and downloaded to `down` after them (either may be null). */
+/* One plane of a call's staging area (host buffers only): `floats` floats (or 32-bit words),
+   uploaded from `up` before the kernels and downloaded to `down` after them (either may be null;
+   both for a plane used in place there). */
 struct Plane {
     const float *up;
     float *down;
-    size_t off, floats;
+    size_t floats;
 };
 
 /* The driver of a display-side call: open (device, stream), begin (the staging area for host
@@ -61,8 +72,10 @@ struct AuxCall {
     RtStage stage;
     hipStream_t st = nullptr;
     bool host = false;
+    static constexpr int kMaxPlanes = 6;
     const Plane *planes = nullptr;
     int n_planes = 0;
+    size_t off[kMaxPlanes] = {}; /* the planes in declaration order, each 16-byte aligned (float4 streams, px may be odd) */
 
     int open(void *stream, int flags)
     {
@@ -72,18 +85,25 @@ struct AuxCall {
         return RT_OK;
     }
     /* plane i on the device (after begin): in the staging area, or the caller's own buffer */
-    float *at(int i, const float *dev) const { return host ? c->d_dn_stage + planes[i].off : const_cast<float *>(dev); }
-    int begin(const Plane *pl, int n, size_t floats)
+    float *at(int i, const float *dev) const { return host ? c->d_dn_stage + off[i] : const_cast<float *>(dev); }
+    uint32_t *words(int i, const void *dev) const { return reinterpret_cast<uint32_t *>(at(i, static_cast<const float *>(dev))); }
+    int begin(const Plane *pl, int n)
     {
+        if (n > kMaxPlanes) return fail(c, RT_ERR_ARG, "display call: too many staged planes");
         planes = pl;
         n_planes = n;
+        size_t floats = 0;
+        for (int i = 0; i < n; ++i) {
+            off[i] = floats;
+            floats += (pl[i].floats + 3) & ~(size_t)3;
+        }
         if (host)
             if (const int r = ensure_dev(c, c->d_dn_stage, floats)) return r;
         if (const int r = aux_begin(c, st)) return r;
         if (host)
             for (int i = 0; i < n_planes; ++i)
                 if (planes[i].up)
-                    HIPCHK(c, hipMemcpyAsync(c->d_dn_stage + planes[i].off, planes[i].up, planes[i].floats * sizeof(float),
+                    HIPCHK(c, hipMemcpyAsync(c->d_dn_stage + off[i], planes[i].up, planes[i].floats * sizeof(float),
                                              hipMemcpyHostToDevice, st));
         HIPCHK(c, hipEventRecord(c->stage_time[stage].e0, st));
         return RT_OK;
@@ -95,7 +115,7 @@ struct AuxCall {
         if (host)
             for (int i = 0; i < n_planes; ++i)
                 if (planes[i].down)
-                    HIPCHK(c, hipMemcpyAsync(planes[i].down, c->d_dn_stage + planes[i].off, planes[i].floats * sizeof(float),
+                    HIPCHK(c, hipMemcpyAsync(planes[i].down, c->d_dn_stage + off[i], planes[i].floats * sizeof(float),
                                              hipMemcpyDeviceToHost, st));
         return aux_end(c, st);
     }
@@ -109,12 +129,50 @@ int finish_sync(rt_ctx *c, int r)
     return RT_OK;
 }
 
-/* a stage's kernel time, once it has run */
-int stage_ms(const rt_ctx *c, RtStage s, float *ms)
+/* The kernel times of the stages asked for (a null `ms`: not this one; one at least), once each of
+   those has run: none is read before all of them have. */
+struct StageOut {
+    RtStage stage;
+    float *ms;
+};
+int last_ms(const rt_ctx *c, std::initializer_list<StageOut> want)
 {
-    const rt_ctx::StageTime &t = c->stage_time[s];
-    if (hipEventSynchronize(t.e1) != hipSuccess) return RT_ERR_HIP;
-    return hipEventElapsedTime(ms, t.e0, t.e1) == hipSuccess ? RT_OK : RT_ERR_HIP;
+    if (!c) return RT_ERR_ARG;
+    bool any = false;
+    for (const StageOut &w : want) {
+        if (w.ms && !c->stage_time[w.stage].have) return RT_ERR_STATE;
+        any |= w.ms != nullptr;
+    }
+    if (!any) return RT_ERR_ARG;
+    for (const StageOut &w : want) {
+        if (!w.ms) continue;
+        const rt_ctx::StageTime &t = c->stage_time[w.stage];
+        if (hipEventSynchronize(t.e1) != hipSuccess) return RT_ERR_HIP;
+        if (hipEventElapsedTime(w.ms, t.e0, t.e1) != hipSuccess) return RT_ERR_HIP;
+    }
+    return RT_OK;
+}
+
+/* 1 / sigma^2 in float: the inverse variance of a weight's term (+INFINITY: 0, the term is off) */
+float inv_sq(float sigma) { return 1.0f / (sigma * sigma); }
+
+/* whether [a, a + na) and [b, b + nb) share a byte (addresses of one kind: all host or all device; a
+   null buffer shares none) */
+bool overlaps(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x && y && x < y + nb && y < x + na;
+}
+
+/* Where a meter counts on device buffers: the caller's histogram, or without one the context's own
+   (allocated once, never grown).  On host buffers the counts are a plane of the staging area. */
+int dev_hist(AuxCall &x, uint32_t *hist_out, DevBuf<uint32_t> &own, uint32_t *&hist)
+{
+    hist = hist_out;
+    if (x.host || hist_out) return RT_OK;
+    HIPCHK(x.c, own.reserve(RT_METER_BINS));
+    hist = own.p;
+    return RT_OK;
 }
 
 /* The a-trous passes' ping-pong: pass i reads the previous pass's output (pass 0: the input) and
@@ -127,9 +185,9 @@ float *pass_dst(bool last, float *out, const float *src, DevBuf<float> tmp[2])
 
 /* The passes of rt_denoise (in_var null) and of rt_denoise_var, from the scratch buffers to the
    call's end.  pl: the call's planes — colour (filtered in place in the staging area: the last pass
-   never reads its destination), the two feature planes, then with in_var the variance plane —
-   `floats` in all.  sigma: sigma_color, its tolerance halving every pass, or sigma_lum. */
-int atrous_passes(AuxCall &x, const Plane *pl, size_t floats, const float *in, const float *in_var, const float *feat,
+   never reads its destination), the two feature planes, then with in_var the variance plane.
+   sigma: sigma_color, its tolerance halving every pass, or sigma_lum. */
+int atrous_passes(AuxCall &x, const Plane *pl, const float *in, const float *in_var, const float *feat,
                   float *out, float *out_var, uint32_t W, uint32_t H, uint32_t n, float sigma, int lum_on, float isn,
                   float isp)
 {
@@ -140,7 +198,7 @@ int atrous_passes(AuxCall &x, const Plane *pl, size_t floats, const float *in, c
         if (in_var)
             if (const int r = ensure_dev(c, c->d_var_tmp[k], px)) return r;
     }
-    if (const int r = x.begin(pl, in_var ? 3 : 2, floats)) return r;
+    if (const int r = x.begin(pl, in_var ? 3 : 2)) return r;
     float *dout = x.at(0, out), *dvout = !in_var || (x.host && !out_var) ? nullptr : x.at(2, out_var);
     /* each pass reads the one before it (col, var) and sets its own outputs, step and colour parameter */
     RtAtrousLaunch a = {x.at(0, in), in_var ? x.at(2, in_var) : nullptr, x.at(1, feat), nullptr, nullptr, W, H, 0, 0.0f,
@@ -150,8 +208,7 @@ int atrous_passes(AuxCall &x, const Plane *pl, size_t floats, const float *in, c
         a.out = pass_dst(last, dout, a.col, c->d_dn_tmp);
         a.out_var = in_var ? pass_dst(last, dvout, a.var, c->d_var_tmp) : nullptr;
         a.step = 1u << i;
-        const float sc = ldexpf(sigma, -(int)i);
-        a.colour = in_var ? sigma : 1.0f / (sc * sc);
+        a.colour = in_var ? sigma : inv_sq(ldexpf(sigma, -(int)i));
         const int e = rt_launch_atrous(a, x.st);
         if (e) return hip_fail(c, (hipError_t)e, "filter kernel launch");
         a.col = a.out;
@@ -178,7 +235,7 @@ try {
     AuxCall x = {c, RT_ST_FEATURES};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    const Plane pl[] = {{nullptr, feat, 0, 8 * px}};
+    const Plane pl[] = {{nullptr, feat, 8 * px}};
     RtFeatLaunch a{};
     a.cam = frame_camera(c, W);
     a.W = W;
@@ -200,7 +257,7 @@ try {
         a.spheres = c->d_spheres;
         a.n_spheres = (uint32_t)c->spheres.size();
     }
-    if (const int r = x.begin(pl, 1, 8 * px)) return r;
+    if (const int r = x.begin(pl, 1)) return r;
     a.feat = x.at(0, feat);
     const int e = rt_launch_features(a, trav, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "feature kernel launch");
@@ -233,15 +290,14 @@ try {
     const float sig[3] = {prm->sigma_color, prm->sigma_normal, prm->sigma_plane};
     for (float s : sig)
         if (!(s > 0.0f)) return fail(c, RT_ERR_ARG, "rt_denoise: a sigma is not positive"); /* <= 0 or NaN */
-    /* the inverse variances, in float (+INFINITY: 0, the term is off) */
-    const float isn = 1.0f / (sig[1] * sig[1]), isp = 1.0f / (sig[2] * sig[2]);
     AuxCall x = {c, RT_ST_DENOISE};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    /* staged: colour (filtered in place there: the last pass never reads its destination), then the
+    /* staged: colour (filtered in place there: the last pass never reads its destination) and the
        two feature planes */
-    const Plane pl[] = {{in, out, 0, 4 * px}, {feat, nullptr, 4 * px, 8 * px}};
-    return atrous_passes(x, pl, 12 * px, in, nullptr, feat, out, nullptr, W, H, prm->iterations, sig[0], 0, isn, isp);
+    const Plane pl[] = {{in, out, 4 * px}, {feat, nullptr, 8 * px}};
+    return atrous_passes(x, pl, in, nullptr, feat, out, nullptr, W, H, prm->iterations, sig[0], 0, inv_sq(sig[1]),
+                         inv_sq(sig[2]));
 } RT_CATCH(err_of(c))
 
 int rt_denoise(rt_ctx *c, const float *in, const float *feat, float *out, uint32_t W, uint32_t H,
@@ -252,16 +308,12 @@ try {
 
 int rt_last_features_ms(const rt_ctx *c, float *ms)
 try {
-    if (!c || !ms) return RT_ERR_ARG;
-    if (!c->stage_time[RT_ST_FEATURES].have) return RT_ERR_STATE;
-    return stage_ms(c, RT_ST_FEATURES, ms);
+    return last_ms(c, {{RT_ST_FEATURES, ms}});
 } RT_CATCH(err_of(c))
 
 int rt_last_denoise_ms(const rt_ctx *c, float *ms)
 try {
-    if (!c || !ms) return RT_ERR_ARG;
-    if (!c->stage_time[RT_ST_DENOISE].have) return RT_ERR_STATE;
-    return stage_ms(c, RT_ST_DENOISE, ms);
+    return last_ms(c, {{RT_ST_DENOISE, ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- temporal reprojection of the displayed frame ------- */
@@ -292,11 +344,9 @@ try {
     AuxCall x = {c, RT_ST_REPROJECT};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    /* staged: the float4 streams first (px may be odd), then the two length planes */
-    const Plane pl[] = {{prev_rgba, nullptr, 0, 4 * px},      {prev_feat, nullptr, 4 * px, 8 * px},
-                        {cur_feat, nullptr, 12 * px, 8 * px}, {prev_len, nullptr, 24 * px, px},
-                        {nullptr, out_rgba, 20 * px, 4 * px}, {nullptr, out_len, 25 * px, px}};
-    if (const int r = x.begin(pl, 6, 26 * px)) return r;
+    const Plane pl[] = {{prev_rgba, nullptr, 4 * px}, {prev_feat, nullptr, 8 * px}, {cur_feat, nullptr, 8 * px},
+                        {prev_len, nullptr, px},      {nullptr, out_rgba, 4 * px},  {nullptr, out_len, px}};
+    if (const int r = x.begin(pl, 6)) return r;
     const int e = rt_launch_reproject(x.at(0, prev_rgba), x.at(3, prev_len), x.at(1, prev_feat), *prev_cam, x.at(2, cur_feat),
                                       x.at(4, out_rgba), x.at(5, out_len), W, H, prm->plane_tol, prm->normal_min,
                                       prm->max_history, x.st);
@@ -328,8 +378,8 @@ try {
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
     /* staged, and merged in place there */
-    const Plane pl[] = {{hist_rgba, out_rgba, 0, 4 * px}, {cur_rgba, nullptr, 4 * px, 4 * px}, {hist_len, out_len, 8 * px, px}};
-    if (const int r = x.begin(pl, 3, 9 * px)) return r;
+    const Plane pl[] = {{hist_rgba, out_rgba, 4 * px}, {cur_rgba, nullptr, 4 * px}, {hist_len, out_len, px}};
+    if (const int r = x.begin(pl, 3)) return r;
     const int e = rt_launch_temporal_merge(x.at(0, hist_rgba), x.at(2, hist_len), x.at(1, cur_rgba), n_cur, max_history,
                                            x.at(0, out_rgba), x.at(2, out_len), W, H, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "temporal merge kernel launch");
@@ -345,12 +395,7 @@ try {
 
 int rt_last_reproject_ms(const rt_ctx *c, float *reproject_ms, float *merge_ms)
 try {
-    if (!c || (!reproject_ms && !merge_ms)) return RT_ERR_ARG;
-    if ((reproject_ms && !c->stage_time[RT_ST_REPROJECT].have) || (merge_ms && !c->stage_time[RT_ST_MERGE].have))
-        return RT_ERR_STATE;
-    if (reproject_ms)
-        if (const int r = stage_ms(c, RT_ST_REPROJECT, reproject_ms)) return r;
-    return merge_ms ? stage_ms(c, RT_ST_MERGE, merge_ms) : RT_OK;
+    return last_ms(c, {{RT_ST_REPROJECT, reproject_ms}, {RT_ST_MERGE, merge_ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- lag-adaptive trust of the carried history ----------- */
@@ -379,7 +424,6 @@ try {
         return fail(c, RT_ERR_ARG, "rt_history_trust: a sigma is not positive"); /* <= 0 or NaN */
     if (out_len == hist_rgba || out_len == cur_rgba || out_len == feat)
         return fail(c, RT_ERR_ARG, "rt_history_trust: the output is an input other than hist_len");
-    const float isn = 1.0f / (prm->sigma_normal * prm->sigma_normal), isp = 1.0f / (prm->sigma_plane * prm->sigma_plane);
     const bool all = prm->tolerance == rt_inff(); /* everything is trusted: hist_len's bits, no kernel */
     AuxCall x = {c, RT_ST_TRUST};
     if (const int r = x.open(stream, flags)) return r;
@@ -389,13 +433,12 @@ try {
     const bool in_place = !x.host && out_len == hist_len;
     if (in_place && !all)
         if (const int r = ensure_dev(c, c->d_var_tmp[0], px)) return r;
-    /* staged: the float4 streams first (px may be odd), then the two length planes */
-    const Plane pl[] = {{all ? nullptr : hist_rgba, nullptr, 0, 4 * px},
-                        {all ? nullptr : cur_rgba, nullptr, 4 * px, 4 * px},
-                        {all ? nullptr : feat, nullptr, 8 * px, 8 * px},
-                        {hist_len, nullptr, 16 * px, px},
-                        {nullptr, out_len, 17 * px, px}};
-    if (const int r = x.begin(pl, 5, 18 * px)) return r;
+    const Plane pl[] = {{all ? nullptr : hist_rgba, nullptr, 4 * px},
+                        {all ? nullptr : cur_rgba, nullptr, 4 * px},
+                        {all ? nullptr : feat, nullptr, 8 * px},
+                        {hist_len, nullptr, px},
+                        {nullptr, out_len, px}};
+    if (const int r = x.begin(pl, 5)) return r;
     const float *dlen = x.at(3, hist_len);
     float *dout = x.at(4, out_len);
     if (all) {
@@ -404,7 +447,8 @@ try {
     }
     float *dst = in_place ? c->d_var_tmp[0].p : dout;
     const int e = rt_launch_history_trust(x.at(0, hist_rgba), dlen, x.at(1, cur_rgba), n_cur, x.at(2, feat), dst, W, H,
-                                          prm->tolerance * prm->tolerance, isn, isp, x.st);
+                                          prm->tolerance * prm->tolerance, inv_sq(prm->sigma_normal),
+                                          inv_sq(prm->sigma_plane), x.st);
     if (e) return hip_fail(c, (hipError_t)e, "history trust kernel launch");
     if (in_place) HIPCHK(c, hipMemcpyAsync(dout, dst, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
     return x.end();
@@ -419,9 +463,7 @@ try {
 
 int rt_last_trust_ms(const rt_ctx *c, float *ms)
 try {
-    if (!c || !ms) return RT_ERR_ARG;
-    if (!c->stage_time[RT_ST_TRUST].have) return RT_ERR_STATE;
-    return stage_ms(c, RT_ST_TRUST, ms);
+    return last_ms(c, {{RT_ST_TRUST, ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- the features of a moving mesh in an earlier pose ---- */
@@ -439,8 +481,8 @@ try {
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
     /* staged: the two feature planes, warped in place there, then the earlier pose */
-    const Plane pl[] = {{cur_feat, out_feat, 0, 8 * px}, {prev_verts, nullptr, 8 * px, 3ull * n_verts}};
-    if (const int r = x.begin(pl, 2, 8 * px + 3ull * n_verts)) return r;
+    const Plane pl[] = {{cur_feat, out_feat, 8 * px}, {prev_verts, nullptr, 3ull * n_verts}};
+    if (const int r = x.begin(pl, 2)) return r;
     const int e = rt_launch_warp_features(x.at(0, cur_feat), c->d_idx, c->d_pose, x.at(1, prev_verts), c->n_tris, n_verts,
                                           x.at(0, out_feat), W, H, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "feature warp kernel launch");
@@ -455,9 +497,7 @@ try {
 
 int rt_last_warp_ms(const rt_ctx *c, float *ms)
 try {
-    if (!c || !ms) return RT_ERR_ARG;
-    if (!c->stage_time[RT_ST_WARP].have) return RT_ERR_STATE;
-    return stage_ms(c, RT_ST_WARP, ms);
+    return last_ms(c, {{RT_ST_WARP, ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- the features of moved spheres on the earlier spheres ---- */
@@ -472,22 +512,18 @@ try {
     if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
     if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_warp_features_spheres: flags other than RT_OUT_DEVICE");
     const size_t px = (size_t)W * H;
-    /* out_feat is cur_feat exactly, or apart from both inputs (addresses of one kind: all host or all device) */
-    const auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
-        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-        return x < y + nb && y < x + na;
-    };
+    /* out_feat is cur_feat exactly, or apart from both inputs */
     const size_t feat_bytes = 8 * px * sizeof(float), prev_bytes = (size_t)n_prev * sizeof(rt_sphere);
-    if ((out_feat != cur_feat && overlap(out_feat, feat_bytes, cur_feat, feat_bytes)) ||
-        (n_prev && overlap(out_feat, feat_bytes, prev_spheres, prev_bytes)))
+    if ((out_feat != cur_feat && overlaps(out_feat, feat_bytes, cur_feat, feat_bytes)) ||
+        (n_prev && overlaps(out_feat, feat_bytes, prev_spheres, prev_bytes)))
         return fail(c, RT_ERR_ARG, "rt_warp_features_spheres: the output overlaps an input other than exactly cur_feat");
     AuxCall x = {c, RT_ST_WARP_SPH};
     if (const int r = x.open(stream, flags)) return r;
     /* staged: the two feature planes, warped in place there, then the earlier spheres (20 words each) */
     constexpr size_t kSphereFloats = sizeof(rt_sphere) / sizeof(float);
     const float *prev = n_prev ? reinterpret_cast<const float *>(prev_spheres) : nullptr;
-    const Plane pl[] = {{cur_feat, out_feat, 0, 8 * px}, {prev, nullptr, 8 * px, kSphereFloats * n_prev}};
-    if (const int r = x.begin(pl, 2, 8 * px + kSphereFloats * n_prev)) return r;
+    const Plane pl[] = {{cur_feat, out_feat, 8 * px}, {prev, nullptr, kSphereFloats * n_prev}};
+    if (const int r = x.begin(pl, 2)) return r;
     const int e = rt_launch_warp_features_spheres(x.at(0, cur_feat), c->d_spheres, (uint32_t)c->spheres.size(),
                                                   prev ? reinterpret_cast<const rt_sphere *>(x.at(1, prev)) : nullptr, n_prev,
                                                   x.at(0, out_feat), W, H, x.st);
@@ -503,9 +539,7 @@ try {
 
 int rt_last_sphere_warp_ms(const rt_ctx *c, float *ms)
 try {
-    if (!c || !ms) return RT_ERR_ARG;
-    if (!c->stage_time[RT_ST_WARP_SPH].have) return RT_ERR_STATE;
-    return stage_ms(c, RT_ST_WARP_SPH, ms);
+    return last_ms(c, {{RT_ST_WARP_SPH, ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- variance-guided display filter --------------------- */
@@ -536,11 +570,11 @@ try {
     AuxCall x = {c, RT_ST_MOMENTS};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    /* staged: prev, cur, then the moments, accumulated in place there */
-    const Plane pl[] = {{cur_rgba, nullptr, 4 * px, 4 * px},
-                        {first ? nullptr : prev_rgba, nullptr, 0, 4 * px},
-                        {first ? nullptr : mom_in, mom_out, 8 * px, 4 * px}};
-    if (const int r = x.begin(pl, 3, 12 * px)) return r;
+    /* staged: cur, prev, then the moments, accumulated in place there */
+    const Plane pl[] = {{cur_rgba, nullptr, 4 * px},
+                        {first ? nullptr : prev_rgba, nullptr, 4 * px},
+                        {first ? nullptr : mom_in, mom_out, 4 * px}};
+    if (const int r = x.begin(pl, 3)) return r;
     const int e = rt_launch_moments(x.at(1, prev_rgba), x.at(0, cur_rgba), n_cur, x.at(2, mom_in), x.at(2, mom_out), W, H, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "moments kernel launch");
     return x.end();
@@ -562,16 +596,14 @@ try {
     if (!(prm->min_len >= 2.0f)) return fail(c, RT_ERR_ARG, "rt_variance: min_len below 2 or NaN");
     if (!(prm->sigma_normal > 0.0f) || !(prm->sigma_plane > 0.0f))
         return fail(c, RT_ERR_ARG, "rt_variance: a sigma is not positive"); /* <= 0 or NaN */
-    const float isn = 1.0f / (prm->sigma_normal * prm->sigma_normal), isp = 1.0f / (prm->sigma_plane * prm->sigma_plane);
     AuxCall x = {c, RT_ST_VARIANCE};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
-    /* staged: the float4 streams first (px may be odd), then the two planes */
-    const Plane pl[] = {{disp_rgba, nullptr, 0, 4 * px}, {mom_rgba, nullptr, 4 * px, 4 * px}, {feat, nullptr, 8 * px, 8 * px},
-                        {len, nullptr, 16 * px, px},     {nullptr, out_var, 17 * px, px}};
-    if (const int r = x.begin(pl, 5, 18 * px)) return r;
+    const Plane pl[] = {{disp_rgba, nullptr, 4 * px}, {mom_rgba, nullptr, 4 * px}, {feat, nullptr, 8 * px},
+                        {len, nullptr, px},           {nullptr, out_var, px}};
+    if (const int r = x.begin(pl, 5)) return r;
     const int e = rt_launch_variance(x.at(0, disp_rgba), x.at(1, mom_rgba), x.at(3, len), x.at(2, feat), x.at(4, out_var), W, H,
-                                     isn, isp, prm->min_len, x.st);
+                                     inv_sq(prm->sigma_normal), inv_sq(prm->sigma_plane), prm->min_len, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "variance kernel launch");
     return x.end();
 } RT_CATCH(err_of(c))
@@ -593,15 +625,15 @@ try {
     const float sig[3] = {prm->sigma_lum, prm->sigma_normal, prm->sigma_plane};
     for (float s : sig)
         if (!(s > 0.0f)) return fail(c, RT_ERR_ARG, "rt_denoise_var: a sigma is not positive"); /* <= 0 or NaN */
-    const float isn = 1.0f / (sig[1] * sig[1]), isp = 1.0f / (sig[2] * sig[2]);
     const int lum_on = sig[0] < rt_inff(); /* +INFINITY: the luminance term is off (inf * 0 would be a NaN) */
     AuxCall x = {c, RT_ST_DENOISE_VAR};
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
     /* staged: colour, the two feature planes, then the variance plane; filtered in place there
        (the last pass never reads its destination) */
-    const Plane pl[] = {{in, out, 0, 4 * px}, {feat, nullptr, 4 * px, 8 * px}, {in_var, out_var, 12 * px, px}};
-    return atrous_passes(x, pl, 13 * px, in, in_var, feat, out, out_var, W, H, prm->iterations, sig[0], lum_on, isn, isp);
+    const Plane pl[] = {{in, out, 4 * px}, {feat, nullptr, 8 * px}, {in_var, out_var, px}};
+    return atrous_passes(x, pl, in, in_var, feat, out, out_var, W, H, prm->iterations, sig[0], lum_on, inv_sq(sig[1]),
+                         inv_sq(sig[2]));
 } RT_CATCH(err_of(c))
 
 int rt_denoise_var(rt_ctx *c, const float *in, const float *in_var, const float *feat, float *out, float *out_var,
@@ -612,15 +644,7 @@ try {
 
 int rt_last_variance_ms(const rt_ctx *c, float *moments_ms, float *variance_ms, float *denoise_var_ms)
 try {
-    if (!c || (!moments_ms && !variance_ms && !denoise_var_ms)) return RT_ERR_ARG;
-    float *out[3] = {moments_ms, variance_ms, denoise_var_ms};
-    const RtStage stage[3] = {RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR};
-    for (int k = 0; k < 3; ++k)
-        if (out[k] && !c->stage_time[stage[k]].have) return RT_ERR_STATE;
-    for (int k = 0; k < 3; ++k)
-        if (out[k])
-            if (const int r = stage_ms(c, stage[k], out[k])) return r;
-    return RT_OK;
+    return last_ms(c, {{RT_ST_MOMENTS, moments_ms}, {RT_ST_VARIANCE, variance_ms}, {RT_ST_DENOISE_VAR, denoise_var_ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- tone-mapped 8-bit display output with auto-exposure ---- */
@@ -665,13 +689,11 @@ try {
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
     /* staged: the frame, the exposure, then the counts (words where the other planes hold floats) */
-    const Plane pl[] = {{rgba, nullptr, 0, 4 * px},
-                        {exposure_io, exposure_io, 4 * px, 1},
-                        {nullptr, reinterpret_cast<float *>(hist_out), 4 * px + 1, RT_METER_BINS}};
-    if (!x.host && !hist_out) HIPCHK(c, c->d_meter_hist.reserve(RT_METER_BINS)); /* (allocated once, never grown) */
-    if (const int r = x.begin(pl, 3, 4 * px + 1 + RT_METER_BINS)) return r;
-    uint32_t *hist = x.host || hist_out ? reinterpret_cast<uint32_t *>(x.at(2, reinterpret_cast<float *>(hist_out)))
-                                        : c->d_meter_hist.p;
+    const Plane pl[] = {{rgba, nullptr, 4 * px}, {exposure_io, exposure_io, 1}, {nullptr, reinterpret_cast<float *>(hist_out), RT_METER_BINS}};
+    uint32_t *hist;
+    if (const int r = dev_hist(x, hist_out, c->d_meter_hist, hist)) return r;
+    if (const int r = x.begin(pl, 3)) return r;
+    hist = x.words(2, hist);
     int e = rt_launch_lum_hist(x.at(0, rgba), W, H, hist, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "meter histogram kernel launch");
     e = rt_launch_exposure(hist, x.at(1, exposure_io), prm->key, prm->lo, prm->hi, prm->e_min, prm->e_max, prm->rate, x.st);
@@ -699,18 +721,18 @@ try {
     if (const int r = x.open(stream, flags)) return r;
     const size_t px = (size_t)W * H;
     /* staged: the frame, the 8-bit frame (words), then the exposure */
-    const Plane pl[] = {{rgba, nullptr, 0, 4 * px}, {nullptr, reinterpret_cast<float *>(out), 4 * px, px}, {exposure, nullptr, 5 * px, 1}};
-    if (const int r = x.begin(pl, 3, 5 * px + 1)) return r;
+    const Plane pl[] = {{rgba, nullptr, 4 * px}, {nullptr, reinterpret_cast<float *>(out), px}, {exposure, nullptr, 1}};
+    if (const int r = x.begin(pl, 3)) return r;
     const RtToneLaunch a = {x.at(0, rgba),
                             exposure ? x.at(2, exposure) : nullptr,
-                            reinterpret_cast<uint32_t *>(x.at(1, reinterpret_cast<float *>(out))),
+                            x.words(1, out),
                             W,
                             H,
                             prm->curve,
                             prm->srgb,
                             prm->dither,
                             prm->exposure,
-                            1.0f / (prm->white * prm->white)};
+                            inv_sq(prm->white)};
     const int e = rt_launch_tonemap(a, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "tone-map kernel launch");
     return x.end();
@@ -724,12 +746,7 @@ try {
 
 int rt_last_tonemap_ms(const rt_ctx *c, float *meter_ms, float *tonemap_ms)
 try {
-    if (!c || (!meter_ms && !tonemap_ms)) return RT_ERR_ARG;
-    if ((meter_ms && !c->stage_time[RT_ST_METER].have) || (tonemap_ms && !c->stage_time[RT_ST_TONEMAP].have))
-        return RT_ERR_STATE;
-    if (meter_ms)
-        if (const int r = stage_ms(c, RT_ST_METER, meter_ms)) return r;
-    return tonemap_ms ? stage_ms(c, RT_ST_TONEMAP, tonemap_ms) : RT_OK;
+    return last_ms(c, {{RT_ST_METER, meter_ms}, {RT_ST_TONEMAP, tonemap_ms}});
 } RT_CATCH(err_of(c))
 
 /* ---- the noise meter ------------------------------------- */
@@ -755,7 +772,7 @@ try {
     if (!(prm->lum_floor > 0.0f && prm->lum_floor < rt_inff()))
         return fail(c, RT_ERR_ARG, "rt_noise_meter: lum_floor is not positive and finite");
     const size_t px = (size_t)W * H, tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
-    /* every output apart from both inputs and from the other outputs (addresses of one kind: all host or all device) */
+    /* every output apart from both inputs and from the other outputs (a null one is not there) */
     const struct {
         const void *p;
         size_t bytes;
@@ -763,29 +780,27 @@ try {
                {stats_out, sizeof(rt_noise_stats)},     {tiles_out, 2 * tiles * sizeof(float)},
                {hist_out, RT_METER_BINS * sizeof(uint32_t)}};
     for (int o = 2; o < 5; ++o)
-        for (int i = 0; i < o; ++i) {
-            const uintptr_t a = (uintptr_t)buf[o].p, b = (uintptr_t)buf[i].p;
-            if (a && b && a < b + buf[i].bytes && b < a + buf[o].bytes)
+        for (int i = 0; i < o; ++i)
+            if (overlaps(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
                 return fail(c, RT_ERR_ARG, "rt_noise_meter: an output overlaps an input or another output");
-        }
     AuxCall x = {c, RT_ST_NOISE};
     if (const int r = x.open(stream, flags)) return r;
     /* staged: the frame, the variance plane, then the words of the stats, the counts and the tile pairs */
     constexpr size_t kStatWords = sizeof(rt_noise_stats) / sizeof(float);
-    const Plane pl[] = {{rgba, nullptr, 0, 4 * px},
-                        {var, nullptr, 4 * px, px},
-                        {nullptr, reinterpret_cast<float *>(stats_out), 5 * px, kStatWords},
-                        {nullptr, reinterpret_cast<float *>(hist_out), 5 * px + kStatWords, RT_METER_BINS},
-                        {nullptr, tiles_out, 5 * px + kStatWords + RT_METER_BINS, 2 * tiles}};
-    if (!x.host && !hist_out) HIPCHK(c, c->d_noise_hist.reserve(RT_METER_BINS)); /* (allocated once, never grown) */
-    if (const int r = x.begin(pl, 5, 5 * px + kStatWords + RT_METER_BINS + 2 * tiles)) return r;
-    uint32_t *hist = x.host || hist_out ? reinterpret_cast<uint32_t *>(x.at(3, reinterpret_cast<float *>(hist_out)))
-                                        : c->d_noise_hist.p;
+    const Plane pl[] = {{rgba, nullptr, 4 * px},
+                        {var, nullptr, px},
+                        {nullptr, reinterpret_cast<float *>(stats_out), kStatWords},
+                        {nullptr, reinterpret_cast<float *>(hist_out), RT_METER_BINS},
+                        {nullptr, tiles_out, 2 * tiles}};
+    uint32_t *hist;
+    if (const int r = dev_hist(x, hist_out, c->d_noise_hist, hist)) return r;
+    if (const int r = x.begin(pl, 5)) return r;
+    hist = x.words(3, hist);
     float *dtiles = tiles_out ? x.at(4, tiles_out) : nullptr;
     int e = rt_launch_noise_hist(x.at(0, rgba), x.at(1, var), W, H, prm->lum_floor, hist, dtiles, x.st);
     if (e) return hip_fail(c, (hipError_t)e, "noise histogram kernel launch");
     e = rt_launch_noise_stat(hist, W, H, prm->percentile, prm->threshold,
-                             reinterpret_cast<rt_noise_stats *>(x.at(2, reinterpret_cast<float *>(stats_out))), x.st);
+                             reinterpret_cast<rt_noise_stats *>(x.words(2, stats_out)), x.st);
     if (e) return hip_fail(c, (hipError_t)e, "noise statistic kernel launch");
     return x.end();
 } RT_CATCH(err_of(c))
@@ -798,9 +813,7 @@ try {
 
 int rt_last_noise_ms(const rt_ctx *c, float *ms)
 try {
-    if (!c || !ms) return RT_ERR_ARG;
-    if (!c->stage_time[RT_ST_NOISE].have) return RT_ERR_STATE;
-    return stage_ms(c, RT_ST_NOISE, ms);
+    return last_ms(c, {{RT_ST_NOISE, ms}});
 } RT_CATCH(err_of(c))
 
 } /* extern "C" */

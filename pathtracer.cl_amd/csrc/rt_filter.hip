@@ -23,15 +23,11 @@
 
 #include <cstdlib>
 
-#include "pathtracer_rt.h"
-#include "rt_internal.h"
-#include "rt_math.h"
+#include "rt_display_util.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ float lum3(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
 
 /* the sample a progressive frame mixed in: mix(old, s, 1/n) inverted, negative results (rounding) to 0 */
 __device__ __forceinline__ float unmix(float prev, float cur, float n)
@@ -41,10 +37,10 @@ __device__ __forceinline__ float unmix(float prev, float cur, float n)
 }
 
 /* One lane per pixel; mom_out may be mom_in (each lane reads its pixel before it writes it). */
-__global__ __launch_bounds__(256) void k_moments(const float4 *prev, const float4 *cur, float n, float f,
+__global__ __launch_bounds__(kPixelBlock) void k_moments(const float4 *prev, const float4 *cur, float n, float f,
                                                  const float4 *mom_in, float4 *mom_out, uint32_t npx)
 {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
     if (p >= npx) return;
     const float4 c = cur[p];
     if (n == 1.0f) { /* the first frame of a view is its own sample; no history is read */
@@ -55,17 +51,6 @@ __global__ __launch_bounds__(256) void k_moments(const float4 *prev, const float
     const float4 o = prev[p], m = mom_in[p];
     const float L = lum3(unmix(o.x, c.x, n), unmix(o.y, c.y, n), unmix(o.z, c.z, n));
     mom_out[p] = make_float4(m.x + (L - m.x) * f, m.y + (L * L - m.y) * f, 0.0f, 0.0f);
-}
-
-/* the feature terms of a tap: en isn, and ep isp through ep_isp */
-__device__ __forceinline__ float feat_arg(float4 pq, float4 nq, float4 pp, float4 np, float isn, float isp, float &ep_isp)
-{
-    const float dnx = nq.x - np.x, dny = nq.y - np.y, dnz = nq.z - np.z;
-    const float en = dnx * dnx + dny * dny + dnz * dnz;
-    const float pl = (pq.x - pp.x) * np.x + (pq.y - pp.y) * np.y + (pq.z - pp.z) * np.z;
-    const float ep = pl * pl;
-    ep_isp = ep * isp;
-    return en * isn;
 }
 
 /* The 49 taps of the spatial estimate are gathered from global memory (only pixels with a short
@@ -141,9 +126,9 @@ struct LumOverSigma {
     __device__ __forceinline__ void centre(float4 c, float g)
     {
         il = lum_on ? 1.0f / (sigma_lum * rt_sqrtf(g) + 1e-8f) : 0.0f;
-        lp = lum3(c.x, c.y, c.z);
+        lp = lum3(c);
     }
-    __device__ __forceinline__ float arg(float4 cq) const { return fabsf(lum3(cq.x, cq.y, cq.z) - lp) * il; }
+    __device__ __forceinline__ float arg(float4 cq) const { return fabsf(lum3(cq) - lp) * il; }
 };
 
 __device__ __forceinline__ float atrous_h(int dx, int dy)
@@ -298,7 +283,7 @@ int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur
                       uint32_t W, uint32_t H, void *stream)
 {
     const uint32_t npx = W * H; /* < 2^28 (the host's frame check) */
-    hipLaunchKernelGGL(k_moments, dim3((npx + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_moments, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(prev_rgba), reinterpret_cast<const float4 *>(cur_rgba), n_cur,
                        1.0f / n_cur, reinterpret_cast<const float4 *>(mom_in), reinterpret_cast<float4 *>(mom_out), npx);
     return (int)hipGetLastError();
@@ -307,8 +292,7 @@ int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur
 int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
                        uint32_t W, uint32_t H, float isn, float isp, float min_len, void *stream)
 {
-    const dim3 grid((W + RT_TILE_BX - 1) / RT_TILE_BX, (H + RT_TILE_BY - 1) / RT_TILE_BY);
-    hipLaunchKernelGGL(k_variance, grid, dim3(RT_TILE_BX, RT_TILE_BY), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_variance, tile_grid(W, H), tile_block(), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(disp_rgba), reinterpret_cast<const float4 *>(mom_rgba), len,
                        reinterpret_cast<const float4 *>(feat), out_var, W, H, isn, isp, min_len);
     return (int)hipGetLastError();
@@ -316,12 +300,10 @@ int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const floa
 
 int rt_launch_atrous(const RtAtrousLaunch &a, void *stream)
 {
-    const dim3 grid((a.W + RT_TILE_BX - 1) / RT_TILE_BX, (a.H + RT_TILE_BY - 1) / RT_TILE_BY);
-    const dim3 block(RT_TILE_BX, RT_TILE_BY);
     const float4 *c4 = reinterpret_cast<const float4 *>(a.col), *f4 = reinterpret_cast<const float4 *>(a.feat);
     float4 *o4 = reinterpret_cast<float4 *>(a.out);
     const auto go = [&](auto kernel, auto... args) {
-        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, args...);
+        hipLaunchKernelGGL(kernel, tile_grid(a.W, a.H), tile_block(), 0, (hipStream_t)stream, args...);
     };
     /* steps 1 and 2 from LDS, the larger ones gathered (the step size decides: profiles/denoise);
        RTMI_ATROUS_LDS (A/B knob, read at every launch, no result bit depends on it): the largest

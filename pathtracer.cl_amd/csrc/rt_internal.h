@@ -432,8 +432,8 @@ struct RtFeatLaunch {
 };
 int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
 /* The pixel tile of a block of the display-side kernels that run one lane per pixel of a 2-D grid
-   (the a-trous passes, k_variance, k_reproject): a wave covers two rows of 32 (512-B row segments
-   per float4 stream). */
+   (the a-trous passes, k_variance, k_reproject, k_history_trust; launched with rt_display_util.h's
+   tile_grid / tile_block): a wave covers two rows of 32 (512-B row segments per float4 stream). */
 #define RT_TILE_BX 32
 #define RT_TILE_BY 8
 /* -- rt_temporal.hip -- */

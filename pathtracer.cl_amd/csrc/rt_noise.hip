@@ -19,40 +19,28 @@
  */
 #include <hip/hip_runtime.h>
 
-#include "pathtracer_rt.h"
-#include "rt_internal.h"
-#include "rt_math.h"
+#include "rt_display_util.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kBins = RT_METER_BINS;
-constexpr int kBlock = 256, kWaves = kBlock / 64; /* four horizontally adjacent tiles a block */
-constexpr uint32_t kMaxBlocks = 1024;             /* the persistent grid: 4 blocks for each of 256 CUs */
-constexpr int kBinsPerLane = kBins / 64;
+constexpr int kBinsPerLane = kMeterBins / 64;
 
-__device__ __forceinline__ float lum3(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-
-/* A persistent grid-stride grid over groups of four tiles (a 32 x 8 pixel strip: each of its pixel
-   rows is one 512-byte segment of the colour stream).  Every wave counts into an LDS histogram of its
-   own with k_lum_hist's leader aggregation (rt_tonemap.hip): the lanes that share the bin of the
-   wave's first counted lane are added by that lane alone, as one LDS atomic of their number — a
-   converged frame is nearly one bin — the others add themselves.  The block's sum of its copies goes
-   to global memory with one integer atomic per occupied bin.  tiles may be null. */
-__global__ __launch_bounds__(kBlock) void k_noise_hist(const float4 *__restrict__ rgba, const float *__restrict__ var,
+/* The block histogram (rt_display_util.h: a converged frame is nearly one bin) over groups of
+   kHistWaves horizontally adjacent tiles, a tile a wave (a 32 x 8 pixel strip: each of its pixel
+   rows is one 512-byte segment of the colour stream).  tiles may be null. */
+__global__ __launch_bounds__(kHistBlock) void k_noise_hist(const float4 *__restrict__ rgba, const float *__restrict__ var,
                                                         uint32_t W, uint32_t H, uint32_t tw, uint32_t gw, uint32_t groups,
                                                         float lum_floor, uint32_t *__restrict__ hist,
                                                         float *__restrict__ tiles)
 {
-    __shared__ uint32_t s_h[kWaves * kBins];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t i = tid; i < kWaves * kBins; i += kBlock) s_h[i] = 0u;
-    __syncthreads();
-    uint32_t *mine = s_h + wave * kBins;
+    __shared__ uint32_t s_h[kHistWaves * kMeterBins];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t *mine = hist_zero(s_h);
     /* (the trip count is the block's: every lane stays in the loop for the ballots and the butterflies) */
     for (uint32_t g = blockIdx.x; g < groups; g += gridDim.x) {
-        const uint32_t ty = g / gw, tx = (g - ty * gw) * kWaves + wave;
+        const uint32_t ty = g / gw, tx = (g - ty * gw) * kHistWaves + wave;
         const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
         bool valid = false;
         int bin = 0;
@@ -61,24 +49,16 @@ __global__ __launch_bounds__(kBlock) void k_noise_hist(const float4 *__restrict_
             const uint32_t p = y * W + x;
             const float4 c = rgba[p];
             const float v = var[p];
-            const float L = lum3(c.x, c.y, c.z);
+            const float L = lum3(c);
             /* v >= 0 (NaN is not) and finite, L finite; without a branch, so that both loads are in
                flight together (a skipped pixel's quotient is dropped) */
             valid = v >= 0.0f && rt_f2u(v) != RT_INF_BITS && (rt_f2u(L) & 0x7fffffffu) < RT_INF_BITS;
             const float Lp = L > 0.0f ? L : 0.0f;
             const float q = rt_sqrtf(v) / (Lp + lum_floor);
             e = valid ? q : 0.0f;
-            const int b = (int)((rt_f2u(e) & 0x7fffffffu) >> 19) - 1776;
-            bin = b < 0 ? 0 : (b > kBins - 1 ? kBins - 1 : b);
+            bin = meter_bin(rt_f2u(e) & 0x7fffffffu);
         }
-        const unsigned long long any = __ballot(valid);
-        if (any) {
-            const int leader = __ffsll((long long)any) - 1;
-            const int b0 = __shfl(bin, leader);
-            const unsigned long long same = __ballot(valid && bin == b0);
-            if ((int)lane == leader) atomicAdd(&mine[b0], (uint32_t)__popcll(same));
-            else if (valid && bin != b0) atomicAdd(&mine[bin], 1u);
-        }
+        const unsigned long long any = hist_add(mine, valid, bin);
         if (tiles) { /* (uniform) */
             float s = e, m = e;
 #pragma unroll
@@ -94,12 +74,7 @@ __global__ __launch_bounds__(kBlock) void k_noise_hist(const float4 *__restrict_
             }
         }
     }
-    __syncthreads();
-    for (uint32_t i = tid; i < (uint32_t)kBins; i += kBlock) {
-        uint32_t n = 0u;
-        for (int w = 0; w < kWaves; ++w) n += s_h[w * kBins + i];
-        if (n) atomicAdd(&hist[i], n);
-    }
+    hist_flush(s_h, hist);
 }
 
 /* the sum of v over the wave, in every lane */
@@ -125,7 +100,7 @@ __global__ __launch_bounds__(64) void k_noise_stat(const uint32_t *__restrict__ 
         const int i = (int)lane * kBinsPerLane + k;
         own += n[k];
         /* the bin's upper edge (bin 383's is +INFINITY, which is under no threshold) */
-        const bool at_or_under = i < kBins - 1 && rt_u2f((uint32_t)(i + 1777) << 19) <= threshold;
+        const bool at_or_under = i < kMeterBins - 1 && meter_bin_top(i) <= threshold;
         under += at_or_under ? n[k] : 0u;
     }
     /* the count before this lane's bins: an inclusive scan of `own` less itself */
@@ -158,7 +133,7 @@ __global__ __launch_bounds__(64) void k_noise_stat(const uint32_t *__restrict__ 
             if (c > r) break;
             ++i;
         }
-        out->level = i < kBins - 1 ? rt_u2f((uint32_t)(i + 1777) << 19) : rt_inff();
+        out->level = i < kMeterBins - 1 ? meter_bin_top(i) : rt_inff();
         out->counted = (uint32_t)N;
         out->skipped = npx - (uint32_t)N;
         out->below = (uint32_t)under;
@@ -170,11 +145,11 @@ __global__ __launch_bounds__(64) void k_noise_stat(const uint32_t *__restrict__ 
 int rt_launch_noise_hist(const float *rgba, const float *var, uint32_t W, uint32_t H, float lum_floor, uint32_t *hist,
                          float *tiles, void *stream)
 {
-    const hipError_t e = hipMemsetAsync(hist, 0, kBins * sizeof(uint32_t), (hipStream_t)stream);
+    const hipError_t e = hipMemsetAsync(hist, 0, kMeterBins * sizeof(uint32_t), (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    const uint32_t tw = (W + 7u) / 8u, th = (H + 7u) / 8u, gw = (tw + kWaves - 1) / kWaves;
+    const uint32_t tw = (W + 7u) / 8u, th = (H + 7u) / 8u, gw = (tw + kHistWaves - 1) / kHistWaves;
     const uint32_t groups = gw * th; /* < 2^28 / 8 + 2^28 / 64 (the host's frame check) */
-    hipLaunchKernelGGL(k_noise_hist, dim3(groups < kMaxBlocks ? groups : kMaxBlocks), dim3(kBlock), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_noise_hist, hist_grid(groups), dim3(kHistBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(rgba), var, W, H, tw, gw, groups, lum_floor, hist, tiles);
     return (int)hipGetLastError();
 }

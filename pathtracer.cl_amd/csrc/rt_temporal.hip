@@ -18,9 +18,7 @@
  */
 #include <hip/hip_runtime.h>
 
-#include "pathtracer_rt.h"
-#include "rt_internal.h"
-#include "rt_math.h"
+#include "rt_display_util.h"
 
 #pragma clang fp contract(off)
 
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_reproject(ReprojArgs
                         const float4 nq = a.prev_feat[npx + q];
                         const int idq = __float_as_int(nq.w);
                         if (idq == RT_FEAT_NONE) continue;
-                        if (!((idp >= 0 && idq >= 0) || idp == idq)) continue; /* the surface class */
+                        if (!same_surface_class(idp, idq)) continue;
                         const float4 pq = a.prev_feat[q];
                         const float pl = ((pq.x - pp.x) * np.x + (pq.y - pp.y) * np.y) + (pq.z - pp.z) * np.z;
                         if (!(fabsf(pl) <= tol)) continue;
@@ -117,11 +115,11 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_reproject(ReprojArgs
 
 /* out = h + (c - h) (n / (n + m)) where the history is m > 0 frames long, c's bits elsewhere; h, m
    and the outputs may be the same buffers (each lane reads its pixel before it writes it). */
-__global__ __launch_bounds__(256) void k_temporal_merge(const float4 *hist, const float *hist_len, const float4 *cur,
+__global__ __launch_bounds__(kPixelBlock) void k_temporal_merge(const float4 *hist, const float *hist_len, const float4 *cur,
                                                         float n, float max_history, float4 *out, float *out_len,
                                                         uint32_t npx)
 {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
     if (p >= npx) return;
     const float4 c = cur[p];
     const float m = hist_len[p];
@@ -152,8 +150,6 @@ struct TrustArgs {
 constexpr int TRUST_R = 3; /* the 7 x 7 window */
 constexpr int TRUST_TW = RT_TILE_BX + 2 * TRUST_R, TRUST_TH = RT_TILE_BY + 2 * TRUST_R, TRUST_CELLS = TRUST_TW * TRUST_TH;
 
-__device__ __forceinline__ float trust_lum(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-
 /* One lane per pixel of the block's RT_TILE_BX x RT_TILE_BY tile.  The tile and
    its halo of 3 pixels — 38 x 14 cells — are staged in LDS once: per cell the luminance of the
    accumulation buffer and of the history (computed here, so the 49 taps of a pixel read two dwords
@@ -182,8 +178,8 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustA
                 nq = a.feat[npx + q];
                 if (__float_as_int(nq.w) != RT_FEAT_NONE) {
                     s_p[i] = a.feat[q];
-                    s_lc[i] = trust_lum(a.cur[q]);
-                    s_lh[i] = trust_lum(a.hist[q]);
+                    s_lc[i] = lum3(a.cur[q]);
+                    s_lh[i] = lum3(a.hist[q]);
                 }
             }
         }
@@ -215,15 +211,13 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustA
             const float4 nq = s_n[q];
             const int idq = __float_as_int(nq.w);
             if (idq == RT_FEAT_NONE) continue;
-            if (!((idp >= 0 && idq >= 0) || idp == idq)) continue; /* the surface class, as k_reproject */
+            if (!same_surface_class(idp, idq)) continue;
             /* all of a tap's loads before its weight (rt_expf branches) */
             const float4 pq = s_p[q];
             const float Lc = s_lc[q], Lh = s_lh[q];
-            const float dnx = nq.x - np.x, dny = nq.y - np.y, dnz = nq.z - np.z;
-            const float en = dnx * dnx + dny * dny + dnz * dnz;
-            const float pl = (pq.x - pp.x) * np.x + (pq.y - pp.y) * np.y + (pq.z - pp.z) * np.z;
-            const float ep = pl * pl;
-            const float w = rt_expf(-(en * a.isn + ep * a.isp));
+            float ep_isp;
+            const float en_isn = feat_arg(pq, nq, pp, np, a.isn, a.isp, ep_isp);
+            const float w = rt_expf(-(en_isn + ep_isp));
             ws += w;
             w2 += w * w;
             ac += Lc * w;
@@ -281,9 +275,7 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
     a.plane_tol = plane_tol;
     a.normal_min = normal_min;
     a.max_history = max_history;
-    const dim3 grid((W + RT_TILE_BX - 1) / RT_TILE_BX, (H + RT_TILE_BY - 1) / RT_TILE_BY);
-    const dim3 block(RT_TILE_BX, RT_TILE_BY);
-    hipLaunchKernelGGL(k_reproject, grid, block, 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_reproject, tile_grid(W, H), tile_block(), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -291,7 +283,7 @@ int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, cons
                              float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream)
 {
     const uint32_t npx = W * H; /* < 2^28 (the host's frame check) */
-    hipLaunchKernelGGL(k_temporal_merge, dim3((npx + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_temporal_merge, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(hist_rgba), hist_len, reinterpret_cast<const float4 *>(cur_rgba),
                        n_cur, max_history, reinterpret_cast<float4 *>(out_rgba), out_len, npx);
     return (int)hipGetLastError();
@@ -313,7 +305,6 @@ int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const
     a.k2 = k2;
     a.isn = isn;
     a.isp = isp;
-    const dim3 grid((W + RT_TILE_BX - 1) / RT_TILE_BX, (H + RT_TILE_BY - 1) / RT_TILE_BY);
-    hipLaunchKernelGGL(k_history_trust, grid, dim3(RT_TILE_BX, RT_TILE_BY), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_history_trust, tile_grid(W, H), tile_block(), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

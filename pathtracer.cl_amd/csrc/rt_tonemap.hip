@@ -18,60 +18,32 @@
  */
 #include <hip/hip_runtime.h>
 
-#include "pathtracer_rt.h"
-#include "rt_internal.h"
-#include "rt_math.h"
+#include "rt_display_util.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kBins = RT_METER_BINS;
-constexpr int kHistBlock = 256, kHistWaves = kHistBlock / 64;
-constexpr uint32_t kHistMaxBlocks = 1024; /* the persistent grid: 4 blocks for each of 256 CUs */
-
-__device__ __forceinline__ float lum3(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-
-/* A persistent grid-stride grid.  Every wave counts into an LDS histogram of its own (4 x 384 words:
-   6 KB a block); neighbouring pixels fall into the same bin, so the lanes that share the bin of the
-   wave's first counted lane are added by that lane alone, as one LDS atomic of their number (a flat
-   region of the frame: one atomic a wave instead of 64 on one address), the others add themselves.
-   The block's sum of its copies goes to global memory with one integer atomic per occupied bin. */
+/* The block histogram (rt_display_util.h) over the frame's pixels, kHistBlock a trip. */
 __global__ __launch_bounds__(kHistBlock) void k_lum_hist(const float4 *__restrict__ rgba, uint32_t npx,
                                                          uint32_t *__restrict__ hist)
 {
-    __shared__ uint32_t s_h[kHistWaves * kBins];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    for (uint32_t i = tid; i < kHistWaves * kBins; i += kHistBlock) s_h[i] = 0u;
-    __syncthreads();
-    uint32_t *mine = s_h + (tid >> 6) * kBins;
+    __shared__ uint32_t s_h[kHistWaves * kMeterBins];
+    uint32_t *mine = hist_zero(s_h);
     /* (the trip count is the wave's: every lane stays in the loop for the ballots) */
     for (uint32_t base = blockIdx.x * kHistBlock; base < npx; base += gridDim.x * kHistBlock) {
-        const uint32_t p = base + tid;
+        const uint32_t p = base + threadIdx.x;
         bool counted = false;
         int bin = 0;
         if (p < npx) {
             const float4 c = rgba[p];
-            const uint32_t u = rt_f2u(lum3(c.x, c.y, c.z));
+            const uint32_t u = rt_f2u(lum3(c));
             counted = u > 0u && u < RT_INF_BITS; /* positive and finite */
-            const int b = (int)(u >> 19) - 1776;
-            bin = b < 0 ? 0 : (b > kBins - 1 ? kBins - 1 : b);
+            bin = meter_bin(u);
         }
-        const unsigned long long any = __ballot(counted);
-        if (any) {
-            const int leader = __ffsll((long long)any) - 1;
-            const int b0 = __shfl(bin, leader);
-            const unsigned long long same = __ballot(counted && bin == b0);
-            if ((int)lane == leader) atomicAdd(&mine[b0], (uint32_t)__popcll(same));
-            else if (counted && bin != b0) atomicAdd(&mine[bin], 1u);
-        }
+        hist_add(mine, counted, bin);
     }
-    __syncthreads();
-    for (uint32_t i = tid; i < (uint32_t)kBins; i += kHistBlock) {
-        uint32_t n = 0u;
-        for (int w = 0; w < kHistWaves; ++w) n += s_h[w * kBins + i];
-        if (n) atomicAdd(&hist[i], n);
-    }
+    hist_flush(s_h, hist);
 }
 
 /* One lane, sequential. */
@@ -81,7 +53,7 @@ __global__ void k_exposure(const uint32_t *__restrict__ hist, float *exposure_io
     if (blockIdx.x || threadIdx.x) return;
     const float prev = *exposure_io;
     uint64_t N = 0;
-    for (int i = 0; i < kBins; ++i) N += hist[i];
+    for (int i = 0; i < kMeterBins; ++i) N += hist[i];
     if (N == 0) {
         *exposure_io = prev > 0.0f ? prev : 1.0f;
         return;
@@ -92,7 +64,7 @@ __global__ void k_exposure(const uint32_t *__restrict__ hist, float *exposure_io
     if (hi_n < lo_n + 1) hi_n = lo_n + 1;
     if (hi_n > N) hi_n = N;
     uint64_t c = 0, S = 0;
-    for (int i = 0; i < kBins; ++i) {
+    for (int i = 0; i < kMeterBins; ++i) {
         const uint64_t n = hist[i];
         const uint64_t a = c > lo_n ? c : lo_n, b = c + n < hi_n ? c + n : hi_n;
         if (b > a) S += (b - a) * (uint64_t)(2 * i + 1);
@@ -124,11 +96,11 @@ __device__ __forceinline__ uint32_t encode8(float v, bool srgb, float d)
 }
 
 /* One lane per pixel, one dword store per pixel. */
-__global__ __launch_bounds__(256) void k_tonemap(const float4 *__restrict__ rgba, const float *__restrict__ exposure,
+__global__ __launch_bounds__(kPixelBlock) void k_tonemap(const float4 *__restrict__ rgba, const float *__restrict__ exposure,
                                                  uint32_t *__restrict__ out, uint32_t W, uint32_t npx, uint32_t curve,
                                                  uint32_t srgb, uint32_t dither, float exposure_fixed, float iw)
 {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
     if (p >= npx) return;
     const float E = exposure ? *exposure : exposure_fixed;
     const float4 c = rgba[p];
@@ -156,11 +128,10 @@ __global__ __launch_bounds__(256) void k_tonemap(const float4 *__restrict__ rgba
 int rt_launch_lum_hist(const float *rgba, uint32_t W, uint32_t H, uint32_t *hist, void *stream)
 {
     const uint32_t npx = W * H; /* < 2^28 (the host's frame check) */
-    const hipError_t e = hipMemsetAsync(hist, 0, kBins * sizeof(uint32_t), (hipStream_t)stream);
+    const hipError_t e = hipMemsetAsync(hist, 0, kMeterBins * sizeof(uint32_t), (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    const uint32_t blocks = (npx + kHistBlock - 1) / kHistBlock;
-    hipLaunchKernelGGL(k_lum_hist, dim3(blocks < kHistMaxBlocks ? blocks : kHistMaxBlocks), dim3(kHistBlock), 0,
-                       (hipStream_t)stream, reinterpret_cast<const float4 *>(rgba), npx, hist);
+    hipLaunchKernelGGL(k_lum_hist, hist_grid((npx + kHistBlock - 1) / kHistBlock), dim3(kHistBlock), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4 *>(rgba), npx, hist);
     return (int)hipGetLastError();
 }
 
@@ -175,7 +146,7 @@ int rt_launch_exposure(const uint32_t *hist, float *exposure_io, float key, floa
 int rt_launch_tonemap(const RtToneLaunch &a, void *stream)
 {
     const uint32_t npx = a.W * a.H; /* < 2^28 */
-    hipLaunchKernelGGL(k_tonemap, dim3((npx + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_tonemap, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(a.rgba), a.exposure, a.out, a.W, npx, a.curve, a.srgb, a.dither,
                        a.exposure_fixed, a.iw);
     return (int)hipGetLastError();

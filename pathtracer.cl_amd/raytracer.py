@@ -223,54 +223,64 @@ class RayTracer:
         halo=True: the caller keeps this tile's seed rows current (dist.SeedHalo), which
         permits progressive sphere frames on a tile."""
         self._sync_scene()
-        flags = _abi.RT_SEEDS_HALO if halo else 0
-        if not isinstance(out, np.ndarray):
-            if getattr(out, "is_cuda", False):
-                flags |= _abi.RT_OUT_DEVICE
-            if out.dtype.__str__() not in ("torch.float32",):
-                raise TypeError("framebuffer must be float32")
-            if not out.is_contiguous():
-                raise ValueError("framebuffer must be contiguous")
-        else:
-            if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"]:
-                raise ValueError("framebuffer must be a contiguous float32 array")
         t, _keep = _abi.tile_struct(tile)  # (_keep: the owner map the struct points into)
-        rows = self._lib.rt_tile_rows(height, ctypes.byref(t) if t else None)
-        need = int(width) * int(rows) * 4
-        n = out.size if isinstance(out, np.ndarray) else out.numel()
-        if n < need:
-            raise ValueError(f"framebuffer holds {n} floats, {need} needed")
         tp = ctypes.byref(t) if t else None
-        if sync and stream is None:
-            st = self._lib.rt_render(self._h, _abi.ptr(out), int(width), int(height), int(progression), int(kernel),
-                                     tp, flags)
-            self._check(st, "rt_render")
-        else:
-            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
-            st = self._lib.rt_render_async(self._h, _abi.ptr(out), int(width), int(height), int(progression),
-                                           int(kernel), tp, flags, sp)
-            self._check(st, "rt_render_async")
-            if sync:
-                self.synchronize()
+        rows = self._lib.rt_tile_rows(height, tp)
+        flags = self._buffer(out, int(width) * int(rows) * 4, "framebuffer") | (_abi.RT_SEEDS_HALO if halo else 0)
+        args = (self._h, _abi.ptr(out), int(width), int(height), int(progression), int(kernel), tp, flags)
+        self._aux_call("rt_render", args, stream, sync)
 
     # ---- first-hit features and the display denoiser (pathtracer_rt.h) --------------------
+    _WORDS = ("uint32", "int32")
+
     @staticmethod
-    def _frame_buffer(buf, need: int, what: str) -> int:
-        """The checks of rayTrace's framebuffer (float32, contiguous, `need` floats); returns the
-        RT_OUT_DEVICE flag of a torch CUDA tensor, 0 for host memory."""
+    def _buffer(buf, need: int, what: str, dtypes: tuple = ("float32",)) -> int:
+        """The checks of a buffer that crosses the ABI (one of `dtypes`, contiguous, `need` elements);
+        returns the RT_OUT_DEVICE flag of a torch CUDA tensor, 0 for host memory."""
         if isinstance(buf, np.ndarray):
-            if buf.dtype != np.float32 or not buf.flags["C_CONTIGUOUS"]:
-                raise ValueError(f"{what} must be a contiguous float32 array")
+            if buf.dtype not in [np.dtype(d) for d in dtypes] or not buf.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{what} must be a contiguous {dtypes[0]} array")
             n, dev = buf.size, 0
         else:
-            if buf.dtype.__str__() not in ("torch.float32",):
-                raise TypeError(f"{what} must be float32")
+            if str(buf.dtype) not in ["torch." + d for d in dtypes]:
+                raise TypeError(f"{what} must be {' or '.join(dtypes)}")
             if not buf.is_contiguous():
                 raise ValueError(f"{what} must be contiguous")
             n, dev = buf.numel(), _abi.RT_OUT_DEVICE if getattr(buf, "is_cuda", False) else 0
         if n < need:
-            raise ValueError(f"{what} holds {n} floats, {need} needed")
+            raise ValueError(f"{what} holds {n} {'floats' if dtypes == ('float32',) else 'words'}, {need} needed")
         return dev
+
+    def _same_kind(self, method: str, bufs: list, who: str = "the buffers", also: tuple = ()) -> int:
+        """_buffer for every (buf, need, what[, dtypes]) of `bufs` whose buf is not None; all of them (and
+        the flags `also`) host arrays, or all device tensors: returns their common flag."""
+        flags = {self._buffer(*b) for b in bufs if b[0] is not None} | set(also)
+        if len(flags) != 1:
+            raise ValueError(f"{method}: {who} must all be host arrays or all device tensors")
+        return flags.pop()
+
+    def _aux_call(self, name: str, args: tuple, stream, sync: bool) -> None:
+        """`name` on the context's stream and waited for, or `name`_async on `stream` (sync: then waited for)."""
+        if sync and stream is None:
+            self._check(getattr(self._lib, name)(*args), name)
+        else:
+            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
+            self._check(getattr(self._lib, name + "_async")(*args, sp), name + "_async")
+            if sync:
+                self.synchronize()
+
+    def _last_ms(self, name: str, n_slots: int = 1, slot: int = 0) -> float:
+        """`name`(handle, n_slots float pointers): the one at `slot`, the others null."""
+        ms = ctypes.c_float()
+        a = [None] * n_slots
+        a[slot] = ctypes.byref(ms)
+        self._check(getattr(self._lib, name)(self._h, *a), name)
+        return ms.value
+
+    def _defaults(self, prm_type, name: str) -> dict:
+        prm = prm_type()
+        self._check(getattr(self._lib, name)(ctypes.byref(prm)), name)
+        return {f: getattr(prm, f) for f, _ in prm_type._fields_}
 
     def getCamera(self, width: int) -> np.ndarray:
         """The Camera (16 floats) a render of this width would use."""
@@ -291,17 +301,8 @@ class RayTracer:
         """First-hit features of every pixel-centre ray into `feat` (2 planes of W*H float4: (P, t),
         then (N, surface id as int32 bits); numpy or torch CUDA tensor)."""
         self._sync_scene()
-        flags = self._frame_buffer(feat, 2 * int(width) * int(height) * 4, "feature buffer")
-        if sync and stream is None:
-            st = self._lib.rt_render_features(self._h, _abi.ptr(feat), int(width), int(height), int(kernel), flags)
-            self._check(st, "rt_render_features")
-        else:
-            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
-            st = self._lib.rt_render_features_async(self._h, _abi.ptr(feat), int(width), int(height), int(kernel),
-                                                    flags, sp)
-            self._check(st, "rt_render_features_async")
-            if sync:
-                self.synchronize()
+        flags = self._buffer(feat, 2 * int(width) * int(height) * 4, "feature buffer")
+        self._aux_call("rt_render_features", (self._h, _abi.ptr(feat), int(width), int(height), int(kernel), flags), stream, sync)
 
     def denoise(self, src, feat, dst, width: int, height: int, iterations: int = 5, sigma_color: float = 2.0,
                 sigma_normal: float = 0.3, sigma_plane: float = 0.1, stream=None, sync: bool = True) -> None:
@@ -309,40 +310,22 @@ class RayTracer:
         into `dst` (may be `src`); all three numpy arrays, or all three torch CUDA tensors.  The
         accumulation buffer of a progressive render is `src`: it is only read."""
         px = int(width) * int(height)
-        f_src = self._frame_buffer(src, px * 4, "source frame")
-        f_feat = self._frame_buffer(feat, px * 8, "feature buffer")
-        f_dst = self._frame_buffer(dst, px * 4, "destination frame")
-        if not f_src == f_feat == f_dst:
-            raise ValueError("denoise: source, features and destination must all be host arrays or all device tensors")
+        flags = self._same_kind("denoise", [(src, px * 4, "source frame"), (feat, px * 8, "feature buffer"),
+                                            (dst, px * 4, "destination frame")], who="source, features and destination")
         prm = _abi.RtDenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_plane))
-        if sync and stream is None:
-            st = self._lib.rt_denoise(self._h, _abi.ptr(src), _abi.ptr(feat), _abi.ptr(dst), int(width), int(height),
-                                      ctypes.byref(prm), f_src)
-            self._check(st, "rt_denoise")
-        else:
-            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
-            st = self._lib.rt_denoise_async(self._h, _abi.ptr(src), _abi.ptr(feat), _abi.ptr(dst), int(width),
-                                            int(height), ctypes.byref(prm), f_src, sp)
-            self._check(st, "rt_denoise_async")
-            if sync:
-                self.synchronize()
+        args = (self._h, _abi.ptr(src), _abi.ptr(feat), _abi.ptr(dst), int(width), int(height), ctypes.byref(prm), flags)
+        self._aux_call("rt_denoise", args, stream, sync)
 
     def lastFeaturesMs(self) -> float:
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_features_ms(self._h, ctypes.byref(ms)), "rt_last_features_ms")
-        return ms.value
+        return self._last_ms("rt_last_features_ms")
 
     def lastDenoiseMs(self) -> float:
         """Device time of all passes of the last denoise, ms."""
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_denoise_ms(self._h, ctypes.byref(ms)), "rt_last_denoise_ms")
-        return ms.value
+        return self._last_ms("rt_last_denoise_ms")
 
     # ---- temporal reprojection of the displayed frame (pathtracer_rt.h, DESIGN.md §4.10) ----
     def reprojectDefaults(self) -> dict:
-        prm = _abi.RtReprojectParams()
-        self._check(self._lib.rt_reproject_defaults(ctypes.byref(prm)), "rt_reproject_defaults")
-        return dict(plane_tol=prm.plane_tol, normal_min=prm.normal_min, max_history=prm.max_history)
+        return self._defaults(_abi.RtReprojectParams, "rt_reproject_defaults")
 
     def reproject(self, prev_rgba, prev_len, prev_feat, prev_cam, cur_feat, out_rgba, out_len, width: int, height: int,
                   plane_tol: float = 0.01, normal_min: float = 0.9, max_history: float = 32.0, stream=None,
@@ -352,25 +335,17 @@ class RayTracer:
         over to the view whose features are `cur_feat`: `out_rgba`, `out_len`.  The six buffers are
         all numpy arrays or all torch CUDA tensors; the inputs are only read."""
         px = int(width) * int(height)
-        need = [(prev_rgba, 4, "previous frame"), (prev_len, 1, "previous history lengths"),
-                (prev_feat, 8, "previous feature buffer"), (cur_feat, 8, "feature buffer"),
-                (out_rgba, 4, "destination frame"), (out_len, 1, "destination history lengths")]
-        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
-        if len(set(flags)) != 1:
-            raise ValueError("reproject: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("reproject", [
+            (prev_rgba, px * 4, "previous frame"), (prev_len, px, "previous history lengths"),
+            (prev_feat, px * 8, "previous feature buffer"), (cur_feat, px * 8, "feature buffer"),
+            (out_rgba, px * 4, "destination frame"), (out_len, px, "destination history lengths")])
         cam = np.ascontiguousarray(prev_cam, np.float32)
         if cam.size != _abi.CAMERA_FLOATS:
             raise ValueError(f"prev_cam holds {cam.size} floats, {_abi.CAMERA_FLOATS} needed")
         prm = _abi.RtReprojectParams(float(plane_tol), float(normal_min), float(max_history))
         args = (self._h, _abi.ptr(prev_rgba), _abi.ptr(prev_len), _abi.ptr(prev_feat), _abi.ptr(cam), _abi.ptr(cur_feat),
-                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags[0])
-        if sync and stream is None:
-            self._check(self._lib.rt_reproject(*args), "rt_reproject")
-        else:
-            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
-            self._check(self._lib.rt_reproject_async(*args, sp), "rt_reproject_async")
-            if sync:
-                self.synchronize()
+                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags)
+        self._aux_call("rt_reproject", args, stream, sync)
 
     def temporalMerge(self, hist_rgba, hist_len, cur_rgba, n_cur: float, out_rgba, out_len, width: int, height: int,
                       max_history: float = 32.0, stream=None, sync: bool = True) -> None:
@@ -378,33 +353,20 @@ class RayTracer:
         of `n_cur` = max(progression, 1) frames into `out_rgba`, `out_len` (may be the history's
         buffers); all numpy arrays or all torch CUDA tensors.  `cur_rgba` is only read."""
         px = int(width) * int(height)
-        need = [(hist_rgba, 4, "history frame"), (hist_len, 1, "history lengths"), (cur_rgba, 4, "current frame"),
-                (out_rgba, 4, "destination frame"), (out_len, 1, "destination history lengths")]
-        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
-        if len(set(flags)) != 1:
-            raise ValueError("temporalMerge: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("temporalMerge", [
+            (hist_rgba, px * 4, "history frame"), (hist_len, px, "history lengths"), (cur_rgba, px * 4, "current frame"),
+            (out_rgba, px * 4, "destination frame"), (out_len, px, "destination history lengths")])
         args = (self._h, _abi.ptr(hist_rgba), _abi.ptr(hist_len), _abi.ptr(cur_rgba), float(n_cur), float(max_history),
-                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), flags[0])
-        if sync and stream is None:
-            self._check(self._lib.rt_temporal_merge(*args), "rt_temporal_merge")
-        else:
-            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
-            self._check(self._lib.rt_temporal_merge_async(*args, sp), "rt_temporal_merge_async")
-            if sync:
-                self.synchronize()
+                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), flags)
+        self._aux_call("rt_temporal_merge", args, stream, sync)
 
     def lastReprojectMs(self, merge: bool = False) -> float:
         """Device time of the last reprojection kernel, or (merge=True) of the last merge kernel, ms."""
-        ms = ctypes.c_float()
-        a, b = (None, ctypes.byref(ms)) if merge else (ctypes.byref(ms), None)
-        self._check(self._lib.rt_last_reproject_ms(self._h, a, b), "rt_last_reproject_ms")
-        return ms.value
+        return self._last_ms("rt_last_reproject_ms", 2, 1 if merge else 0)
 
     # ---- lag-adaptive trust of the carried history (pathtracer_rt.h, DESIGN.md §4.14) ----
     def trustDefaults(self) -> dict:
-        prm = _abi.RtTrustParams()
-        self._check(self._lib.rt_trust_defaults(ctypes.byref(prm)), "rt_trust_defaults")
-        return dict(tolerance=prm.tolerance, sigma_normal=prm.sigma_normal, sigma_plane=prm.sigma_plane)
+        return self._defaults(_abi.RtTrustParams, "rt_trust_defaults")
 
     def historyTrust(self, hist_rgba, hist_len, cur_rgba, n_cur: float, feat, out_len, width: int, height: int,
                      tolerance: float | None = None, sigma_normal: float = 0.3, sigma_plane: float = 0.1, stream=None,
@@ -416,23 +378,19 @@ class RayTracer:
         standard deviations (None: the library's default; inf: everything is trusted).  All numpy arrays
         or all torch CUDA tensors; the inputs are only read."""
         px = int(width) * int(height)
-        need = [(hist_rgba, 4, "history frame"), (hist_len, 1, "history lengths"), (cur_rgba, 4, "current frame"),
-                (feat, 8, "feature buffer"), (out_len, 1, "destination history lengths")]
-        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
-        if len(set(flags)) != 1:
-            raise ValueError("historyTrust: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("historyTrust", [
+            (hist_rgba, px * 4, "history frame"), (hist_len, px, "history lengths"), (cur_rgba, px * 4, "current frame"),
+            (feat, px * 8, "feature buffer"), (out_len, px, "destination history lengths")])
         if tolerance is None:
             tolerance = self.trustDefaults()["tolerance"]
         prm = _abi.RtTrustParams(float(tolerance), float(sigma_normal), float(sigma_plane))
         args = (self._h, _abi.ptr(hist_rgba), _abi.ptr(hist_len), _abi.ptr(cur_rgba), float(n_cur), _abi.ptr(feat),
-                _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags[0])
+                _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags)
         self._aux_call("rt_history_trust", args, stream, sync)
 
     def lastTrustMs(self) -> float:
         """Device time of the last historyTrust kernel, ms."""
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_trust_ms(self._h, ctypes.byref(ms)), "rt_last_trust_ms")
-        return ms.value
+        return self._last_ms("rt_last_trust_ms")
 
     # ---- carrying the displayed frame across updateMesh (pathtracer_rt.h, DESIGN.md §4.13) ----
     def meshPose(self, out=None, device: bool = False):
@@ -449,7 +407,7 @@ class RayTracer:
                 out = torch.empty((n, 3), dtype=torch.float32, device=f"cuda:{self.device}")
             else:
                 out = np.empty((n, 3), np.float32)
-        flags = self._frame_buffer(out, 3 * n, "pose buffer")
+        flags = self._buffer(out, 3 * n, "pose buffer")
         self._check(self._lib.rt_mesh_pose(self._h, _abi.ptr(out), n, flags), "rt_mesh_pose")
         return out
 
@@ -463,18 +421,14 @@ class RayTracer:
         if isinstance(prev_verts, np.ndarray):
             prev_verts = np.ascontiguousarray(prev_verts, np.float32)
         nv = (prev_verts.size if isinstance(prev_verts, np.ndarray) else prev_verts.numel()) // 3
-        flags = [self._frame_buffer(cur_feat, px * 8, "feature buffer"), self._frame_buffer(prev_verts, 3 * n, "earlier pose"),
-                 self._frame_buffer(out_feat, px * 8, "destination feature buffer")]
-        if len(set(flags)) != 1:
-            raise ValueError("warpFeatures: the buffers must all be host arrays or all device tensors")
-        args = (self._h, _abi.ptr(cur_feat), _abi.ptr(prev_verts), nv, _abi.ptr(out_feat), int(width), int(height), flags[0])
+        flags = self._same_kind("warpFeatures", [(cur_feat, px * 8, "feature buffer"), (prev_verts, 3 * n, "earlier pose"),
+                                                 (out_feat, px * 8, "destination feature buffer")])
+        args = (self._h, _abi.ptr(cur_feat), _abi.ptr(prev_verts), nv, _abi.ptr(out_feat), int(width), int(height), flags)
         self._aux_call("rt_warp_features", args, stream, sync)
 
     def lastWarpMs(self) -> float:
         """Device time of the last warpFeatures kernel, ms."""
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_warp_ms(self._h, ctypes.byref(ms)), "rt_last_warp_ms")
-        return ms.value
+        return self._last_ms("rt_last_warp_ms")
 
     # ---- carrying the displayed frame across sphere moves (pathtracer_rt.h, DESIGN.md §4.16) ----
     def warpFeaturesSpheres(self, cur_feat, prev_spheres, out_feat, width: int, height: int, stream=None,
@@ -496,35 +450,19 @@ class RayTracer:
             if prev_spheres.numel() % size:
                 raise ValueError(f"earlier spheres hold {prev_spheres.numel()} bytes, no multiple of {size}")
             n_prev, f_prev = prev_spheres.numel() // size, _abi.RT_OUT_DEVICE if prev_spheres.is_cuda else 0
-        flags = [self._frame_buffer(cur_feat, px * 8, "feature buffer"), f_prev,
-                 self._frame_buffer(out_feat, px * 8, "destination feature buffer")]
-        if len(set(flags)) != 1:
-            raise ValueError("warpFeaturesSpheres: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("warpFeaturesSpheres", [(cur_feat, px * 8, "feature buffer"),
+                                                        (out_feat, px * 8, "destination feature buffer")], also=(f_prev,))
         args = (self._h, _abi.ptr(cur_feat), _abi.ptr(prev_spheres) if n_prev else None, n_prev, _abi.ptr(out_feat),
-                int(width), int(height), flags[0])
+                int(width), int(height), flags)
         self._aux_call("rt_warp_features_spheres", args, stream, sync)
 
     def lastSphereWarpMs(self) -> float:
         """Device time of the last warpFeaturesSpheres kernel, ms."""
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_sphere_warp_ms(self._h, ctypes.byref(ms)), "rt_last_sphere_warp_ms")
-        return ms.value
+        return self._last_ms("rt_last_sphere_warp_ms")
 
     # ---- variance-guided display filter (pathtracer_rt.h, DESIGN.md §4.11) ----
     def denoiseVarDefaults(self) -> dict:
-        prm = _abi.RtDenoiseVarParams()
-        self._check(self._lib.rt_denoise_var_defaults(ctypes.byref(prm)), "rt_denoise_var_defaults")
-        return dict(iterations=prm.iterations, sigma_lum=prm.sigma_lum, sigma_normal=prm.sigma_normal,
-                    sigma_plane=prm.sigma_plane, min_len=prm.min_len)
-
-    def _aux_call(self, name: str, args: tuple, stream, sync: bool) -> None:
-        if sync and stream is None:
-            self._check(getattr(self._lib, name)(*args), name)
-        else:
-            sp = ctypes.c_void_p(stream) if isinstance(stream, int) else stream
-            self._check(getattr(self._lib, name + "_async")(*args, sp), name + "_async")
-            if sync:
-                self.synchronize()
+        return self._defaults(_abi.RtDenoiseVarParams, "rt_denoise_var_defaults")
 
     def momentsAccumulate(self, prev_rgba, cur_rgba, n_cur: float, mom_in, mom_out, width: int, height: int,
                           stream=None, sync: bool = True) -> None:
@@ -534,13 +472,11 @@ class RayTracer:
         buffer).  With n_cur == 1 `prev_rgba` and `mom_in` are not read and may be None.  All numpy
         arrays or all torch CUDA tensors; the accumulation buffers are only read."""
         px = int(width) * int(height)
-        need = [(prev_rgba, "previous accumulation"), (cur_rgba, "current accumulation"), (mom_in, "moments"),
-                (mom_out, "destination moments")]
-        flags = [self._frame_buffer(b, px * 4, what) for b, what in need if b is not None]
-        if len(set(flags)) != 1:
-            raise ValueError("momentsAccumulate: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("momentsAccumulate", [
+            (prev_rgba, px * 4, "previous accumulation"), (cur_rgba, px * 4, "current accumulation"),
+            (mom_in, px * 4, "moments"), (mom_out, px * 4, "destination moments")])
         args = (self._h, _abi.ptr(prev_rgba), _abi.ptr(cur_rgba), float(n_cur), _abi.ptr(mom_in), _abi.ptr(mom_out),
-                int(width), int(height), flags[0])
+                int(width), int(height), flags)
         self._aux_call("rt_moments_accumulate", args, stream, sync)
 
     def variance(self, disp_rgba, mom_rgba, length, feat, out_var, width: int, height: int, sigma_normal: float = 0.3,
@@ -550,14 +486,12 @@ class RayTracer:
         feature-weighted window of `disp_rgba`, the frame about to be displayed.  All numpy arrays or
         all torch CUDA tensors; the inputs are only read."""
         px = int(width) * int(height)
-        need = [(disp_rgba, 4, "displayed frame"), (mom_rgba, 4, "moments"), (length, 1, "history lengths"),
-                (feat, 8, "feature buffer"), (out_var, 1, "destination variance")]
-        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need]
-        if len(set(flags)) != 1:
-            raise ValueError("variance: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("variance", [
+            (disp_rgba, px * 4, "displayed frame"), (mom_rgba, px * 4, "moments"), (length, px, "history lengths"),
+            (feat, px * 8, "feature buffer"), (out_var, px, "destination variance")])
         prm = _abi.RtDenoiseVarParams(5, 4.0, float(sigma_normal), float(sigma_plane), float(min_len))
         args = (self._h, _abi.ptr(disp_rgba), _abi.ptr(mom_rgba), _abi.ptr(length), _abi.ptr(feat), _abi.ptr(out_var),
-                int(width), int(height), ctypes.byref(prm), flags[0])
+                int(width), int(height), ctypes.byref(prm), flags)
         self._aux_call("rt_variance", args, stream, sync)
 
     def denoiseVar(self, src, var, feat, dst, dst_var, width: int, height: int, iterations: int = 5,
@@ -567,53 +501,25 @@ class RayTracer:
         (W*H floats, `variance`) guided by `feat` into `dst` (may be `src`) and `dst_var` (may be
         `var`, or None); all numpy arrays or all torch CUDA tensors."""
         px = int(width) * int(height)
-        need = [(src, 4, "source frame"), (var, 1, "variance"), (feat, 8, "feature buffer"), (dst, 4, "destination frame"),
-                (dst_var, 1, "destination variance")]
-        flags = [self._frame_buffer(b, px * k, what) for b, k, what in need if b is not None]
-        if len(set(flags)) != 1:
-            raise ValueError("denoiseVar: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("denoiseVar", [
+            (src, px * 4, "source frame"), (var, px, "variance"), (feat, px * 8, "feature buffer"),
+            (dst, px * 4, "destination frame"), (dst_var, px, "destination variance")])
         prm = _abi.RtDenoiseVarParams(int(iterations), float(sigma_lum), float(sigma_normal), float(sigma_plane), 4.0)
         args = (self._h, _abi.ptr(src), _abi.ptr(var), _abi.ptr(feat), _abi.ptr(dst), _abi.ptr(dst_var), int(width),
-                int(height), ctypes.byref(prm), flags[0])
+                int(height), ctypes.byref(prm), flags)
         self._aux_call("rt_denoise_var", args, stream, sync)
 
     def lastVarianceMs(self, which: str = "denoise_var") -> float:
         """Device time of the last `moments` kernel, `variance` kernel, or of all passes of the last
         `denoise_var`, ms."""
-        k = ("moments", "variance", "denoise_var").index(which)
-        ms = ctypes.c_float()
-        a = [None, None, None]
-        a[k] = ctypes.byref(ms)
-        self._check(self._lib.rt_last_variance_ms(self._h, *a), "rt_last_variance_ms")
-        return ms.value
+        return self._last_ms("rt_last_variance_ms", 3, ("moments", "variance", "denoise_var").index(which))
 
     # ---- tone-mapped 8-bit display output with auto-exposure (pathtracer_rt.h, DESIGN.md §4.15) ----
-    @staticmethod
-    def _word_buffer(buf, need: int, what: str) -> int:
-        """_frame_buffer for a buffer of 32-bit words (uint32 or int32)."""
-        if isinstance(buf, np.ndarray):
-            if buf.dtype not in (np.uint32, np.int32) or not buf.flags["C_CONTIGUOUS"]:
-                raise ValueError(f"{what} must be a contiguous uint32 array")
-            n, dev = buf.size, 0
-        else:
-            if buf.dtype.__str__() not in ("torch.uint32", "torch.int32"):
-                raise TypeError(f"{what} must be uint32 or int32")
-            if not buf.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
-            n, dev = buf.numel(), _abi.RT_OUT_DEVICE if getattr(buf, "is_cuda", False) else 0
-        if n < need:
-            raise ValueError(f"{what} holds {n} words, {need} needed")
-        return dev
-
     def toneMapDefaults(self) -> dict:
-        prm = _abi.RtTonemapParams()
-        self._check(self._lib.rt_tonemap_defaults(ctypes.byref(prm)), "rt_tonemap_defaults")
-        return dict(curve=prm.curve, srgb=prm.srgb, dither=prm.dither, exposure=prm.exposure, white=prm.white)
+        return self._defaults(_abi.RtTonemapParams, "rt_tonemap_defaults")
 
     def meterDefaults(self) -> dict:
-        prm = _abi.RtMeterParams()
-        self._check(self._lib.rt_meter_defaults(ctypes.byref(prm)), "rt_meter_defaults")
-        return dict(key=prm.key, lo=prm.lo, hi=prm.hi, e_min=prm.e_min, e_max=prm.e_max, rate=prm.rate)
+        return self._defaults(_abi.RtMeterParams, "rt_meter_defaults")
 
     def meterExposure(self, rgba, exposure, width: int, height: int, hist=None, stream=None, sync: bool = True,
                       **params) -> None:
@@ -623,14 +529,11 @@ class RayTracer:
         (key, lo, hi, e_min, e_max, rate).  All numpy arrays or all torch CUDA tensors; the frame is
         only read."""
         px = int(width) * int(height)
-        flags = [self._frame_buffer(rgba, px * 4, "frame"), self._frame_buffer(exposure, 1, "exposure")]
-        if hist is not None:
-            flags.append(self._word_buffer(hist, _abi.RT_METER_BINS, "histogram"))
-        if len(set(flags)) != 1:
-            raise ValueError("meterExposure: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("meterExposure", [(rgba, px * 4, "frame"), (exposure, 1, "exposure"),
+                                                  (hist, _abi.RT_METER_BINS, "histogram", self._WORDS)])
         prm = _abi.RtMeterParams(**{**self.meterDefaults(), **{k: float(v) for k, v in params.items()}})
         args = (self._h, _abi.ptr(rgba), _abi.ptr(exposure), _abi.ptr(hist), int(width), int(height), ctypes.byref(prm),
-                flags[0])
+                flags)
         self._aux_call("rt_meter_exposure", args, stream, sync)
 
     def toneMap(self, rgba, out_rgba8, width: int, height: int, exposure=None, stream=None, sync: bool = True,
@@ -641,31 +544,23 @@ class RayTracer:
         other than the library's defaults (curve, srgb, dither, white).  All numpy arrays or all torch CUDA
         tensors; the frame is only read."""
         px = int(width) * int(height)
-        flags = [self._frame_buffer(rgba, px * 4, "frame"), self._word_buffer(out_rgba8, px, "destination 8-bit frame")]
         d = {**self.toneMapDefaults(), **params}
         if isinstance(exposure, (int, float, np.floating)):
             d["exposure"], exposure = float(exposure), None
-        if exposure is not None:
-            flags.append(self._frame_buffer(exposure, 1, "exposure"))
-        if len(set(flags)) != 1:
-            raise ValueError("toneMap: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("toneMap", [(rgba, px * 4, "frame"), (out_rgba8, px, "destination 8-bit frame", self._WORDS),
+                                            (exposure, 1, "exposure")])
         prm = _abi.RtTonemapParams(int(d["curve"]), int(d["srgb"]), int(d["dither"]), float(d["exposure"]), float(d["white"]))
         args = (self._h, _abi.ptr(rgba), _abi.ptr(exposure), _abi.ptr(out_rgba8), int(width), int(height), ctypes.byref(prm),
-                flags[0])
+                flags)
         self._aux_call("rt_tonemap", args, stream, sync)
 
     def lastToneMapMs(self, meter: bool = False) -> float:
         """Device time of the last tone-map kernel, or (meter=True) of the last meter, ms."""
-        ms = ctypes.c_float()
-        a, b = (ctypes.byref(ms), None) if meter else (None, ctypes.byref(ms))
-        self._check(self._lib.rt_last_tonemap_ms(self._h, a, b), "rt_last_tonemap_ms")
-        return ms.value
+        return self._last_ms("rt_last_tonemap_ms", 2, 0 if meter else 1)
 
     # ---- the noise meter (pathtracer_rt.h, DESIGN.md §4.17) ----
     def noiseDefaults(self) -> dict:
-        prm = _abi.RtNoiseParams()
-        self._check(self._lib.rt_noise_defaults(ctypes.byref(prm)), "rt_noise_defaults")
-        return dict(percentile=prm.percentile, threshold=prm.threshold, lum_floor=prm.lum_floor)
+        return self._defaults(_abi.RtNoiseParams, "rt_noise_defaults")
 
     def noiseMeter(self, rgba, var, width: int, height: int, percentile: float | None = None,
                    threshold: float | None = None, lum_floor: float | None = None, tiles=None, hist=None, stats=None,
@@ -681,19 +576,13 @@ class RayTracer:
         given, nothing is read back and None is returned."""
         px = int(width) * int(height)
         n_tiles = ((int(width) + 7) // 8) * ((int(height) + 7) // 8)
-        flags = [self._frame_buffer(rgba, px * 4, "frame"), self._frame_buffer(var, px, "variance")]
-        if tiles is not None:
-            flags.append(self._frame_buffer(tiles, 2 * n_tiles, "tile map"))
-        if hist is not None:
-            flags.append(self._word_buffer(hist, _abi.RT_METER_BINS, "histogram"))
-        if stats is not None:
-            flags.append(self._word_buffer(stats, 4, "stats"))
-        if len(set(flags)) != 1:
-            raise ValueError("noiseMeter: the buffers must all be host arrays or all device tensors")
+        flags = self._same_kind("noiseMeter", [
+            (rgba, px * 4, "frame"), (var, px, "variance"), (tiles, 2 * n_tiles, "tile map"),
+            (hist, _abi.RT_METER_BINS, "histogram", self._WORDS), (stats, 4, "stats", self._WORDS)])
         if stats is None:
             if not sync:
                 raise ValueError("noiseMeter: sync=False needs a stats buffer")
-            if flags[0]:
+            if flags:
                 import torch
 
                 stats = torch.zeros(4, dtype=torch.int32, device=rgba.device)
@@ -705,7 +594,7 @@ class RayTracer:
                 d[k] = float(v)
         prm = _abi.RtNoiseParams(d["percentile"], d["threshold"], d["lum_floor"])
         args = (self._h, _abi.ptr(rgba), _abi.ptr(var), _abi.ptr(stats), _abi.ptr(tiles), _abi.ptr(hist), int(width),
-                int(height), ctypes.byref(prm), flags[0])
+                int(height), ctypes.byref(prm), flags)
         self._aux_call("rt_noise_meter", args, stream, sync)
         if not sync:
             return None
@@ -715,9 +604,7 @@ class RayTracer:
 
     def lastNoiseMs(self) -> float:
         """Device time of the last noise meter, ms."""
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_noise_ms(self._h, ctypes.byref(ms)), "rt_last_noise_ms")
-        return ms.value
+        return self._last_ms("rt_last_noise_ms")
 
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
@@ -761,9 +648,7 @@ class RayTracer:
         return d
 
     def lastKernelMs(self) -> float:
-        ms = ctypes.c_float()
-        self._check(self._lib.rt_last_kernel_ms(self._h, ctypes.byref(ms)), "rt_last_kernel_ms")
-        return ms.value
+        return self._last_ms("rt_last_kernel_ms")
 
     def lastKernelSplitMs(self) -> tuple[float, float]:
         """(candidate-list pre-pass, main kernel) device times of the last render, ms."""

@@ -24,7 +24,7 @@ CASE = "tris_64x48_sr1"
 F = np.float32
 U = np.uint32
 TW, TH = 37, 29  # the tone-map frame: every Bayer cell, no multiple of 8, more than one block
-SIZES = [(1, 1), (63, 1), (65, 3), (37, 29), (300, 200)]
+SIZES = [(1, 1), (63, 1), (65, 3), (37, 29), (300, 200), (520, 512)]
 
 
 @pytest.fixture(scope="module")
@@ -107,7 +107,8 @@ def test_constructed_inputs_reach_every_bin():
 @pytest.mark.parametrize("w,h", SIZES)
 def test_histogram_equals_numpy(w, h, rt, oracle):
     """Host arrays and device tensors, with and without hist_out; 300 x 200 has 235 blocks, so the flush
-    into global memory runs many times; the frame is only read."""
+    into global memory runs many times; 520 x 512 has 1040 blocks of 256 pixels against the grid's 1024, so
+    some blocks take a second trip through the grid-stride loop; the frame is only read."""
     for seed in (0, 1, 2) if w * h < 1000 else (0,):
         frame = hist_frame(w, h, seed)
         keep = frame.copy()
@@ -345,6 +346,48 @@ def test_argument_checks(pt, rt):
         assert t._lib.rt_last_tonemap_ms(t._h, None, None) == ab.RT_ERR_ARG
     finally:
         t.close()
+
+
+MIXED = ["denoise", "reproject", "temporalMerge", "historyTrust", "warpFeatures", "warpFeaturesSpheres",
+         "momentsAccumulate", "variance", "denoiseVar", "meterExposure", "toneMap", "noiseMeter"]
+
+
+@pytest.fixture(scope="module")
+def untouched(pt):
+    """A tracer no call has failed on: its last error is empty."""
+    t = pt.RayTracer(0)
+    yield t
+    t.close()
+
+
+@pytest.mark.parametrize("method", MIXED)
+def test_mixed_host_and_device_buffers(method, pt, untouched):
+    """Every display method of RayTracer, with one buffer a CUDA tensor and the rest numpy arrays: a
+    ValueError before any call crosses the ABI, so the library's last error stays empty."""
+    t = untouched
+    w, h = 5, 3
+    px = w * h
+    c4, f8, l1 = np.zeros(px * 4, F), np.zeros(px * 8, F), np.ones(px, F)
+    d4, d8, d1 = device(c4), device(f8), device(l1)
+    cam = np.zeros(pt._abi.CAMERA_FLOATS, F)
+    calls = {
+        "denoise": lambda: t.denoise(c4, f8, d4, w, h),
+        "reproject": lambda: t.reproject(c4, l1, f8, cam, f8, c4.copy(), d1, w, h),
+        "temporalMerge": lambda: t.temporalMerge(c4, l1, c4.copy(), 2.0, c4.copy(), d1, w, h),
+        "historyTrust": lambda: t.historyTrust(c4, l1, c4.copy(), 2.0, f8, d1, w, h),
+        "warpFeatures": lambda: t.warpFeatures(f8, np.zeros((0, 3), F), d8, w, h),
+        "warpFeaturesSpheres": lambda: t.warpFeaturesSpheres(f8, np.zeros(0, pt._abi.SPHERE_DTYPE), d8, w, h),
+        "momentsAccumulate": lambda: t.momentsAccumulate(c4, c4.copy(), 2.0, c4.copy(), d4, w, h),
+        "variance": lambda: t.variance(c4, c4.copy(), l1, f8, d1, w, h),
+        "denoiseVar": lambda: t.denoiseVar(c4, l1, f8, c4.copy(), d1, w, h),
+        "meterExposure": lambda: t.meterExposure(c4, device(np.zeros(1, F)), w, h),
+        "toneMap": lambda: t.toneMap(c4, device(np.zeros(px, U)), w, h),
+        "noiseMeter": lambda: t.noiseMeter(c4, d1, w, h),
+    }
+    assert sorted(calls) == sorted(MIXED)
+    with pytest.raises(ValueError, match="must all be host arrays or all device tensors"):
+        calls[method]()
+    assert t._lib.rt_last_error(t._h) == b""
 
 
 def test_render_state_untouched(pt, golden, golden_meta, oracle):
