@@ -103,6 +103,17 @@
  *                    restart(), a key, a drag, a reshape, updateMesh or sceneChanged() — which then ask for
  *                    a redisplay as they do after maxProgression.  What is displayed does not change.  Off
  *                    (the default), nothing changes, allocation included.
+ *   setAdaptive(on, params)  (no counterpart in the reference) with setConverge, in a view of RT_KERNEL_TRIS without
+ *                    setTemporal: stop tracing the 8x8 tiles the noise meter calls quiet.  The
+ *                    view keeps a stop plane on the device (a word per tile: 0 = refined, k = stopped after k
+ *                    frames) that masks its renders (rt_set_tile_stop); the moments and the history lengths
+ *                    follow it (rt_moments_accumulate_tiles), the meter's tile map is always computed, and once
+ *                    the view's moments hold setConverge's minFrames frames rt_tile_stop_select updates the plane
+ *                    on the device after every traced display.  A stopped tile keeps its pixels and stays
+ *                    stopped until the plane is zeroed: at a (re)allocation, a key, a drag, restart(),
+ *                    updateMesh and sceneChanged().  The view is converged() by setConverge's rule, or when no
+ *                    tile is live.  In any other view (adaptiveInEffect() false) and off (the default), nothing
+ *                    changes and no plane is set.
  *   setFloatReadback(on)  with setToneMap: off, display() reads back only the 8-bit frame (a quarter of
  *                    the bytes) and pixels() keeps its last contents — those of the last display with the
  *                    readback on, zeros before any; rawPixels() still fetches the accumulation buffer.  On
@@ -129,6 +140,10 @@ public:
     ProgressiveViewHIP(RayTracerHIP &rt, unsigned width, unsigned height, int kernel = RT_KERNEL_SPHERES)
         : rt_(rt), width_(width), height_(height), kernel_(kernel), buf_(new Buffers)
     {
+    }
+    ~ProgressiveViewHIP()
+    {
+        if (planeSet_) rt_set_tile_stop(rt_.handle(), nullptr, 0, 0, 0); /* the tracer outlives the view's plane */
     }
     ProgressiveViewHIP(const ProgressiveViewHIP &) = delete;
     ProgressiveViewHIP &operator=(const ProgressiveViewHIP &) = delete;
@@ -186,6 +201,7 @@ public:
         converged_ = false;
         progression_ = 0;
         carry_ = true;
+        stopReset_ = true; /* setAdaptive: every tile is live again */
         return post;
     }
 
@@ -319,6 +335,23 @@ public:
     void setNoiseMapReadback(bool on) { noiseMapReadback_ = on; }
     const std::vector<float> &noiseMap() const { return noiseMap_; }
 
+    /* (no counterpart in the reference) adaptive sampling on the meter's tile map: see the
+       file comment.  params.min_frames holds beside setConverge's minFrames: no tile stops before both. */
+    void setAdaptive(bool on, const rt_adaptive_params &params = RayTracerHIP::adaptiveDefaults())
+    {
+        if (on != adaptive_) stopReset_ = true;
+        adaptive_ = on;
+        adaptiveParams_ = params;
+        converged_ = false; /* the next traced display decides afresh */
+    }
+    bool adaptiveInEffect() const { return adaptive_ && converge_ && kernel_ == RT_KERNEL_TRIS && !temporal_; }
+    /* the stop rule's figures after the last traced display with setAdaptive in effect (zeros before one) */
+    const rt_adaptive_stats &adaptiveStats() const { return adaptiveStats_; }
+    /* With setAdaptive in effect: also read the stop plane back at every traced display into stopMap():
+       ceil(W/8) ceil(H/8) words, row-major, bottom tile row first. */
+    void setStopMapReadback(bool on) { stopMapReadback_ = on; }
+    const std::vector<uint32_t> &stopMap() const { return stopMap_; }
+
     /* (no counterpart in the reference) the tone-mapped 8-bit display output */
     void setToneMap(bool on, const rt_tonemap_params &params = RayTracerHIP::toneMapDefaults(), bool autoExposure = true,
                     const rt_meter_params &meter = RayTracerHIP::meterDefaults())
@@ -433,6 +466,9 @@ private:
         DeviceFloats tone8, exposure;
         /* setConverge: the meter's stats (four words) and, with setNoiseMapReadback, the tile pairs */
         DeviceFloats noiseStats, noiseTiles;
+        /* setAdaptive: the stop plane (a word per tile) and the stop rule's stats (four words); the per-pixel
+           history lengths are in `len` */
+        DeviceFloats stop, adaptStats;
     };
     /* setVarianceGuided or setConverge: the view keeps the accumulation copy, the moments and the variance plane */
     bool momentsWanted() const { return varGuided_ || converge_; }
@@ -445,15 +481,20 @@ private:
         posePending_ = false;
         spheresPending_ = false;
         if (moments) momValid_ = false;
+        if (moments) stopReset_ = true; /* the moments start afresh: so do the tiles */
     }
     void allocate()
     {
+        clearPlane(); /* (the tracer borrows the old size's plane) */
         buf_.reset(new Buffers); /* frees the old size's buffers, the pose snapshot among them */
         buf_->dev.need((size_t)width_ * height_ * 4, "framebuffer");
         pbo_.assign((size_t)width_ * height_ * 4, 0.0f);
         pbo8_.clear();
         noiseMap_.clear();
         noiseStats_ = rt_noise_stats{};
+        adaptiveStats_ = rt_adaptive_stats{};
+        stopMap_.clear();
+        stopReset_ = true;
         converged_ = false;
         frames_ = 0;
         exposureReset_ = true;
@@ -584,13 +625,31 @@ private:
     /* setConverge: meter what stage (6) chose to show, before any filter, with the variance plane just
        estimated for it; the stats (and with setNoiseMapReadback the tile pairs) stay on the device
        until the frame's readback. */
-    void meterShown(const float *shown, bool sync)
+    void meterShown(const float *shown, bool sync, bool tiles)
     {
         Buffers &b = *buf_;
         b.noiseStats.need(sizeof(rt_noise_stats) / sizeof(float), "noise stats");
-        if (noiseMapReadback_) b.noiseTiles.need(2 * noiseTileCount(), "noise tile map");
-        rt_.noiseMeter(shown, b.var.p, reinterpret_cast<rt_noise_stats *>(b.noiseStats.p), noiseMapReadback_ ? b.noiseTiles.p : nullptr,
+        if (tiles) b.noiseTiles.need(2 * noiseTileCount(), "noise tile map");
+        rt_.noiseMeter(shown, b.var.p, reinterpret_cast<rt_noise_stats *>(b.noiseStats.p), tiles ? b.noiseTiles.p : nullptr,
                        nullptr, width_, height_, convergeParams_, true, sync);
+    }
+    /* setAdaptive: the tracer's renders are whole frames again */
+    void clearPlane()
+    {
+        if (planeSet_) rt_.setTileStop(nullptr);
+        planeSet_ = false;
+    }
+    /* setAdaptive in effect: the view's plane, zeroed where the accumulation starts afresh, masks the renders */
+    void maskRenders()
+    {
+        Buffers &b = *buf_;
+        b.stop.need(noiseTileCount(), "stop plane");
+        b.adaptStats.need(sizeof(rt_adaptive_stats) / sizeof(float), "stop rule stats");
+        if (stopReset_ && (hipMemset(b.stop.p, 0, noiseTileCount() * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+            throw std::runtime_error("ProgressiveViewHIP: stop plane reset failed");
+        stopReset_ = false;
+        if (!planeSet_) rt_.setTileStop(reinterpret_cast<const uint32_t *>(b.stop.p), width_, height_, true);
+        planeSet_ = true;
     }
     /* One traced display, whatever is switched on: render, then compose what is shown from the
        accumulation buffer, which every stage only reads. */
@@ -599,13 +658,24 @@ private:
         Buffers &b = *buf_;
         const size_t px = (size_t)width_ * height_;
         const float n = (float)(progression_ > 1 ? progression_ : 1);
+        const bool adapt = adaptiveInEffect();
         if (momentsWanted()) keepAccumulation();
+        if (adapt) maskRenders();
+        else {
+            clearPlane();
+            stopReset_ = true; /* (in effect again later: from a zero plane) */
+        }
         rt_.rayTrace(b.dev.p, width_, height_, progression_, kernel_, true);
         if (momentsWanted()) {
             b.mom.need(4 * px, "moments buffer");
             /* (without valid moments, after it was switched on in mid-accumulation: start from this frame) */
             const float nMom = momValid_ ? n : 1.0f;
-            rt_.momentsAccumulate(b.accPrev.p, b.dev.p, nMom, b.mom.p, b.mom.p, width_, height_, true);
+            if (adapt) { /* a stopped tile keeps its moments, and its pixels the length it stopped at */
+                b.len.need(px, "history length buffer");
+                rt_.momentsAccumulateTiles(b.accPrev.p, b.dev.p, nMom, b.mom.p, b.mom.p, reinterpret_cast<const uint32_t *>(b.stop.p),
+                                           b.len.p, width_, height_, true);
+            } else
+                rt_.momentsAccumulate(b.accPrev.p, b.dev.p, nMom, b.mom.p, b.mom.p, width_, height_, true);
             momValid_ = true;
             frames_ = nMom == 1.0f ? 1u : frames_ + 1u; /* the frames in the view's own moments */
         }
@@ -618,14 +688,20 @@ private:
             moments = b.moments.kept.rgba();
             len = b.colour.kept.len();
         } else if (momentsWanted()) {
-            len = constantLengths(n);
+            len = adapt ? b.len.p : constantLengths(n);
         }
         if (varGuided_ || denoise_) b.den.need(4 * px, "denoised framebuffer");
         if (momentsWanted()) {
             b.var.need(px, "variance buffer");
             rt_.variance(shown, moments, len, b.feat.p, b.var.p, width_, height_, varParams_, true);
         }
-        if (converge_) meterShown(shown, /*sync=*/!varGuided_ && !denoise_); /* (a filter's call waits for the stream) */
+        /* (the last of these calls waits for the stream, unless a filter's call does) */
+        const bool select = adapt && frames_ >= convergeMinFrames_;
+        if (converge_) meterShown(shown, /*sync=*/!varGuided_ && !denoise_ && !select, noiseMapReadback_ || adapt);
+        if (select) /* the plane the next render is masked by, from this display's tile map */
+            rt_.tileStopSelect(b.noiseTiles.p, reinterpret_cast<uint32_t *>(b.stop.p), (uint32_t)n,
+                               reinterpret_cast<rt_adaptive_stats *>(b.adaptStats.p), width_, height_, adaptiveParams_, true,
+                               /*sync=*/!varGuided_ && !denoise_);
         if (varGuided_) { /* in place of setDenoise's filter, whether that is on or not */
             rt_.denoiseVar(shown, b.var.p, b.feat.p, b.den.p, nullptr, width_, height_, varParams_, true);
             shown = b.den.p;
@@ -653,6 +729,17 @@ private:
             }
             if (!ok) throw std::runtime_error("ProgressiveViewHIP: noise stats readback failed");
             converged_ = frames_ >= convergeMinFrames_ && noiseStats_.counted > 0 && noiseStats_.level <= convergeParams_.threshold;
+        }
+        if (adapt) { /* the stop rule's sixteen bytes, and the other way to be done: no tile is live */
+            const uint32_t tiles = (uint32_t)noiseTileCount();
+            adaptiveStats_ = rt_adaptive_stats{tiles, tiles, 0u, (uint32_t)n}; /* before the first select the plane is zero */
+            bool ok = !select || hipMemcpy(&adaptiveStats_, b.adaptStats.p, sizeof adaptiveStats_, hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && stopMapReadback_) {
+                stopMap_.resize(tiles);
+                ok = hipMemcpy(stopMap_.data(), b.stop.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+            }
+            if (!ok) throw std::runtime_error("ProgressiveViewHIP: stop rule readback failed");
+            converged_ = converged_ || adaptiveStats_.active == 0u;
         }
         if (sphereCarry_ && kernel_ != RT_KERNEL_TRIS) { /* the spheres this frame was displayed with */
             shownSpheres_ = rt_.spheres();
@@ -687,6 +774,11 @@ private:
     rt_noise_params convergeParams_ = RayTracerHIP::noiseDefaults();
     rt_noise_stats noiseStats_{};
     std::vector<float> noiseMap_;
+    /* setAdaptive: on; the plane is to be zeroed before the next render; the tracer holds the view's plane */
+    bool adaptive_ = false, stopReset_ = true, planeSet_ = false, stopMapReadback_ = false;
+    rt_adaptive_params adaptiveParams_ = RayTracerHIP::adaptiveDefaults();
+    rt_adaptive_stats adaptiveStats_{};
+    std::vector<uint32_t> stopMap_;
     bool toneMap_ = false, autoExposure_ = true, exposureReset_ = true, floatReadback_ = true;
     rt_tonemap_params toneParams_ = RayTracerHIP::toneMapDefaults();
     rt_meter_params meterParams_ = RayTracerHIP::meterDefaults();

@@ -463,6 +463,48 @@ public:
         check(rt_last_noise_ms(ctx_, &ms), "lastNoiseMs");
         return ms;
     }
+    /* (no counterpart in the reference) adaptive sampling on the tile map */
+    static rt_adaptive_params adaptiveDefaults()
+    {
+        rt_adaptive_params p;
+        rt_adaptive_defaults(&p);
+        return p;
+    }
+    /* The stop plane (a word per 8x8 tile, 0 = rendered) that masks the raytrace_tris renders of width x
+       height from now on; NULL clears it.  A host plane is copied; a device plane is borrowed and read at
+       every render. */
+    void setTileStop(const uint32_t *stop, unsigned width = 0, unsigned height = 0, bool on_device = false)
+    {
+        check(rt_set_tile_stop(ctx_, stop, width, height, on_device ? RT_OUT_DEVICE : 0), "setTileStop");
+    }
+    /* The stop rule on noiseMeter's tile map: stop_io updated in place, *stats_out the counts.  sync = false
+       (device buffers): enqueued on the tracer's stream without a wait. */
+    void tileStopSelect(const float *tiles_mean_max, uint32_t *stop_io, uint32_t n_frames, rt_adaptive_stats *stats_out,
+                        unsigned width, unsigned height, const rt_adaptive_params &params = adaptiveDefaults(),
+                        bool on_device = false, bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_tile_stop_select(ctx_, tiles_mean_max, stop_io, n_frames, stats_out, width, height, &params, flags)
+                   : rt_tile_stop_select_async(ctx_, tiles_mean_max, stop_io, n_frames, stats_out, width, height, &params,
+                                               flags, nullptr),
+              "tileStopSelect");
+    }
+    /* momentsAccumulate under a stop plane, with the per-pixel history lengths `variance` takes. */
+    void momentsAccumulateTiles(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in,
+                                float *mom_out, const uint32_t *stop, float *len_out, unsigned width, unsigned height,
+                                bool on_device = false)
+    {
+        check(rt_moments_accumulate_tiles(ctx_, prev_rgba, cur_rgba, n_cur, mom_in, mom_out, stop, len_out, width, height,
+                                          on_device ? RT_OUT_DEVICE : 0),
+              "momentsAccumulateTiles");
+    }
+    /* Device time of the last stop rule, or (order) of the last masked order kernel, ms. */
+    float lastAdaptiveMs(bool order = false) const
+    {
+        float ms = 0.0f;
+        check(rt_last_adaptive_ms(ctx_, order ? nullptr : &ms, order ? &ms : nullptr), "lastAdaptiveMs");
+        return ms;
+    }
 
     rt_counters counters() const
     {

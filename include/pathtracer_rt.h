@@ -663,6 +663,83 @@ int rt_noise_meter_async(rt_ctx *ctx, const float *rgba, const float *var, rt_no
    RT_ERR_STATE when it has not run. */
 int rt_last_noise_ms(const rt_ctx *ctx, float *ms);
 
+/* ---- adaptive sampling: stop tracing the tiles the noise meter calls quiet.  A stop
+   plane holds one word per 8x8 tile of a frame, ceil(width / 8) x ceil(height / 8) words, row-major, the
+   tiles rt_noise_meter's tiles_out is on: 0 = the tile is refined, k > 0 = it stopped after k frames.
+   Triangle kernel only (the sphere kernels' seed rows shift with the progression), whole frames only. ---- */
+/* Sets the plane that masks the context's renders (stop == NULL: clears it; width, height and flags are
+   then not read).  A host pointer is copied at the call (after the renders in flight).  With
+   RT_OUT_DEVICE the pointer is borrowed: it is read on each render's stream, so the caller may change
+   its contents between renders (ordered against them by the caller), and must keep it alive until it is
+   cleared or replaced.  While a plane is set, rt_render / rt_render_async of RT_KERNEL_TRIS with tile ==
+   NULL and the plane's width x height renders only the tiles whose word is 0: every pixel of such a tile
+   gets exactly the framebuffer value and seed words the unmasked render would have given it, every pixel
+   of any other tile keeps its framebuffer value and both seed words.  Such a render is always a
+   whole-pixel launch (no sample split, no pilot render), records no pixel costs, and its counters count
+   the live tiles' rays.  Any other render while a plane is set — another kernel, a tile, another size —
+   is RT_ERR_ARG, never a silent full render.  The display-side calls are not affected.  RT_ERR_ARG for
+   an empty or oversized frame and for flags other than RT_OUT_DEVICE. */
+int rt_set_tile_stop(rt_ctx *ctx, const uint32_t *stop, uint32_t width, uint32_t height, int flags);
+typedef struct rt_adaptive_params {
+    float threshold;     /* a tile's mean relative error at or under which it is quiet; >= 0 */
+    float max_ratio;     /* ... with its maximum at or under threshold max_ratio; >= 1, +INFINITY: the term is off */
+    uint32_t min_frames; /* no tile is quiet before the view has this many frames */
+    uint32_t dilate;     /* a tile stops only when every tile within this many tiles of it is settled; 0..4 */
+} rt_adaptive_params;
+typedef struct rt_adaptive_stats {
+    uint32_t tiles;       /* the tile count */
+    uint32_t active;      /* the live tiles after the call */
+    uint32_t stopped_now; /* the tiles this call stopped */
+    uint32_t frames;      /* n_frames */
+} rt_adaptive_stats;
+int rt_adaptive_defaults(rt_adaptive_params *p); /* 0.05f, 4.0f, 16, 1 */
+/* The stop rule.  tiles_mean_max: rt_noise_meter's tiles_out, pairs (mean, max).  Tile t is quiet when
+   n_frames >= min_frames, mean <= threshold and max <= lim, with lim the float product threshold
+   max_ratio formed by the host, or +INFINITY when max_ratio is (a NaN of the map is under neither; a
+   tile with no valid pixel reads (0, 0) and is quiet).  It is settled when stop_io[t] != 0 or it is
+   quiet.  A live tile (stop_io[t] == 0) is stopped, stop_io[t] = n_frames, exactly when every tile
+   inside the frame within `dilate` tiles of it (Chebyshev distance, itself included) is settled; every
+   tile is decided from the plane as it was before the call.  A stopped tile's word is never changed:
+   stopping is monotone.  Only comparisons and integers: the result is exact.  The rules of the display
+   stages hold: no render state is changed, `flags` takes RT_OUT_DEVICE only (with it every buffer is a
+   device pointer, stats_out included), the same stream ordering — a render enqueued after the call
+   sees the new plane.  Null pointers, an empty frame, n_frames == 0, threshold negative or NaN,
+   max_ratio < 1 or NaN, dilate > 4, overlapping buffers: RT_ERR_ARG. */
+int rt_tile_stop_select(rt_ctx *ctx, const float *tiles_mean_max, uint32_t *stop_io, uint32_t n_frames,
+                        rt_adaptive_stats *stats_out, uint32_t width, uint32_t height, const rt_adaptive_params *params,
+                        int flags);
+int rt_tile_stop_select_async(rt_ctx *ctx, const float *tiles_mean_max, uint32_t *stop_io, uint32_t n_frames,
+                              rt_adaptive_stats *stats_out, uint32_t width, uint32_t height,
+                              const rt_adaptive_params *params, int flags, void *hip_stream);
+/* The pixel queue's order under a plane, as a masked render computes it before its launch: order_out
+   (n_tiles words) receives the entries of `base` (a tile order of n_tiles words; NULL: 0, 1, ...) whose
+   tile's word of `stop` (n_tiles words) is 0, in base's order, then n_tiles — the first index outside
+   the frame, which the kernel's queue rejects — in every remaining position; *live_out their number.
+   An entry of base that is no tile index counts as stopped.  The display stages' rules as above.  Null
+   stop or outputs, n_tiles 0 or above 2^28 - 1, an output overlapping an input or the other output:
+   RT_ERR_ARG. */
+int rt_tile_stop_order(rt_ctx *ctx, const uint32_t *base, const uint32_t *stop, uint32_t n_tiles, uint32_t *order_out,
+                       uint32_t *live_out, int flags);
+int rt_tile_stop_order_async(rt_ctx *ctx, const uint32_t *base, const uint32_t *stop, uint32_t n_tiles,
+                             uint32_t *order_out, uint32_t *live_out, int flags, void *hip_stream);
+/* rt_moments_accumulate under a plane, with the history lengths rt_variance needs.  A pixel of a live
+   tile (stop[t] == 0): exactly rt_moments_accumulate, and len_out[p] = n_cur.  A pixel of a stopped
+   tile was not traced (cur == prev there: the recovered "sample" would be its own mean): mom_out =
+   mom_in, and len_out[p] = (float)stop[t].  mom_in may be NULL only with n_cur == 1; a stopped tile's
+   mom_out is then left as it is.  len_out: W*H floats apart from every other buffer; the plane apart
+   from mom_out; otherwise rt_moments_accumulate's rules and errors. */
+int rt_moments_accumulate_tiles(rt_ctx *ctx, const float *prev_rgba, const float *cur_rgba, float n_cur,
+                                const float *mom_in, float *mom_out, const uint32_t *stop, float *len_out, uint32_t width,
+                                uint32_t height, int flags);
+int rt_moments_accumulate_tiles_async(rt_ctx *ctx, const float *prev_rgba, const float *cur_rgba, float n_cur,
+                                      const float *mom_in, float *mom_out, const uint32_t *stop, float *len_out,
+                                      uint32_t width, uint32_t height, int flags, void *hip_stream);
+/* Device time of the last stop rule (the stats' reset, both kernels) and of the last masked order kernel
+   (a masked render's, or rt_tile_stop_order's; HIP events of their own), ms; either pointer may be NULL
+   (not both).  RT_ERR_STATE when a stage asked for has not run.  rt_moments_accumulate_tiles' time is
+   rt_last_variance_ms' moments_ms. */
+int rt_last_adaptive_ms(const rt_ctx *ctx, float *select_ms, float *order_ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

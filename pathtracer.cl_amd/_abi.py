@@ -215,6 +215,16 @@ class RtNoiseStats(ctypes.Structure):
                 ("below", ctypes.c_uint32)]
 
 
+class RtAdaptiveParams(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_float), ("max_ratio", ctypes.c_float), ("min_frames", ctypes.c_uint32),
+                ("dilate", ctypes.c_uint32)]
+
+
+class RtAdaptiveStats(ctypes.Structure):
+    _fields_ = [("tiles", ctypes.c_uint32), ("active", ctypes.c_uint32), ("stopped_now", ctypes.c_uint32),
+                ("frames", ctypes.c_uint32)]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -316,6 +326,16 @@ SIGNATURES = {
     "rt_noise_meter": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtNoiseParams), _i32]),
     "rt_noise_meter_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtNoiseParams), _i32, _vp]),
     "rt_last_noise_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
+    # adaptive sampling on the tile map (csrc/rt_adaptive.hip)
+    "rt_set_tile_stop": (_i32, [_vp, _vp, _u32, _u32, _i32]),
+    "rt_adaptive_defaults": (_i32, [ctypes.POINTER(RtAdaptiveParams)]),
+    "rt_tile_stop_select": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, ctypes.POINTER(RtAdaptiveParams), _i32]),
+    "rt_tile_stop_select_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, ctypes.POINTER(RtAdaptiveParams), _i32, _vp]),
+    "rt_tile_stop_order": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _i32]),
+    "rt_tile_stop_order_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _i32, _vp]),
+    "rt_moments_accumulate_tiles": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _u32, _u32, _i32]),
+    "rt_moments_accumulate_tiles_async": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "rt_last_adaptive_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

@@ -104,7 +104,7 @@ static_assert((kCounterBytes + kWorkWords * sizeof(uint32_t)) % sizeof(unsigned 
 constexpr bool kLightCone = true;
 
 /* the display-side stages with a kernel time of their own (rt_display.cpp) */
-enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_METER, RT_ST_TONEMAP, RT_ST_WARP_SPH, RT_ST_NOISE, RT_ST_COUNT };
+enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_METER, RT_ST_TONEMAP, RT_ST_WARP_SPH, RT_ST_NOISE, RT_ST_STOP_SELECT, RT_ST_STOP_ORDER, RT_ST_COUNT };
 
 struct rt_ctx {
     int device = 0;
@@ -305,6 +305,15 @@ struct rt_ctx {
     DevBuf<float> d_dn_stage;   /* host buffers' staging */
     DevBuf<uint32_t> d_meter_hist; /* rt_meter_exposure without hist_out: the meter's RT_METER_BINS counts */
     DevBuf<uint32_t> d_noise_hist; /* rt_noise_meter without hist_out, likewise */
+    /* adaptive sampling (rt_adaptive.hip).  The stop plane of rt_set_tile_stop: null
+       (none set), the caller's device plane, or d_stop_own, the copy of a host plane; the frame it is
+       for.  While one is set a triangle render's queue takes d_stop_order, which k_order_stop writes
+       before every such launch from d_order (or the identity); d_order itself is never modified. */
+    const uint32_t *stop_plane = nullptr;
+    uint32_t stop_w = 0, stop_h = 0;
+    DevBuf<uint32_t> d_stop_own;
+    DevBuf<uint32_t> d_stop_order; /* n_tiles entries, then the live count */
+    DevBuf<uint32_t> d_stop_settled; /* rt_tile_stop_select's scratch plane */
     struct StageTime {
         Event e0, e1;
         bool have = false;

@@ -11,6 +11,7 @@
  *   the meter and the tone map to 8 bits                      rt_tonemap.hip    §4.15
  *   the features of moved spheres on the earlier ones         rt_motion.hip     §4.16
  *   the noise meter                                           rt_noise.hip      §4.17
+ *   the stop rule, the masked order, the masked moments       rt_adaptive.hip, rt_filter.hip   §4.18
  *
  * Every call runs through one driver (AuxCall), which also lays out the staging area of a call on
  * host buffers.
@@ -45,11 +46,11 @@ int aux_end(rt_ctx *c, hipStream_t st)
 }
 
 /* growing a display-side buffer: a pending call may still use it */
-int ensure_dev(rt_ctx *c, DevBuf<float> &buf, size_t floats)
+template <class T> int ensure_dev(rt_ctx *c, DevBuf<T> &buf, size_t n)
 {
-    if (floats <= buf.cap) return RT_OK;
+    if (n <= buf.cap) return RT_OK;
     if (c->aux_stream) HIPCHK(c, hipEventSynchronize(c->ev_aux));
-    HIPCHK(c, buf.reserve(floats));
+    HIPCHK(c, buf.reserve(n));
     return RT_OK;
 }
 
@@ -586,6 +587,55 @@ try {
     return finish_sync(c, rt_moments_accumulate_async(c, prev_rgba, cur_rgba, n_cur, mom_in, mom_out, W, H, flags, nullptr));
 } RT_CATCH(err_of(c))
 
+int rt_moments_accumulate_tiles_async(rt_ctx *c, const float *prev_rgba, const float *cur_rgba, float n_cur,
+                                      const float *mom_in, float *mom_out, const uint32_t *stop, float *len_out, uint32_t W,
+                                      uint32_t H, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_moments_accumulate_tiles: n_cur below 1 or NaN");
+    const bool first = n_cur == 1.0f;
+    if (!cur_rgba || !mom_out || !stop || !len_out || (!first && (!prev_rgba || !mom_in)))
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate_tiles: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_moments_accumulate_tiles: flags other than RT_OUT_DEVICE");
+    if (mom_out == prev_rgba || mom_out == cur_rgba)
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate_tiles: the output is an accumulation buffer");
+    const size_t px = (size_t)W * H, tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    /* len_out apart from everything else, the plane apart from the moments written */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } buf[] = {{prev_rgba, 4 * px * sizeof(float)}, {cur_rgba, 4 * px * sizeof(float)}, {mom_in, 4 * px * sizeof(float)},
+               {mom_out, 4 * px * sizeof(float)},   {stop, tiles * sizeof(uint32_t)}};
+    for (const auto &b : buf)
+        if (overlaps(len_out, px * sizeof(float), b.p, b.bytes))
+            return fail(c, RT_ERR_ARG, "rt_moments_accumulate_tiles: len_out overlaps another buffer");
+    if (overlaps(stop, tiles * sizeof(uint32_t), mom_out, 4 * px * sizeof(float)))
+        return fail(c, RT_ERR_ARG, "rt_moments_accumulate_tiles: the stop plane overlaps the output");
+    AuxCall x = {c, RT_ST_MOMENTS};
+    if (const int r = x.open(stream, flags)) return r;
+    /* staged: cur, prev, the moments (accumulated in place there; without mom_in the output's own
+       contents, which a stopped tile keeps), the plane's words, then the lengths */
+    const Plane pl[] = {{cur_rgba, nullptr, 4 * px},
+                        {first ? nullptr : prev_rgba, nullptr, 4 * px},
+                        {mom_in ? mom_in : mom_out, mom_out, 4 * px},
+                        {reinterpret_cast<const float *>(stop), nullptr, tiles},
+                        {nullptr, len_out, px}};
+    if (const int r = x.begin(pl, 5)) return r;
+    const float *din = mom_in || x.host ? x.at(2, mom_in) : nullptr;
+    const int e = rt_launch_moments_tiles(x.at(1, prev_rgba), x.at(0, cur_rgba), n_cur, din, x.at(2, mom_out), x.words(3, stop),
+                                          x.at(4, len_out), W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "masked moments kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_moments_accumulate_tiles(rt_ctx *c, const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in,
+                                float *mom_out, const uint32_t *stop, float *len_out, uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_moments_accumulate_tiles_async(c, prev_rgba, cur_rgba, n_cur, mom_in, mom_out, stop, len_out, W,
+                                                            H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
 int rt_variance_async(rt_ctx *c, const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat,
                       float *out_var, uint32_t W, uint32_t H, const rt_denoise_var_params *prm, int flags, void *stream)
 try {
@@ -814,6 +864,94 @@ try {
 int rt_last_noise_ms(const rt_ctx *c, float *ms)
 try {
     return last_ms(c, {{RT_ST_NOISE, ms}});
+} RT_CATCH(err_of(c))
+
+/* ---- adaptive sampling on the tile map (rt_set_tile_stop: rt_render.cpp) ---- */
+
+int rt_adaptive_defaults(rt_adaptive_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->threshold = 0.05f;
+    p->max_ratio = 4.0f;
+    p->min_frames = 16;
+    p->dilate = 1;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_tile_stop_select_async(rt_ctx *c, const float *tiles_mean_max, uint32_t *stop_io, uint32_t n_frames,
+                              rt_adaptive_stats *stats_out, uint32_t W, uint32_t H, const rt_adaptive_params *prm, int flags,
+                              void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!tiles_mean_max || !stop_io || !stats_out || !prm) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: flags other than RT_OUT_DEVICE");
+    if (n_frames == 0) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: n_frames is 0");
+    if (!(prm->threshold >= 0.0f)) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: threshold negative or NaN");
+    if (!(prm->max_ratio >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: max_ratio below 1 or NaN");
+    if (prm->dilate > 4) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: dilate above 4");
+    const size_t tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    const size_t tb = 2 * tiles * sizeof(float), sb = tiles * sizeof(uint32_t), qb = sizeof(rt_adaptive_stats);
+    if (overlaps(tiles_mean_max, tb, stop_io, sb) || overlaps(tiles_mean_max, tb, stats_out, qb) ||
+        overlaps(stop_io, sb, stats_out, qb))
+        return fail(c, RT_ERR_ARG, "rt_tile_stop_select: the buffers overlap");
+    /* one float product, formed here; +INFINITY switches the term off (0 x INFINITY would be a NaN) */
+    const float max_limit = prm->max_ratio == rt_inff() ? rt_inff() : prm->threshold * prm->max_ratio;
+    AuxCall x = {c, RT_ST_STOP_SELECT};
+    if (const int r = x.open(stream, flags)) return r;
+    if (const int r = ensure_dev(c, c->d_stop_settled, tiles)) return r;
+    /* staged: the tile pairs, the plane's words (updated in place there), then the stats' words */
+    constexpr size_t kStatWords = sizeof(rt_adaptive_stats) / sizeof(float);
+    const Plane pl[] = {{tiles_mean_max, nullptr, 2 * tiles},
+                        {reinterpret_cast<const float *>(stop_io), reinterpret_cast<float *>(stop_io), tiles},
+                        {nullptr, reinterpret_cast<float *>(stats_out), kStatWords}};
+    if (const int r = x.begin(pl, 3)) return r;
+    const int e = rt_launch_stop_select(x.at(0, tiles_mean_max), x.words(1, stop_io), c->d_stop_settled, W, H, n_frames,
+                                        n_frames >= prm->min_frames, prm->threshold, max_limit, prm->dilate,
+                                        x.words(2, stats_out), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "stop rule kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_tile_stop_select(rt_ctx *c, const float *tiles_mean_max, uint32_t *stop_io, uint32_t n_frames,
+                        rt_adaptive_stats *stats_out, uint32_t W, uint32_t H, const rt_adaptive_params *prm, int flags)
+try {
+    return finish_sync(c, rt_tile_stop_select_async(c, tiles_mean_max, stop_io, n_frames, stats_out, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_tile_stop_order_async(rt_ctx *c, const uint32_t *base, const uint32_t *stop, uint32_t n_tiles, uint32_t *order_out,
+                             uint32_t *live_out, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!stop || !order_out || !live_out) return fail(c, RT_ERR_ARG, "rt_tile_stop_order: null argument");
+    if (n_tiles == 0 || n_tiles >= (1u << 28)) return fail(c, RT_ERR_ARG, "rt_tile_stop_order: n_tiles is 0 or above 2^28 - 1");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tile_stop_order: flags other than RT_OUT_DEVICE");
+    const size_t nb = (size_t)n_tiles * sizeof(uint32_t);
+    if (overlaps(order_out, nb, base, nb) || overlaps(order_out, nb, stop, nb) || overlaps(order_out, nb, live_out, 4) ||
+        overlaps(live_out, 4, base, nb) || overlaps(live_out, 4, stop, nb))
+        return fail(c, RT_ERR_ARG, "rt_tile_stop_order: an output overlaps an input or the other output");
+    AuxCall x = {c, RT_ST_STOP_ORDER};
+    if (const int r = x.open(stream, flags)) return r;
+    const Plane pl[] = {{reinterpret_cast<const float *>(base), nullptr, base ? n_tiles : 0u},
+                        {reinterpret_cast<const float *>(stop), nullptr, n_tiles},
+                        {nullptr, reinterpret_cast<float *>(order_out), n_tiles},
+                        {nullptr, reinterpret_cast<float *>(live_out), 1}};
+    if (const int r = x.begin(pl, 4)) return r;
+    const int e = rt_launch_order_stop(base ? x.words(0, base) : nullptr, x.words(1, stop), n_tiles, x.words(2, order_out),
+                                       x.words(3, live_out), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "masked order kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_tile_stop_order(rt_ctx *c, const uint32_t *base, const uint32_t *stop, uint32_t n_tiles, uint32_t *order_out,
+                       uint32_t *live_out, int flags)
+try {
+    return finish_sync(c, rt_tile_stop_order_async(c, base, stop, n_tiles, order_out, live_out, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_adaptive_ms(const rt_ctx *c, float *select_ms, float *order_ms)
+try {
+    return last_ms(c, {{RT_ST_STOP_SELECT, select_ms}, {RT_ST_STOP_ORDER, order_ms}});
 } RT_CATCH(err_of(c))
 
 } /* extern "C" */

@@ -3,6 +3,8 @@
  *
  *   k_moments          per pixel: recover the frame's own sample from the accumulation buffer before
  *                      and after it, and keep the running mean of its luminance and of its square
+ *   k_moments_tiles    the same on the pixels of the live tiles of a stop plane, with the per-pixel
+ *                      history lengths; a stopped tile's pixels keep their moments
  *   k_variance         per pixel: the variance of the displayed (mean) luminance, from the moments
  *                      where the history is long enough, else from a 7 x 7 feature-weighted window
  *   k_atrous, k_atrous_lds<S>           one pass of the a-trous wavelet filter (Dammertz et al. 2010)
@@ -36,12 +38,10 @@ __device__ __forceinline__ float unmix(float prev, float cur, float n)
     return s > 0.0f ? s : 0.0f;
 }
 
-/* One lane per pixel; mom_out may be mom_in (each lane reads its pixel before it writes it). */
-__global__ __launch_bounds__(kPixelBlock) void k_moments(const float4 *prev, const float4 *cur, float n, float f,
-                                                 const float4 *mom_in, float4 *mom_out, uint32_t npx)
+/* pixel p's moments after a frame; mom_out may be mom_in (the pixel is read before it is written) */
+__device__ __forceinline__ void moments_pixel(const float4 *prev, const float4 *cur, float n, float f, const float4 *mom_in,
+                                              float4 *mom_out, uint32_t p)
 {
-    const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
-    if (p >= npx) return;
     const float4 c = cur[p];
     if (n == 1.0f) { /* the first frame of a view is its own sample; no history is read */
         const float L = lum3(c.x > 0.0f ? c.x : 0.0f, c.y > 0.0f ? c.y : 0.0f, c.z > 0.0f ? c.z : 0.0f);
@@ -51,6 +51,36 @@ __global__ __launch_bounds__(kPixelBlock) void k_moments(const float4 *prev, con
     const float4 o = prev[p], m = mom_in[p];
     const float L = lum3(unmix(o.x, c.x, n), unmix(o.y, c.y, n), unmix(o.z, c.z, n));
     mom_out[p] = make_float4(m.x + (L - m.x) * f, m.y + (L * L - m.y) * f, 0.0f, 0.0f);
+}
+
+/* One lane per pixel. */
+__global__ __launch_bounds__(kPixelBlock) void k_moments(const float4 *prev, const float4 *cur, float n, float f,
+                                                 const float4 *mom_in, float4 *mom_out, uint32_t npx)
+{
+    const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
+    if (p >= npx) return;
+    moments_pixel(prev, cur, n, f, mom_in, mom_out, p);
+}
+
+/* The same under a stop plane: a stopped tile's pixels were not traced, so cur ==
+   prev there and the recovered "sample" would be the pixel's own mean; they keep their moments, and
+   their history length is the frame count their tile stopped at. */
+__global__ __launch_bounds__(kPixelBlock) void k_moments_tiles(const float4 *prev, const float4 *cur, float n, float f,
+                                                               const float4 *mom_in, float4 *mom_out,
+                                                               const uint32_t *__restrict__ stop, float *__restrict__ len_out,
+                                                               uint32_t W, uint32_t tw, uint32_t npx)
+{
+    const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
+    if (p >= npx) return;
+    const uint32_t y = p / W, x = p - y * W;
+    const uint32_t s = stop[(y >> 3) * tw + (x >> 3)];
+    if (s) {
+        if (mom_in && mom_out != mom_in) mom_out[p] = mom_in[p];
+        len_out[p] = (float)s;
+        return;
+    }
+    moments_pixel(prev, cur, n, f, mom_in, mom_out, p);
+    len_out[p] = n;
 }
 
 /* The 49 taps of the spatial estimate are gathered from global memory (only pixels with a short
@@ -286,6 +316,17 @@ int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur
     hipLaunchKernelGGL(k_moments, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(prev_rgba), reinterpret_cast<const float4 *>(cur_rgba), n_cur,
                        1.0f / n_cur, reinterpret_cast<const float4 *>(mom_in), reinterpret_cast<float4 *>(mom_out), npx);
+    return (int)hipGetLastError();
+}
+
+int rt_launch_moments_tiles(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
+                            const uint32_t *stop, float *len_out, uint32_t W, uint32_t H, void *stream)
+{
+    const uint32_t npx = W * H; /* < 2^28 (the host's frame check) */
+    hipLaunchKernelGGL(k_moments_tiles, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4 *>(prev_rgba), reinterpret_cast<const float4 *>(cur_rgba), n_cur,
+                       1.0f / n_cur, reinterpret_cast<const float4 *>(mom_in), reinterpret_cast<float4 *>(mom_out), stop,
+                       len_out, W, (W + 7u) / 8u, npx);
     return (int)hipGetLastError();
 }
 

@@ -466,6 +466,12 @@ int rt_launch_warp_features_spheres(const float *cur_feat, const rt_sphere *sphe
    moments' output may be their input; n_cur == 1 reads neither prev_rgba nor mom_in. */
 int rt_launch_moments(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
                       uint32_t W, uint32_t H, void *stream);
+/* rt_launch_moments on the pixels of the 8x8 tiles whose word of `stop` (ceil(W/8) ceil(H/8) words) is
+   0, with len_out = n_cur there; a pixel of any other tile keeps its moments (mom_in copied where
+   mom_out is another buffer; a null mom_in: mom_out left alone) and gets len_out = (float)stop[tile]
+   (DESIGN.md §4.18). */
+int rt_launch_moments_tiles(const float *prev_rgba, const float *cur_rgba, float n_cur, const float *mom_in, float *mom_out,
+                            const uint32_t *stop, float *len_out, uint32_t W, uint32_t H, void *stream);
 int rt_launch_variance(const float *disp_rgba, const float *mom_rgba, const float *len, const float *feat, float *out_var,
                        uint32_t W, uint32_t H, float isn, float isp, float min_len, void *stream);
 /* One a-trous pass at tap distance `step` with the inverse variances of its normal and plane terms.
@@ -505,5 +511,17 @@ int rt_launch_noise_hist(const float *rgba, const float *var, uint32_t W, uint32
                          float *tiles, void *stream);
 int rt_launch_noise_stat(const uint32_t *hist, uint32_t W, uint32_t H, float percentile, float threshold,
                          rt_noise_stats *stats, void *stream);
+/* -- rt_adaptive.hip -- */
+/* Adaptive sampling: device buffers.  The masked order: `out` (n_tiles words, apart
+   from both inputs) receives the entries of `base` (n_tiles words; NULL: 0, 1, ...) whose tile's word
+   of `stop` is 0, in base's order, then n_tiles in every remaining position; *live their number.  An
+   entry of base that is no tile index counts as stopped. */
+int rt_launch_order_stop(const uint32_t *base, const uint32_t *stop, uint32_t n_tiles, uint32_t *out, uint32_t *live,
+                         void *stream);
+/* The stop rule: tiles = (mean, max) pairs, stop updated in place, settled = n_tiles words of scratch,
+   stats = the four words of rt_adaptive_stats (zeroed on the stream first).  quiet_ok: n_frames >=
+   min_frames; max_limit: the product threshold max_ratio, or +INFINITY. */
+int rt_launch_stop_select(const float *tiles, uint32_t *stop, uint32_t *settled, uint32_t W, uint32_t H, uint32_t n_frames,
+                          int quiet_ok, float threshold, float max_limit, uint32_t dilate, uint32_t *stats, void *stream);
 
 #endif /* RT_INTERNAL_H */

@@ -513,6 +513,7 @@ struct Frame {
     float *dout = nullptr; /* the device framebuffer: the caller's, or the staging area */
     uint32_t stripe = 1, nr = 1, rk = 0, map_key = 0;
     const uint32_t *smap = nullptr;
+    bool masked = false; /* under a stop plane (rt_set_tile_stop): whole pixels of its live tiles only */
 };
 
 /* The triangle launch's plan. */
@@ -536,6 +537,11 @@ int render_args(rt_ctx *c, const Frame &f)
                     "a tile need the seed-row halo (rt_pack_seed_rows / rt_unpack_seed_rows, flag RT_SEEDS_HALO)");
     if (f.kernel == RT_KERNEL_TRIS && c->n_tris == 0) return fail(c, RT_ERR_NO_MESH, "no mesh set");
     if (f.kernel != RT_KERNEL_TRIS && c->spheres.empty()) return fail(c, RT_ERR_NO_SCENE, "no spheres set");
+    if (c->stop_plane) { /* never a silent full render */
+        if (f.kernel != RT_KERNEL_TRIS) return fail(c, RT_ERR_ARG, "a tile stop plane is set: it masks raytrace_tris renders only");
+        if (tile) return fail(c, RT_ERR_ARG, "a tile stop plane is set: it masks whole frames, not tiles");
+        if (f.W != c->stop_w || f.H != c->stop_h) return fail(c, RT_ERR_ARG, "a tile stop plane is set for another frame size");
+    }
     return RT_OK;
 }
 
@@ -744,6 +750,7 @@ int plan_split(rt_ctx *c, const Frame &f, RtTriLaunch &a, TriPlan &p)
 {
     const uint32_t W = f.W, hl = f.hl;
     a.split_chunks = 0;
+    if (f.masked) return RT_OK; /* always whole pixels */
     if (!(a.tile_order && p.trav == RT_TRAV_BVH4Q && split_wanted(c, (uint64_t)W * hl, (uint64_t)p.blocks * RT_BLOCK)))
         return RT_OK;
     /* chunks of about spp / 16 samples; seeds stored every quarter chunk, so that the long
@@ -828,7 +835,8 @@ int record_costs(rt_ctx *c, const Frame &f, RtTriLaunch &a, TriPlan &p)
     a.pixel_iter = nullptr;
     /* (frames of >= 16 samples per pixel: a 1-spp pixel's cost is one random path, and the bunny
        class measured 0.436 -> 0.459 ms re-sorted by it, profiles/r05aj) */
-    if (a.tile_order && !c->order_measured && c->sample_rate * c->sample_rate >= 16u) {
+    /* (not from a masked frame: its stopped tiles' pixels would record nothing) */
+    if (!f.masked && a.tile_order && !c->order_measured && c->sample_rate * c->sample_rate >= 16u) {
         const uint32_t nch = a.split_chunks ? a.split_chunks : 1u;
         const size_t n_i = (size_t)f.W * f.hl * nch;
         HIPCHK(c, c->d_pixel_iter.reserve(2 * n_i));
@@ -1002,6 +1010,17 @@ int launch_tris(rt_ctx *c, const Frame &f, RtTriLaunch &a, TriPlan &p, int *e_ou
         const int rp = pilot_order(c, a, trav, p.blocks, st);
         if (rp != RT_OK) return rp;
     }
+    if (f.masked && !e) {
+        /* the queue's order without the stopped tiles, in a buffer of its own (the plane is read here,
+           on the render's stream: a borrowed one may have changed since the last render) */
+        const uint32_t n_tiles = ((f.W + 7u) / 8u) * ((f.hl + 7u) / 8u);
+        rt_ctx::StageTime &t = c->stage_time[RT_ST_STOP_ORDER];
+        HIPCHK(c, hipEventRecord(t.e0, st));
+        e = rt_launch_order_stop(a.tile_order, c->stop_plane, n_tiles, c->d_stop_order, c->d_stop_order + n_tiles, st);
+        HIPCHK(c, hipEventRecord(t.e1, st));
+        t.have = true;
+        a.tile_order = c->d_stop_order;
+    }
     HIPCHK(c, hipEventRecord(c->evm, st));
     if (!e && p.lists && getenv("RT_LIST_STATS"))
         if (const int r = list_stats(c, f, p)) return r;
@@ -1077,6 +1096,12 @@ int render_tris(rt_ctx *c, const Frame &f, int *e_out)
     const char *stats_path = nullptr;
     if (const int r = pixel_stats_begin(c, f, a, stats, &stats_path)) return r;
     if (const int r = plan_lists(c, f, a, p)) return r;
+    if (f.masked) {
+        const size_t n_tiles = (size_t)((f.W + 7u) / 8u) * ((f.hl + 7u) / 8u);
+        HIPCHK(c, c->d_stop_order.reserve(n_tiles + 1));
+        HIPCHK(c, c->stage_time[RT_ST_STOP_ORDER].e0.create());
+        HIPCHK(c, c->stage_time[RT_ST_STOP_ORDER].e1.create());
+    }
     if (const int r = launch_tris(c, f, a, p, e_out)) return r;
     tris_info(c, a, p);
     return pixel_stats_dump(c, f, stats, stats_path);
@@ -1261,6 +1286,7 @@ try {
     if (W == 0 || H == 0) return RT_OK; /* RayTracerCL.cpp:219-220 */
     Frame f = {out, W, H, prog, kernel, tile, flags, nullptr};
     if (const int r = render_args(c, f)) return r;
+    f.masked = c->stop_plane != nullptr;
     HIPCHK(c, hipSetDevice(c->device));
     f.st = stream ? (hipStream_t)stream : c->stream;
     if (const int r = refresh_view(c, W, H)) return r;
@@ -1272,6 +1298,34 @@ try {
     if (const int r = kernel == RT_KERNEL_TRIS ? render_tris(c, f, &e) : render_spheres(c, f, &e)) return r;
     if (e) return hip_fail(c, (hipError_t)e, "kernel launch");
     return hand_back(c, f);
+} RT_CATCH(err_of(c))
+
+int rt_set_tile_stop(rt_ctx *c, const uint32_t *stop, uint32_t W, uint32_t H, int flags)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_set_tile_stop: flags other than RT_OUT_DEVICE");
+    if (!stop) { /* cleared: the renders are whole frames again */
+        c->stop_plane = nullptr;
+        c->stop_w = c->stop_h = 0;
+        return RT_OK;
+    }
+    if (!W || !H || (uint64_t)W * H >= (1ull << 28)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & RT_OUT_DEVICE) {
+        c->stop_plane = stop; /* borrowed: read on each render's stream */
+    } else {
+        HIPCHK(c, hipSetDevice(c->device));
+        /* a render in flight may still read the last copy */
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->sync_stream && c->sync_stream != c->stream) HIPCHK(c, hipStreamSynchronize(c->sync_stream));
+        const size_t n_tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+        c->stop_plane = nullptr;
+        HIPCHK(c, c->d_stop_own.reserve(n_tiles));
+        HIPCHK(c, hipMemcpy(c->d_stop_own, stop, n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->stop_plane = c->d_stop_own;
+    }
+    c->stop_w = W;
+    c->stop_h = H;
+    return RT_OK;
 } RT_CATCH(err_of(c))
 
 int rt_synchronize(rt_ctx *c)

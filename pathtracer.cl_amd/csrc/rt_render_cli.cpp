@@ -52,6 +52,11 @@
  *              rt_noise_defaults'); the event lines gain "converged") [--converge-percentile Q] [--converge-min-frames N]
  *              [--noise-log FILE] (per traced display one line: the level's bits in hex, counted, skipped, below,
  *              converged 0 / 1) [--noise-map-out FILE] (the tile planes of the traced displays, appended as float pairs)
+ *             [--adaptive [THRESHOLD]]   (with --converge and --mesh / --ply, without --temporal: the view stops tracing
+ *              the 8x8 tiles the noise meter calls quiet (ProgressiveViewHIP::setAdaptive: a tile's mean error at or
+ *              under THRESHOLD, default rt_adaptive_defaults'); the event lines gain "tiles_active")
+ *              [--adaptive-max-ratio R] [--adaptive-min-frames N] [--adaptive-dilate D]
+ *              [--stop-map-out FILE] (the stop planes after the traced displays, appended as words)
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -155,7 +160,8 @@ int usage()
                          "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--sphere-carry [MAXHIST]] (--events o:I:DX:DY:DZ[:DR] moves sphere I) [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
-                         "[--noise-log f] [--noise-map-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
+                         "[--noise-log f] [--noise-map-out f] [--adaptive [THRESHOLD]] [--adaptive-max-ratio R] [--adaptive-min-frames N] "
+                         "[--adaptive-dilate D] [--stop-map-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
 
@@ -227,6 +233,9 @@ int main(int argc, char **argv)
     rt_noise_params noise_params = RayTracerHIP::noiseDefaults();
     unsigned converge_min_frames = 8;
     std::string noise_log, noise_map_out;
+    bool adaptive = false;
+    rt_adaptive_params adaptive_params = RayTracerHIP::adaptiveDefaults();
+    std::string stop_map_out;
     float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
@@ -293,8 +302,17 @@ int main(int argc, char **argv)
             if ((v = optional_number(argc, argv, i))) noise_params.threshold = (float)std::atof(v);
             continue;
         }
+        if (a == "--adaptive") { /* an optional threshold follows */
+            adaptive = true;
+            if ((v = optional_number(argc, argv, i))) adaptive_params.threshold = (float)std::atof(v);
+            continue;
+        }
         if (!(v = next())) return usage();
         if (a == "--scene") scene = v;
+        else if (a == "--adaptive-max-ratio") adaptive_params.max_ratio = (float)std::atof(v); /* ("inf": the term is off) */
+        else if (a == "--adaptive-min-frames") adaptive_params.min_frames = (unsigned)std::atoi(v);
+        else if (a == "--adaptive-dilate") adaptive_params.dilate = (unsigned)std::atoi(v);
+        else if (a == "--stop-map-out") stop_map_out = v;
         else if (a == "--converge-percentile") noise_params.percentile = (float)std::atof(v);
         else if (a == "--converge-min-frames") converge_min_frames = (unsigned)std::atoi(v);
         else if (a == "--noise-log") noise_log = v;
@@ -381,6 +399,22 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --noise-log / --noise-map-out need --converge (nothing is metered without it)\n");
         return 2;
     }
+    if (adaptive && !converge) {
+        std::fprintf(stderr, "rt_render: --adaptive needs --converge (it stops tiles by the noise meter's map)\n");
+        return 2;
+    }
+    if (adaptive && temporal) {
+        std::fprintf(stderr, "rt_render: --adaptive does not go with --temporal (the merged history has no per-tile frame count)\n");
+        return 2;
+    }
+    if (adaptive && n_tris == 0 && ply_path.empty()) {
+        std::fprintf(stderr, "rt_render: --adaptive needs --mesh or --ply (the sphere kernels' seed rows shift with the progression)\n");
+        return 2;
+    }
+    if (!adaptive && !stop_map_out.empty()) {
+        std::fprintf(stderr, "rt_render: --stop-map-out needs --adaptive (there is no stop plane without it)\n");
+        return 2;
+    }
     try {
         RayTracerHIP rt(device);
         add_scene(rt, ply);
@@ -419,6 +453,8 @@ int main(int argc, char **argv)
             if (tonemap) view.setToneMap(true, tone_params, auto_exposure, meter_params);
             if (converge) view.setConverge(true, noise_params, converge_min_frames);
             if (!noise_map_out.empty()) view.setNoiseMapReadback(true);
+            if (adaptive) view.setAdaptive(true, adaptive_params);
+            if (!stop_map_out.empty()) view.setStopMapReadback(true);
             rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
             SphereOffsets sphere_offsets{};            /* the o events so far */
             std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
@@ -444,6 +480,8 @@ int main(int argc, char **argv)
             FILE *fn = noise_log.empty() ? nullptr : std::fopen(noise_log.c_str(), "w");
             FILE *fm = noise_map_out.empty() ? nullptr : std::fopen(noise_map_out.c_str(), "wb");
             if ((!noise_log.empty() && !fn) || (!noise_map_out.empty() && !fm)) return 1;
+            FILE *fs = stop_map_out.empty() ? nullptr : std::fopen(stop_map_out.c_str(), "wb");
+            if (!stop_map_out.empty() && !fs) return 1;
             size_t pos = 0;
             while (pos <= events.size()) {
                 const size_t end = std::min(events.find(',', pos), events.size());
@@ -471,6 +509,7 @@ int main(int argc, char **argv)
                         std::fprintf(fn, "%08x %u %u %u %d\n", u, ns.counted, ns.skipped, ns.below, view.converged() ? 1 : 0);
                     }
                     if (traced && fm && !append(fm, view.noiseMap())) return 1;
+                    if (traced && fs && std::fwrite(view.stopMap().data(), 4, view.stopMap().size(), fs) != view.stopMap().size()) return 1;
                     if (traced && ff) {
                         std::vector<float> ft((size_t)view.width() * view.height() * 8);
                         rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
@@ -516,6 +555,7 @@ int main(int argc, char **argv)
                             view.azimuth(), view.elevation(), view.width(), view.height());
                 if (mesh_update) std::printf(", \"mesh_update\": \"%s\"", mesh_update);
                 if (converge) std::printf(", \"converged\": %s", view.converged() ? "true" : "false");
+                if (adaptive) std::printf(", \"tiles_active\": %u", view.adaptiveStats().active);
                 std::printf("}\n");
             }
             if (fo) std::fclose(fo);
@@ -525,6 +565,7 @@ int main(int argc, char **argv)
             if (fe) std::fclose(fe);
             if (fn) std::fclose(fn);
             if (fm) std::fclose(fm);
+            if (fs) std::fclose(fs);
             if (!ppm.empty() && (view.pixels8().empty() || !write_ppm(ppm, view.pixels8(), view.width(), view.height()))) return 1;
             std::printf("{\"progression\": %u, \"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, "
                         "\"height\": %u}\n",

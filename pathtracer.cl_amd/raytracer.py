@@ -606,6 +606,94 @@ class RayTracer:
         """Device time of the last noise meter, ms."""
         return self._last_ms("rt_last_noise_ms")
 
+    # ---- adaptive sampling on the tile map (pathtracer_rt.h, DESIGN.md §4.18) ----
+    @staticmethod
+    def _tiles(width: int, height: int) -> int:
+        return ((int(width) + 7) // 8) * ((int(height) + 7) // 8)
+
+    def adaptiveDefaults(self) -> dict:
+        return self._defaults(_abi.RtAdaptiveParams, "rt_adaptive_defaults")
+
+    def setTileStop(self, stop, width: int = 0, height: int = 0) -> None:
+        """The stop plane that masks the raytrace_tris renders of `width` x `height` from now on: one
+        uint32 / int32 word per 8x8 tile, 0 = rendered, anything else = left alone (framebuffer and
+        seeds).  A numpy array is copied now; a torch CUDA tensor is borrowed, read at every render, and
+        must stay alive until the plane is cleared (`stop` None) or replaced."""
+        if stop is None:
+            self._keep_stop = None
+            self._check(self._lib.rt_set_tile_stop(self._h, None, 0, 0, 0), "rt_set_tile_stop")
+            return
+        flags = self._buffer(stop, self._tiles(width, height), "stop plane", self._WORDS)
+        self._check(self._lib.rt_set_tile_stop(self._h, _abi.ptr(stop), int(width), int(height), flags), "rt_set_tile_stop")
+        self._keep_stop = stop if flags else None
+
+    def tileStopSelect(self, tiles, stop, n_frames: int, width: int, height: int, threshold: float | None = None,
+                       max_ratio: float | None = None, min_frames: int | None = None, dilate: int | None = None,
+                       stats=None, stream=None, sync: bool = True):
+        """The stop rule on noiseMeter's tile map `tiles` ((mean, max) pairs): `stop` (a word per tile,
+        0 = live, k = stopped after k frames) is updated in place — a live tile stops, with `n_frames`,
+        when every tile within `dilate` tiles of it is stopped already or quiet (n_frames >= min_frames,
+        mean <= threshold, max <= threshold max_ratio).  None for a parameter: the library's default.
+        Returns the stats as a dict (`tiles`, `active`, `stopped_now`, `frames`).  All numpy arrays or all
+        torch CUDA tensors; `stats` (4 words of the buffers' kind) receives the struct's words as well;
+        with sync=False it must be given, nothing is read back and None is returned."""
+        n = self._tiles(width, height)
+        flags = self._same_kind("tileStopSelect", [(tiles, 2 * n, "tile map"), (stop, n, "stop plane", self._WORDS),
+                                                   (stats, 4, "stats", self._WORDS)])
+        if stats is None:
+            if not sync:
+                raise ValueError("tileStopSelect: sync=False needs a stats buffer")
+            if flags:
+                import torch
+
+                stats = torch.zeros(4, dtype=torch.int32, device=tiles.device)
+            else:
+                stats = np.zeros(4, np.uint32)
+        d = self.adaptiveDefaults()
+        for k, v in (("threshold", threshold), ("max_ratio", max_ratio), ("min_frames", min_frames), ("dilate", dilate)):
+            if v is not None:
+                d[k] = v
+        prm = _abi.RtAdaptiveParams(float(d["threshold"]), float(d["max_ratio"]), int(d["min_frames"]), int(d["dilate"]))
+        args = (self._h, _abi.ptr(tiles), _abi.ptr(stop), int(n_frames), _abi.ptr(stats), int(width), int(height),
+                ctypes.byref(prm), flags)
+        self._aux_call("rt_tile_stop_select", args, stream, sync)
+        if not sync:
+            return None
+        w = stats if isinstance(stats, np.ndarray) else stats.cpu().numpy()
+        w = np.ascontiguousarray(w).view(np.uint32)
+        return dict(tiles=int(w[0]), active=int(w[1]), stopped_now=int(w[2]), frames=int(w[3]))
+
+    def tileStopOrder(self, base, stop, order_out, live_out, stream=None, sync: bool = True) -> None:
+        """The pixel queue's order under the plane `stop` (n words), as a masked render computes it:
+        `order_out` (n words) = the entries of the tile order `base` (n words; None: 0, 1, ...) whose tile
+        is live, in base's order, then n in every remaining position; `live_out` (one word) their number.
+        All numpy arrays or all torch CUDA tensors."""
+        n = stop.size if isinstance(stop, np.ndarray) else stop.numel()
+        flags = self._same_kind("tileStopOrder", [(base, n, "base order", self._WORDS), (stop, n, "stop plane", self._WORDS),
+                                                  (order_out, n, "destination order", self._WORDS),
+                                                  (live_out, 1, "live count", self._WORDS)])
+        args = (self._h, _abi.ptr(base), _abi.ptr(stop), int(n), _abi.ptr(order_out), _abi.ptr(live_out), flags)
+        self._aux_call("rt_tile_stop_order", args, stream, sync)
+
+    def momentsAccumulateTiles(self, prev_rgba, cur_rgba, n_cur: float, mom_in, mom_out, stop, len_out, width: int,
+                               height: int, stream=None, sync: bool = True) -> None:
+        """momentsAccumulate under the plane `stop` (a word per 8x8 tile): the pixels of live tiles as
+        momentsAccumulate, with `len_out` (W*H floats) = n_cur; the pixels of stopped tiles keep their
+        moments and get the frame count their tile stopped at — `variance`'s `length`.  All numpy arrays
+        or all torch CUDA tensors."""
+        px = int(width) * int(height)
+        flags = self._same_kind("momentsAccumulateTiles", [
+            (prev_rgba, px * 4, "previous accumulation"), (cur_rgba, px * 4, "current accumulation"),
+            (mom_in, px * 4, "moments"), (mom_out, px * 4, "destination moments"),
+            (stop, self._tiles(width, height), "stop plane", self._WORDS), (len_out, px, "destination history lengths")])
+        args = (self._h, _abi.ptr(prev_rgba), _abi.ptr(cur_rgba), float(n_cur), _abi.ptr(mom_in), _abi.ptr(mom_out),
+                _abi.ptr(stop), _abi.ptr(len_out), int(width), int(height), flags)
+        self._aux_call("rt_moments_accumulate_tiles", args, stream, sync)
+
+    def lastAdaptiveMs(self, order: bool = False) -> float:
+        """Device time of the last stop rule, or (order=True) of the last masked order kernel, ms."""
+        return self._last_ms("rt_last_adaptive_ms", 2, 1 if order else 0)
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
