@@ -114,6 +114,17 @@
  *                    updateMesh and sceneChanged().  The view is converged() by setConverge's rule, or when no
  *                    tile is live.  In any other view (adaptiveInEffect() false) and off (the default), nothing
  *                    changes and no plane is set.
+ *   setSampleBudget(on, params)  (no counterpart in the reference) where setAdaptive is in effect: give the noisy tiles
+ *                    extra passes per display.  It takes effect at the next display at which the
+ *                    frame count starts afresh (after a (re)allocation, a key, a drag, restart(), updateMesh,
+ *                    sceneChanged()), where the view zeroes a count plane beside the stop plane.  A display of
+ *                    progression 0 is rendered as ever; every later one renders each pass at progression 0 into a
+ *                    scratch frame under the pass's mask (rt_tile_pass_mask) and folds it into the accumulation
+ *                    buffer with the weight the tile's own count gives (rt_fold_tiles), which also keeps the
+ *                    moments and the history lengths; after the stop rule rt_tile_budget sets every tile's passes
+ *                    for the next display from the same tile map.  With max_passes 1 every byte displayed is the
+ *                    one setAdaptive alone displays.  Until it takes effect, where setAdaptive is not in effect
+ *                    and off (the default), every byte and every call is what it was.
  *   setFloatReadback(on)  with setToneMap: off, display() reads back only the 8-bit frame (a quarter of
  *                    the bytes) and pixels() keeps its last contents — those of the last display with the
  *                    readback on, zeros before any; rawPixels() still fetches the accumulation buffer.  On
@@ -143,7 +154,7 @@ public:
     }
     ~ProgressiveViewHIP()
     {
-        if (planeSet_) rt_set_tile_stop(rt_.handle(), nullptr, 0, 0, 0); /* the tracer outlives the view's plane */
+        if (plane_) rt_set_tile_stop(rt_.handle(), nullptr, 0, 0, 0); /* the tracer outlives the view's plane */
     }
     ProgressiveViewHIP(const ProgressiveViewHIP &) = delete;
     ProgressiveViewHIP &operator=(const ProgressiveViewHIP &) = delete;
@@ -352,6 +363,22 @@ public:
     void setStopMapReadback(bool on) { stopMapReadback_ = on; }
     const std::vector<uint32_t> &stopMap() const { return stopMap_; }
 
+    /* (no counterpart in the reference) per-tile sample counts: see the file comment.  In effect
+       only where setAdaptive is, and from the next display at which the frame count starts afresh. */
+    void setSampleBudget(bool on, const rt_budget_params &params = RayTracerHIP::budgetDefaults())
+    {
+        budget_ = on;
+        budgetParams_ = params;
+    }
+    /* whether the last traced display ran (or, at progression 0, began) the pass loop */
+    bool sampleBudgetInEffect() const { return budgetActive_; }
+    /* the budget rule's figures after the last traced display that ran it (zeros before one): the passes of the next */
+    const rt_budget_stats &budgetStats() const { return budgetStats_; }
+    /* With setSampleBudget in effect: also read the count plane back at every traced display into sampleCounts():
+       ceil(W/8) ceil(H/8) words, the frames folded into each tile's mean since progression 0's. */
+    void setSampleCountReadback(bool on) { countReadback_ = on; }
+    const std::vector<uint32_t> &sampleCounts() const { return sampleCounts_; }
+
     /* (no counterpart in the reference) the tone-mapped 8-bit display output */
     void setToneMap(bool on, const rt_tonemap_params &params = RayTracerHIP::toneMapDefaults(), bool autoExposure = true,
                     const rt_meter_params &meter = RayTracerHIP::meterDefaults())
@@ -469,6 +496,9 @@ private:
         /* setAdaptive: the stop plane (a word per tile) and the stop rule's stats (four words); the per-pixel
            history lengths are in `len` */
         DeviceFloats stop, adaptStats;
+        /* setSampleBudget: the frame a pass is rendered into, the count, passes and mask planes (a word per tile)
+           and the budget rule's stats */
+        DeviceFloats sample, count, passes, mask, budgetStats;
     };
     /* setVarianceGuided or setConverge: the view keeps the accumulation copy, the moments and the variance plane */
     bool momentsWanted() const { return varGuided_ || converge_; }
@@ -493,6 +523,9 @@ private:
         noiseMap_.clear();
         noiseStats_ = rt_noise_stats{};
         adaptiveStats_ = rt_adaptive_stats{};
+        budgetStats_ = rt_budget_stats{};
+        budgetActive_ = haveBudget_ = false;
+        sampleCounts_.clear();
         stopMap_.clear();
         stopReset_ = true;
         converged_ = false;
@@ -636,8 +669,14 @@ private:
     /* setAdaptive: the tracer's renders are whole frames again */
     void clearPlane()
     {
-        if (planeSet_) rt_.setTileStop(nullptr);
-        planeSet_ = false;
+        if (plane_) rt_.setTileStop(nullptr);
+        plane_ = nullptr;
+    }
+    /* the plane the tracer borrows: the stop plane, or in the pass loop the mask of the pass */
+    void borrowPlane(const float *plane)
+    {
+        if (plane_ != plane) rt_.setTileStop(reinterpret_cast<const uint32_t *>(plane), width_, height_, true);
+        plane_ = plane;
     }
     /* setAdaptive in effect: the view's plane, zeroed where the accumulation starts afresh, masks the renders */
     void maskRenders()
@@ -645,11 +684,52 @@ private:
         Buffers &b = *buf_;
         b.stop.need(noiseTileCount(), "stop plane");
         b.adaptStats.need(sizeof(rt_adaptive_stats) / sizeof(float), "stop rule stats");
+        if (budgetActive_) {
+            b.sample.need((size_t)width_ * height_ * 4, "sample frame");
+            b.count.need(noiseTileCount(), "count plane");
+            b.passes.need(noiseTileCount(), "passes plane");
+            b.mask.need(noiseTileCount(), "pass mask");
+            b.budgetStats.need(sizeof(rt_budget_stats) / sizeof(float), "budget stats");
+        }
+        /* (the counts start with the stop plane; until a budget says otherwise every tile has one pass) */
+        if (stopReset_ && budgetActive_ &&
+            (hipMemset(b.count.p, 0, noiseTileCount() * sizeof(uint32_t)) != hipSuccess ||
+             hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b.passes.p), 1, noiseTileCount()) != hipSuccess))
+            throw std::runtime_error("ProgressiveViewHIP: count plane reset failed");
+        if (stopReset_) {
+            budgetStats_ = rt_budget_stats{};
+            haveBudget_ = false;
+        }
         if (stopReset_ && (hipMemset(b.stop.p, 0, noiseTileCount() * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
             throw std::runtime_error("ProgressiveViewHIP: stop plane reset failed");
         stopReset_ = false;
-        if (!planeSet_) rt_.setTileStop(reinterpret_cast<const uint32_t *>(b.stop.p), width_, height_, true);
-        planeSet_ = true;
+        borrowPlane(b.stop.p);
+    }
+    /* setSampleBudget in effect, after progression 0: every pass of this display — its mask, a masked render at
+       progression 0 into the scratch frame (which overwrites the live tiles' pixels with the frame's own sample), and
+       the fold of those tiles into the accumulation buffer by their own counts, with the moments and the lengths.
+       All passes but the last are enqueued without a wait. */
+    void tracePasses()
+    {
+        Buffers &b = *buf_;
+        const size_t px = (size_t)width_ * height_;
+        b.mom.need(4 * px, "moments buffer");
+        b.len.need(px, "history length buffer");
+        const uint32_t *stop = reinterpret_cast<const uint32_t *>(b.stop.p), *passes = reinterpret_cast<const uint32_t *>(b.passes.p);
+        const uint32_t rounds = haveBudget_ ? budgetStats_.rounds : 1u;
+        borrowPlane(b.mask.p);
+        rt_.flushScene();
+        for (uint32_t r = 0; r < rounds; ++r) {
+            rt_.tilePassMask(stop, passes, r, reinterpret_cast<uint32_t *>(b.mask.p), width_, height_, true, /*sync=*/false);
+            if (r + 1 < rounds) {
+                if (rt_render_async(rt_.handle(), b.sample.p, width_, height_, 0, kernel_, nullptr, RT_OUT_DEVICE, nullptr) != RT_OK)
+                    throw std::runtime_error(std::string("ProgressiveViewHIP: pass render failed: ") + rt_last_error(rt_.handle()));
+            } else
+                rt_.rayTrace(b.sample.p, width_, height_, 0, kernel_, true);
+            rt_.foldTiles(b.sample.p, b.dev.p, reinterpret_cast<uint32_t *>(b.count.p), passes, r, b.mom.p, b.mom.p, b.len.p, width_,
+                          height_, true, /*sync=*/false);
+        }
+        borrowPlane(b.stop.p);
     }
     /* One traced display, whatever is switched on: render, then compose what is shown from the
        accumulation buffer, which every stage only reads. */
@@ -659,14 +739,24 @@ private:
         const size_t px = (size_t)width_ * height_;
         const float n = (float)(progression_ > 1 ? progression_ : 1);
         const bool adapt = adaptiveInEffect();
-        if (momentsWanted()) keepAccumulation();
+        /* setSampleBudget begins where the frame count starts afresh — the planes are zeroed (restart() and allocate()
+           ask for it) before progression 0, or before progression 1, the first display after a restart(), whose
+           weight is 1 — and ends with what it depends on, or where the planes are zeroed in mid-accumulation */
+        if (!budget_ || !adapt || (stopReset_ && progression_ > 1)) budgetActive_ = false;
+        else if (stopReset_) budgetActive_ = true;
+        const bool passes = budgetActive_ && progression_ > 0; /* (the fold reads the old frame itself: no copy) */
+        if (momentsWanted() && !passes) keepAccumulation();
         if (adapt) maskRenders();
         else {
             clearPlane();
             stopReset_ = true; /* (in effect again later: from a zero plane) */
         }
-        rt_.rayTrace(b.dev.p, width_, height_, progression_, kernel_, true);
-        if (momentsWanted()) {
+        if (passes) {
+            tracePasses();
+            frames_ = n == 1.0f ? 1u : frames_ + 1u;
+        } else
+            rt_.rayTrace(b.dev.p, width_, height_, progression_, kernel_, true);
+        if (momentsWanted() && !passes) {
             b.mom.need(4 * px, "moments buffer");
             /* (without valid moments, after it was switched on in mid-accumulation: start from this frame) */
             const float nMom = momValid_ ? n : 1.0f;
@@ -697,11 +787,18 @@ private:
         }
         /* (the last of these calls waits for the stream, unless a filter's call does) */
         const bool select = adapt && frames_ >= convergeMinFrames_;
-        if (converge_) meterShown(shown, /*sync=*/!varGuided_ && !denoise_ && !select, noiseMapReadback_ || adapt);
+        /* the budget rule follows every fold, and a stop rule that ran at progression 0 (minFrames <= 1): the fold
+           goes by the passes plane alone, where a stopped tile must read 0 */
+        const bool budget = passes || (budgetActive_ && select);
+        if (converge_) meterShown(shown, /*sync=*/!varGuided_ && !denoise_ && !select && !budget, noiseMapReadback_ || adapt);
         if (select) /* the plane the next render is masked by, from this display's tile map */
             rt_.tileStopSelect(b.noiseTiles.p, reinterpret_cast<uint32_t *>(b.stop.p), (uint32_t)n,
                                reinterpret_cast<rt_adaptive_stats *>(b.adaptStats.p), width_, height_, adaptiveParams_, true,
-                               /*sync=*/!varGuided_ && !denoise_);
+                               /*sync=*/!varGuided_ && !denoise_ && !budget);
+        if (budget) /* the passes of the next display, from the same map and the plane just updated */
+            rt_.tileBudget(b.noiseTiles.p, reinterpret_cast<const uint32_t *>(b.stop.p), reinterpret_cast<uint32_t *>(b.passes.p),
+                           reinterpret_cast<rt_budget_stats *>(b.budgetStats.p), width_, height_, budgetParams_, true,
+                           /*sync=*/!varGuided_ && !denoise_);
         if (varGuided_) { /* in place of setDenoise's filter, whether that is on or not */
             rt_.denoiseVar(shown, b.var.p, b.feat.p, b.den.p, nullptr, width_, height_, varParams_, true);
             shown = b.den.p;
@@ -711,8 +808,8 @@ private:
         }
         if (toneMap_) toneMapShown(shown);
         if (!toneMap_ || floatReadback_) { /* (else the 8-bit frame alone: pixels() keeps its last contents) */
-            if (shown == b.dev.p) /* nothing is switched on: the non-sharing readback into the PBO */
-                rt_.read(pbo_.data(), pbo_.size());
+            if (shown == b.dev.p && !passes) /* nothing is switched on: the non-sharing readback into the PBO */
+                rt_.read(pbo_.data(), pbo_.size()); /* (the tracer's last target; in the pass loop that is the scratch frame) */
             else if (hipMemcpy(pbo_.data(), shown, 4 * px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: displayed frame readback failed");
         }
@@ -740,6 +837,16 @@ private:
             }
             if (!ok) throw std::runtime_error("ProgressiveViewHIP: stop rule readback failed");
             converged_ = converged_ || adaptiveStats_.active == 0u;
+        }
+        if (budget) { /* the budget's words, with the frame's other small readbacks */
+            bool ok = hipMemcpy(&budgetStats_, b.budgetStats.p, sizeof budgetStats_, hipMemcpyDeviceToHost) == hipSuccess;
+            haveBudget_ = ok;
+            if (!ok) throw std::runtime_error("ProgressiveViewHIP: budget stats readback failed");
+        }
+        if (budgetActive_ && countReadback_) {
+            sampleCounts_.resize(noiseTileCount());
+            if (hipMemcpy(sampleCounts_.data(), b.count.p, sampleCounts_.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: count plane readback failed");
         }
         if (sphereCarry_ && kernel_ != RT_KERNEL_TRIS) { /* the spheres this frame was displayed with */
             shownSpheres_ = rt_.spheres();
@@ -774,8 +881,14 @@ private:
     rt_noise_params convergeParams_ = RayTracerHIP::noiseDefaults();
     rt_noise_stats noiseStats_{};
     std::vector<float> noiseMap_;
-    /* setAdaptive: on; the plane is to be zeroed before the next render; the tracer holds the view's plane */
-    bool adaptive_ = false, stopReset_ = true, planeSet_ = false, stopMapReadback_ = false;
+    /* setAdaptive: on; the plane is to be zeroed before the next render; the plane the tracer borrows (null: none) */
+    bool adaptive_ = false, stopReset_ = true, stopMapReadback_ = false;
+    const float *plane_ = nullptr;
+    /* setSampleBudget: on; in effect (from a display with zeroed planes on); a budget has run since the planes were zeroed */
+    bool budget_ = false, budgetActive_ = false, haveBudget_ = false, countReadback_ = false;
+    rt_budget_params budgetParams_ = RayTracerHIP::budgetDefaults();
+    rt_budget_stats budgetStats_{};
+    std::vector<uint32_t> sampleCounts_;
     rt_adaptive_params adaptiveParams_ = RayTracerHIP::adaptiveDefaults();
     rt_adaptive_stats adaptiveStats_{};
     std::vector<uint32_t> stopMap_;

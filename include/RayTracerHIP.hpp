@@ -505,6 +505,54 @@ public:
         check(rt_last_adaptive_ms(ctx_, order ? nullptr : &ms, order ? &ms : nullptr), "lastAdaptiveMs");
         return ms;
     }
+    /* (no counterpart in the reference) per-tile sample counts */
+    static rt_budget_params budgetDefaults()
+    {
+        rt_budget_params p;
+        rt_budget_defaults(&p);
+        return p;
+    }
+    /* The fold of a frame's own sample into acc_rgba, a weight per 8x8 tile from count_io (updated in place): the
+       tiles whose word of `passes` exceeds `pass` (passes NULL: all).  The one display-side call that writes an
+       accumulation buffer.  sync = false (device buffers): enqueued on the tracer's stream without a wait. */
+    void foldTiles(const float *sample_rgba, float *acc_rgba, uint32_t *count_io, const uint32_t *passes, uint32_t pass,
+                   const float *mom_in, float *mom_out, float *len_out, unsigned width, unsigned height, bool on_device = false,
+                   bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_fold_tiles(ctx_, sample_rgba, acc_rgba, count_io, passes, pass, mom_in, mom_out, len_out, width, height, flags)
+                   : rt_fold_tiles_async(ctx_, sample_rgba, acc_rgba, count_io, passes, pass, mom_in, mom_out, len_out, width,
+                                         height, flags, nullptr),
+              "foldTiles");
+    }
+    /* The budget rule on noiseMeter's tile map: passes_out[t] = 0 for a stopped tile, else 1 + the limits its mean
+       lies above; *stats_out the counts. */
+    void tileBudget(const float *tiles_mean_max, const uint32_t *stop, uint32_t *passes_out, rt_budget_stats *stats_out,
+                    unsigned width, unsigned height, const rt_budget_params &params = budgetDefaults(), bool on_device = false,
+                    bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_tile_budget(ctx_, tiles_mean_max, stop, passes_out, stats_out, width, height, &params, flags)
+                   : rt_tile_budget_async(ctx_, tiles_mean_max, stop, passes_out, stats_out, width, height, &params, flags, nullptr),
+              "tileBudget");
+    }
+    /* The stop plane of pass `pass`: 0 (rendered) for a live tile whose passes exceed it, else 1. */
+    void tilePassMask(const uint32_t *stop, const uint32_t *passes, uint32_t pass, uint32_t *mask_out, unsigned width,
+                      unsigned height, bool on_device = false, bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_tile_pass_mask(ctx_, stop, passes, pass, mask_out, width, height, flags)
+                   : rt_tile_pass_mask_async(ctx_, stop, passes, pass, mask_out, width, height, flags, nullptr),
+              "tilePassMask");
+    }
+    /* Device time of the last fold (0), budget rule (1) or pass mask (2), ms. */
+    float lastBudgetMs(int which = 0) const
+    {
+        float ms = 0.0f;
+        check(rt_last_budget_ms(ctx_, which == 0 ? &ms : nullptr, which == 1 ? &ms : nullptr, which == 2 ? &ms : nullptr),
+              "lastBudgetMs");
+        return ms;
+    }
 
     rt_counters counters() const
     {

@@ -740,6 +740,64 @@ int rt_moments_accumulate_tiles_async(rt_ctx *ctx, const float *prev_rgba, const
    rt_last_variance_ms' moments_ms. */
 int rt_last_adaptive_ms(const rt_ctx *ctx, float *select_ms, float *order_ms);
 
+/* ---- per-tile sample counts: extra passes per display for the noisy tiles.  The planes
+   hold one word per 8x8 tile, as a stop plane does.  A tile is traced by a masked render at progression
+   0 into a scratch frame — which overwrites the live tiles' pixels with the frame's own sample — and
+   folded into the accumulation buffer afterwards with the weight its own count gives: the triangle
+   kernel needs no per-tile weight. ---- */
+#define RT_BUDGET_MAX_PASSES 8
+/* The fold.  Tile t is folded when passes == NULL or passes[t] > pass.  A folded tile: c = count_io[t], p =
+   c + 1 saturating at 2^32 - 1, n = (float)p, w = 1.0f / n; every pixel of the tile inside the frame gets
+   acc = old + (sample - old) w on all four channels (subtract, multiply, add: the progressive render's own
+   mix, at p == 1 too), with the moments given mom_out = rt_moments_accumulate's moments after a frame with
+   prev = old, cur = new, n_cur = n (its n == 1 branch included), and len_out = n; then count_io[t] = p.  A
+   tile that is not folded keeps acc and its count; mom_out gets mom_in where the two are different
+   buffers, and len_out = (float)count_io[t].  sample_rgba is only read.  mom_in and mom_out are both given
+   or both NULL and may be the same buffer; len_out may be NULL; nothing else may overlap anything
+   (RT_ERR_ARG).  This is the first display-side entry that writes an accumulation buffer; it still touches
+   no render state — seeds, schedule, lists, counters, rt_last_*.  Otherwise the display stages' rules, as
+   rt_moments_accumulate_tiles: `flags` takes RT_OUT_DEVICE only, host arrays are staged, the same stream
+   ordering.  Null sample, acc or count, an empty or oversized frame: RT_ERR_ARG. */
+int rt_fold_tiles(rt_ctx *ctx, const float *sample_rgba, float *acc_rgba, uint32_t *count_io, const uint32_t *passes,
+                  uint32_t pass, const float *mom_in, float *mom_out, float *len_out, uint32_t width, uint32_t height,
+                  int flags);
+int rt_fold_tiles_async(rt_ctx *ctx, const float *sample_rgba, float *acc_rgba, uint32_t *count_io, const uint32_t *passes,
+                        uint32_t pass, const float *mom_in, float *mom_out, float *len_out, uint32_t width, uint32_t height,
+                        int flags, void *hip_stream);
+typedef struct rt_budget_params {
+    uint32_t max_passes;                     /* the most passes a tile gets in one display; 1..RT_BUDGET_MAX_PASSES */
+    float limits[RT_BUDGET_MAX_PASSES - 1]; /* the first max_passes - 1 are read: >= 0, strictly ascending, no NaN */
+} rt_budget_params;
+typedef struct rt_budget_stats {
+    uint32_t tiles;       /* the tile count */
+    uint32_t rounds;      /* the largest pass count a tile got */
+    uint32_t tile_passes; /* the sum of the pass counts */
+    uint32_t reserved;    /* 0 */
+    uint32_t by_passes[RT_BUDGET_MAX_PASSES + 1]; /* [i]: the tiles with i passes */
+} rt_budget_stats;
+int rt_budget_defaults(rt_budget_params *p); /* 4, {0.1f, 0.2f, 0.4f, ...}: the meter's threshold x 2, 4, 8 */
+/* The budget rule on rt_noise_meter's tile map: passes_out[t] = 0 where stop[t] != 0 (stop may be NULL: no
+   tile is stopped), elsewhere 1 + the number of k < max_passes - 1 with mean_t > limits[k].  Comparisons
+   only: a NaN mean is above nothing and gives 1, as does a tile with no valid pixel, which reads (0, 0).
+   The relative error falls as 1 / sqrt(n), so a tile at twice a limit needs four times its samples: the
+   defaults are a coarse monotone step towards that, and the table is the caller's policy.  The display
+   stages' rules as above.  Null map, output or stats, max_passes outside 1..8, a limit read that is NaN,
+   negative or not above the one before it, overlapping buffers: RT_ERR_ARG. */
+int rt_tile_budget(rt_ctx *ctx, const float *tiles_mean_max, const uint32_t *stop, uint32_t *passes_out,
+                   rt_budget_stats *stats_out, uint32_t width, uint32_t height, const rt_budget_params *params, int flags);
+int rt_tile_budget_async(rt_ctx *ctx, const float *tiles_mean_max, const uint32_t *stop, uint32_t *passes_out,
+                         rt_budget_stats *stats_out, uint32_t width, uint32_t height, const rt_budget_params *params,
+                         int flags, void *hip_stream);
+/* The plane of pass `pass`, in rt_set_tile_stop's sense: mask_out[t] = 0 (rendered) where stop[t] == 0 (or
+   stop is NULL) and passes[t] > pass, else 1.  The display stages' rules; mask_out apart from both inputs. */
+int rt_tile_pass_mask(rt_ctx *ctx, const uint32_t *stop, const uint32_t *passes, uint32_t pass, uint32_t *mask_out,
+                      uint32_t width, uint32_t height, int flags);
+int rt_tile_pass_mask_async(rt_ctx *ctx, const uint32_t *stop, const uint32_t *passes, uint32_t pass, uint32_t *mask_out,
+                            uint32_t width, uint32_t height, int flags, void *hip_stream);
+/* Device time of the last fold, budget rule (its stats' reset included) and pass mask, ms; any pointer may be
+   NULL (not all).  RT_ERR_STATE when a stage asked for has not run. */
+int rt_last_budget_ms(const rt_ctx *ctx, float *fold_ms, float *budget_ms, float *mask_ms);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

@@ -225,6 +225,18 @@ class RtAdaptiveStats(ctypes.Structure):
                 ("frames", ctypes.c_uint32)]
 
 
+RT_BUDGET_MAX_PASSES = 8
+
+
+class RtBudgetParams(ctypes.Structure):
+    _fields_ = [("max_passes", ctypes.c_uint32), ("limits", ctypes.c_float * (RT_BUDGET_MAX_PASSES - 1))]
+
+
+class RtBudgetStats(ctypes.Structure):
+    _fields_ = [("tiles", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("tile_passes", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("by_passes", ctypes.c_uint32 * (RT_BUDGET_MAX_PASSES + 1))]
+
+
 # Every symbol the header declares, with its ctypes signature.
 _vp, _u32, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -336,6 +348,15 @@ SIGNATURES = {
     "rt_moments_accumulate_tiles": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _u32, _u32, _i32]),
     "rt_moments_accumulate_tiles_async": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_adaptive_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    # per-tile sample counts (csrc/rt_budget.hip, the fold in csrc/rt_filter.hip)
+    "rt_fold_tiles": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _i32]),
+    "rt_fold_tiles_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "rt_budget_defaults": (_i32, [ctypes.POINTER(RtBudgetParams)]),
+    "rt_tile_budget": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtBudgetParams), _i32]),
+    "rt_tile_budget_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtBudgetParams), _i32, _vp]),
+    "rt_tile_pass_mask": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32]),
+    "rt_tile_pass_mask_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32, _vp]),
+    "rt_last_budget_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

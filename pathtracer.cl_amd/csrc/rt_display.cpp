@@ -12,6 +12,7 @@
  *   the features of moved spheres on the earlier ones         rt_motion.hip     §4.16
  *   the noise meter                                           rt_noise.hip      §4.17
  *   the stop rule, the masked order, the masked moments       rt_adaptive.hip, rt_filter.hip   §4.18
+ *   the fold, the budget rule, the pass mask                  rt_filter.hip, rt_budget.hip     §4.19
  *
  * Every call runs through one driver (AuxCall), which also lays out the staging area of a call on
  * host buffers.
@@ -952,6 +953,140 @@ try {
 int rt_last_adaptive_ms(const rt_ctx *c, float *select_ms, float *order_ms)
 try {
     return last_ms(c, {{RT_ST_STOP_SELECT, select_ms}, {RT_ST_STOP_ORDER, order_ms}});
+} RT_CATCH(err_of(c))
+
+/* ---- per-tile sample counts -------------------------------- */
+
+int rt_fold_tiles_async(rt_ctx *c, const float *sample_rgba, float *acc_rgba, uint32_t *count_io, const uint32_t *passes,
+                        uint32_t pass, const float *mom_in, float *mom_out, float *len_out, uint32_t W, uint32_t H, int flags,
+                        void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!sample_rgba || !acc_rgba || !count_io) return fail(c, RT_ERR_ARG, "rt_fold_tiles: null argument");
+    if (!mom_in != !mom_out) return fail(c, RT_ERR_ARG, "rt_fold_tiles: one of mom_in and mom_out is null");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_fold_tiles: flags other than RT_OUT_DEVICE");
+    const size_t px = (size_t)W * H, tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    /* every buffer apart from every other; the moments may be one buffer exactly */
+    const struct {
+        const void *p;
+        size_t bytes;
+    } buf[] = {{sample_rgba, 4 * px * sizeof(float)}, {acc_rgba, 4 * px * sizeof(float)}, {count_io, tiles * sizeof(uint32_t)},
+               {passes, tiles * sizeof(uint32_t)},    {len_out, px * sizeof(float)},       {mom_in, 4 * px * sizeof(float)},
+               {mom_out, 4 * px * sizeof(float)}};
+    for (int o = 1; o < 7; ++o)
+        for (int i = 0; i < o; ++i)
+            if (!(o == 6 && i == 5 && mom_in == mom_out) && overlaps(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
+                return fail(c, RT_ERR_ARG, "rt_fold_tiles: the buffers overlap");
+    AuxCall x = {c, RT_ST_FOLD};
+    if (const int r = x.open(stream, flags)) return r;
+    /* staged: the sample, the accumulation buffer and the counts (both updated in place there), the passes,
+       the moments (in place there: an unfolded tile keeps them), then the lengths */
+    const Plane pl[] = {{sample_rgba, nullptr, 4 * px},
+                        {acc_rgba, acc_rgba, 4 * px},
+                        {reinterpret_cast<const float *>(count_io), reinterpret_cast<float *>(count_io), tiles},
+                        {reinterpret_cast<const float *>(passes), nullptr, passes ? tiles : 0u},
+                        {mom_in, mom_out, mom_in ? 4 * px : 0u},
+                        {nullptr, len_out, len_out ? px : 0u}};
+    if (const int r = x.begin(pl, 6)) return r;
+    const int e = rt_launch_fold_tiles(x.at(0, sample_rgba), x.at(1, acc_rgba), x.words(2, count_io),
+                                       passes ? x.words(3, passes) : nullptr, pass, mom_in ? x.at(4, mom_in) : nullptr,
+                                       mom_out ? x.at(4, mom_out) : nullptr, len_out ? x.at(5, len_out) : nullptr, W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "fold kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_fold_tiles(rt_ctx *c, const float *sample_rgba, float *acc_rgba, uint32_t *count_io, const uint32_t *passes, uint32_t pass,
+                  const float *mom_in, float *mom_out, float *len_out, uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_fold_tiles_async(c, sample_rgba, acc_rgba, count_io, passes, pass, mom_in, mom_out, len_out, W, H,
+                                              flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_budget_defaults(rt_budget_params *p)
+try {
+    if (!p) return RT_ERR_ARG;
+    p->max_passes = 4;
+    float lim = 0.1f; /* rt_noise_defaults' threshold x 2, 4, 8, ... (exact doublings) */
+    for (float &l : p->limits) {
+        l = lim;
+        lim = lim * 2.0f;
+    }
+    return RT_OK;
+} RT_CATCH(nullptr)
+
+int rt_tile_budget_async(rt_ctx *c, const float *tiles_mean_max, const uint32_t *stop, uint32_t *passes_out,
+                         rt_budget_stats *stats_out, uint32_t W, uint32_t H, const rt_budget_params *prm, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!tiles_mean_max || !passes_out || !stats_out || !prm) return fail(c, RT_ERR_ARG, "rt_tile_budget: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tile_budget: flags other than RT_OUT_DEVICE");
+    if (prm->max_passes < 1 || prm->max_passes > RT_BUDGET_MAX_PASSES)
+        return fail(c, RT_ERR_ARG, "rt_tile_budget: max_passes outside 1..8");
+    for (uint32_t k = 0; k + 1 < prm->max_passes; ++k)
+        if (!(prm->limits[k] >= 0.0f) || (k && !(prm->limits[k] > prm->limits[k - 1])))
+            return fail(c, RT_ERR_ARG, "rt_tile_budget: a limit is NaN, negative or not above the one before it");
+    const size_t tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    const struct {
+        const void *p;
+        size_t bytes;
+    } buf[] = {{tiles_mean_max, 2 * tiles * sizeof(float)}, {stop, tiles * sizeof(uint32_t)},
+               {passes_out, tiles * sizeof(uint32_t)},      {stats_out, sizeof(rt_budget_stats)}};
+    for (int o = 2; o < 4; ++o)
+        for (int i = 0; i < o; ++i)
+            if (overlaps(buf[o].p, buf[o].bytes, buf[i].p, buf[i].bytes))
+                return fail(c, RT_ERR_ARG, "rt_tile_budget: an output overlaps an input or the other output");
+    AuxCall x = {c, RT_ST_BUDGET};
+    if (const int r = x.open(stream, flags)) return r;
+    constexpr size_t kStatWords = sizeof(rt_budget_stats) / sizeof(float);
+    const Plane pl[] = {{tiles_mean_max, nullptr, 2 * tiles},
+                        {reinterpret_cast<const float *>(stop), nullptr, stop ? tiles : 0u},
+                        {nullptr, reinterpret_cast<float *>(passes_out), tiles},
+                        {nullptr, reinterpret_cast<float *>(stats_out), kStatWords}};
+    if (const int r = x.begin(pl, 4)) return r;
+    const int e = rt_launch_tile_budget(x.at(0, tiles_mean_max), stop ? x.words(1, stop) : nullptr, x.words(2, passes_out), W, H,
+                                        prm->max_passes, prm->limits, x.words(3, stats_out), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "budget rule kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_tile_budget(rt_ctx *c, const float *tiles_mean_max, const uint32_t *stop, uint32_t *passes_out, rt_budget_stats *stats_out,
+                   uint32_t W, uint32_t H, const rt_budget_params *prm, int flags)
+try {
+    return finish_sync(c, rt_tile_budget_async(c, tiles_mean_max, stop, passes_out, stats_out, W, H, prm, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_tile_pass_mask_async(rt_ctx *c, const uint32_t *stop, const uint32_t *passes, uint32_t pass, uint32_t *mask_out, uint32_t W,
+                            uint32_t H, int flags, void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!passes || !mask_out) return fail(c, RT_ERR_ARG, "rt_tile_pass_mask: null argument");
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tile_pass_mask: flags other than RT_OUT_DEVICE");
+    const size_t tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u), tb = tiles * sizeof(uint32_t);
+    if (overlaps(mask_out, tb, stop, tb) || overlaps(mask_out, tb, passes, tb))
+        return fail(c, RT_ERR_ARG, "rt_tile_pass_mask: the output overlaps an input");
+    AuxCall x = {c, RT_ST_PASS_MASK};
+    if (const int r = x.open(stream, flags)) return r;
+    const Plane pl[] = {{reinterpret_cast<const float *>(stop), nullptr, stop ? tiles : 0u},
+                        {reinterpret_cast<const float *>(passes), nullptr, tiles},
+                        {nullptr, reinterpret_cast<float *>(mask_out), tiles}};
+    if (const int r = x.begin(pl, 3)) return r;
+    const int e = rt_launch_pass_mask(stop ? x.words(0, stop) : nullptr, x.words(1, passes), pass, W, H, x.words(2, mask_out), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "pass mask kernel launch");
+    return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_tile_pass_mask(rt_ctx *c, const uint32_t *stop, const uint32_t *passes, uint32_t pass, uint32_t *mask_out, uint32_t W,
+                      uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_tile_pass_mask_async(c, stop, passes, pass, mask_out, W, H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_budget_ms(const rt_ctx *c, float *fold_ms, float *budget_ms, float *mask_ms)
+try {
+    return last_ms(c, {{RT_ST_FOLD, fold_ms}, {RT_ST_BUDGET, budget_ms}, {RT_ST_PASS_MASK, mask_ms}});
 } RT_CATCH(err_of(c))
 
 } /* extern "C" */

@@ -1,7 +1,7 @@
 /*
  * rt_display_util.h — what the display kernels' files share: rt_filter.hip (moments, variance, the
  * a-trous passes), rt_temporal.hip (reprojection, merge, trust), rt_tonemap.hip (meter, tone map)
- * and rt_noise.hip (the noise meter).
+ * rt_noise.hip (the noise meter), rt_adaptive.hip and rt_budget.hip (the rules on its tile map).
  *
  *   lum3                  the luminance of a colour, in the bracketing every restatement depends on
  *   kMeterBin0, meter_bin, meter_bin_top   the meter's 384 bins of a float's bits, and back

@@ -5,6 +5,9 @@
  *                      and after it, and keep the running mean of its luminance and of its square
  *   k_moments_tiles    the same on the pixels of the live tiles of a stop plane, with the per-pixel
  *                      history lengths; a stopped tile's pixels keep their moments
+ *   k_fold_tiles       a wave per 8x8 tile: the progressive mix of a frame's own sample into the
+ *                      accumulation buffer with a weight per tile, from a count plane, and the moments
+ *                      and history lengths that go with it
  *   k_variance         per pixel: the variance of the displayed (mean) luminance, from the moments
  *                      where the history is long enough, else from a 7 x 7 feature-weighted window
  *   k_atrous, k_atrous_lds<S>           one pass of the a-trous wavelet filter (Dammertz et al. 2010)
@@ -19,7 +22,8 @@
  * Nothing in the reference corresponds to these kernels; their arithmetic is pinned in
  * DESIGN.md §4.9 and §4.11 under the model of include/rt_math.h (no contraction, IEEE division and
  * square root, the pinned exponential), so that a float32 restatement reproduces every bit.
- * None touches a render's state, and the accumulation buffer is only read.
+ * None touches a render's state, and the accumulation buffer is only read — but for k_fold_tiles,
+ * the one display-side kernel that writes it.
  */
 #include <hip/hip_runtime.h>
 
@@ -38,19 +42,30 @@ __device__ __forceinline__ float unmix(float prev, float cur, float n)
     return s > 0.0f ? s : 0.0f;
 }
 
+/* a pixel's moments after the first frame of a view, which is its own sample: no history */
+__device__ __forceinline__ float4 moments_first(float4 c)
+{
+    const float L = lum3(c.x > 0.0f ? c.x : 0.0f, c.y > 0.0f ? c.y : 0.0f, c.z > 0.0f ? c.z : 0.0f);
+    return make_float4(L, L * L, 0.0f, 0.0f);
+}
+
+/* ... and after frame n > 1 (f = 1 / n), which took the pixel from o to c: m with the sample's luminance mixed in */
+__device__ __forceinline__ float4 moments_next(float4 o, float4 c, float4 m, float n, float f)
+{
+    const float L = lum3(unmix(o.x, c.x, n), unmix(o.y, c.y, n), unmix(o.z, c.z, n));
+    return make_float4(m.x + (L - m.x) * f, m.y + (L * L - m.y) * f, 0.0f, 0.0f);
+}
+
 /* pixel p's moments after a frame; mom_out may be mom_in (the pixel is read before it is written) */
 __device__ __forceinline__ void moments_pixel(const float4 *prev, const float4 *cur, float n, float f, const float4 *mom_in,
                                               float4 *mom_out, uint32_t p)
 {
     const float4 c = cur[p];
     if (n == 1.0f) { /* the first frame of a view is its own sample; no history is read */
-        const float L = lum3(c.x > 0.0f ? c.x : 0.0f, c.y > 0.0f ? c.y : 0.0f, c.z > 0.0f ? c.z : 0.0f);
-        mom_out[p] = make_float4(L, L * L, 0.0f, 0.0f);
+        mom_out[p] = moments_first(c);
         return;
     }
-    const float4 o = prev[p], m = mom_in[p];
-    const float L = lum3(unmix(o.x, c.x, n), unmix(o.y, c.y, n), unmix(o.z, c.z, n));
-    mom_out[p] = make_float4(m.x + (L - m.x) * f, m.y + (L * L - m.y) * f, 0.0f, 0.0f);
+    mom_out[p] = moments_next(prev[p], c, mom_in[p], n, f);
 }
 
 /* One lane per pixel. */
@@ -81,6 +96,49 @@ __global__ __launch_bounds__(kPixelBlock) void k_moments_tiles(const float4 *pre
     }
     moments_pixel(prev, cur, n, f, mom_in, mom_out, p);
     len_out[p] = n;
+}
+
+/* The progressive mix of a frame's own sample into the accumulation buffer, a weight per 8x8 tile
+   (DESIGN.md §4.19), with the moments and the history lengths of the frame it makes.  One wave per
+   tile, lane j = (y & 7) 8 + (x & 7), kHistWaves horizontally adjacent tiles a block as in
+   k_noise_hist: a wave's pixel rows are 128-byte segments.  The tile's count is read once by the whole
+   wave (one address) and written by one lane, whose store waits for that load: no other wave touches
+   the word, so the update in place is safe.  The mix is write_pixel's (rt_kernel_util.h): subtract,
+   multiply, add, at p == 1 too.  passes null: every tile is folded; mom_in and mom_out both or neither;
+   len_out may be null. */
+__global__ __launch_bounds__(kHistBlock) void k_fold_tiles(const float4 *__restrict__ sample, float4 *acc, uint32_t *count,
+                                                           const uint32_t *__restrict__ passes, uint32_t pass,
+                                                           const float4 *mom_in, float4 *mom_out, float *__restrict__ len_out,
+                                                           uint32_t W, uint32_t H, uint32_t tw, uint32_t gw)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t ty = blockIdx.x / gw, tx = (blockIdx.x - ty * gw) * kHistWaves + wave;
+    if (tx >= tw) return; /* (the whole wave) */
+    const uint32_t t = ty * tw + tx;
+    const uint32_t c = count[t];
+    const bool folded = !passes || passes[t] > pass;
+    const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+    const bool inside = x < W && y < H;
+    const uint32_t p = y * W + x; /* < 2^28 where inside */
+    if (!folded) {
+        if (inside) {
+            if (mom_out && mom_out != mom_in) mom_out[p] = mom_in[p];
+            if (len_out) len_out[p] = (float)c;
+        }
+        return;
+    }
+    const uint32_t pc = c == 0xffffffffu ? c : c + 1u;
+    const float n = (float)pc, w = 1.0f / n;
+    if (inside) {
+        const float4 s = sample[p], o = acc[p];
+        float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (mom_out && n != 1.0f) m = mom_in[p]; /* (uniform; in flight with the other two) */
+        const float4 v = make_float4(o.x + (s.x - o.x) * w, o.y + (s.y - o.y) * w, o.z + (s.z - o.z) * w, o.w + (s.w - o.w) * w);
+        acc[p] = v;
+        if (mom_out) mom_out[p] = n == 1.0f ? moments_first(v) : moments_next(o, v, m, n, w);
+        if (len_out) len_out[p] = n;
+    }
+    if (lane == 0u) count[t] = pc;
 }
 
 /* The 49 taps of the spatial estimate are gathered from global memory (only pixels with a short
@@ -327,6 +385,16 @@ int rt_launch_moments_tiles(const float *prev_rgba, const float *cur_rgba, float
                        reinterpret_cast<const float4 *>(prev_rgba), reinterpret_cast<const float4 *>(cur_rgba), n_cur,
                        1.0f / n_cur, reinterpret_cast<const float4 *>(mom_in), reinterpret_cast<float4 *>(mom_out), stop,
                        len_out, W, (W + 7u) / 8u, npx);
+    return (int)hipGetLastError();
+}
+
+int rt_launch_fold_tiles(const float *sample_rgba, float *acc_rgba, uint32_t *count, const uint32_t *passes, uint32_t pass,
+                         const float *mom_in, float *mom_out, float *len_out, uint32_t W, uint32_t H, void *stream)
+{
+    const uint32_t tw = (W + 7u) / 8u, th = (H + 7u) / 8u, gw = (tw + kHistWaves - 1) / kHistWaves;
+    hipLaunchKernelGGL(k_fold_tiles, dim3(gw * th), dim3(kHistBlock), 0, (hipStream_t)stream, /* < 2^22 blocks (the host's frame check) */
+                       reinterpret_cast<const float4 *>(sample_rgba), reinterpret_cast<float4 *>(acc_rgba), count, passes, pass,
+                       reinterpret_cast<const float4 *>(mom_in), reinterpret_cast<float4 *>(mom_out), len_out, W, H, tw, gw);
     return (int)hipGetLastError();
 }
 

@@ -523,5 +523,18 @@ int rt_launch_order_stop(const uint32_t *base, const uint32_t *stop, uint32_t n_
    min_frames; max_limit: the product threshold max_ratio, or +INFINITY. */
 int rt_launch_stop_select(const float *tiles, uint32_t *stop, uint32_t *settled, uint32_t W, uint32_t H, uint32_t n_frames,
                           int quiet_ok, float threshold, float max_limit, uint32_t dilate, uint32_t *stats, void *stream);
+/* -- rt_budget.hip, and the fold in rt_filter.hip -- */
+/* Per-tile sample counts: device buffers.  The fold of a frame's own sample into acc_rgba
+   by the weight 1 / (count[t] + 1) of every tile whose word of `passes` exceeds `pass` (passes null: of
+   every tile), the count updated in place; the moments (both or neither) and len_out (may be null) as
+   rt_fold_tiles gives them. */
+int rt_launch_fold_tiles(const float *sample_rgba, float *acc_rgba, uint32_t *count, const uint32_t *passes, uint32_t pass,
+                         const float *mom_in, float *mom_out, float *len_out, uint32_t W, uint32_t H, void *stream);
+/* The budget rule: tiles = (mean, max) pairs, stop may be null, limits = RT_BUDGET_MAX_PASSES - 1 floats,
+   stats = the words of rt_budget_stats (zeroed on the stream first). */
+int rt_launch_tile_budget(const float *tiles, const uint32_t *stop, uint32_t *passes, uint32_t W, uint32_t H, uint32_t max_passes,
+                          const float *limits, uint32_t *stats, void *stream);
+int rt_launch_pass_mask(const uint32_t *stop, const uint32_t *passes, uint32_t pass, uint32_t W, uint32_t H, uint32_t *mask,
+                        void *stream);
 
 #endif /* RT_INTERNAL_H */

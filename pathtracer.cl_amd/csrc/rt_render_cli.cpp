@@ -57,6 +57,12 @@
  *              under THRESHOLD, default rt_adaptive_defaults'); the event lines gain "tiles_active")
  *              [--adaptive-max-ratio R] [--adaptive-min-frames N] [--adaptive-dilate D]
  *              [--stop-map-out FILE] (the stop planes after the traced displays, appended as words)
+ *             [--budget [MAXPASSES]]   (with --adaptive: the noisy tiles get up to MAXPASSES passes per display
+ *              (ProgressiveViewHIP::setSampleBudget, default rt_budget_defaults'); the event lines gain "rounds" and
+ *              "tile_passes") [--budget-limits A,B,...] (the mean errors above which a tile gets one more pass each)
+ *              [--budget-log FILE] (per traced display one line: rounds, tile_passes, then the tiles with 0, 1, ... 8
+ *              passes, as the budget rule left them for the next display) [--counts-out FILE] (the count planes
+ *              after the traced displays, appended as words)
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -161,7 +167,7 @@ int usage()
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
                          "[--noise-log f] [--noise-map-out f] [--adaptive [THRESHOLD]] [--adaptive-max-ratio R] [--adaptive-min-frames N] "
-                         "[--adaptive-dilate D] [--stop-map-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
+                         "[--adaptive-dilate D] [--stop-map-out f] [--budget [MAXPASSES]] [--budget-limits a,b,...] [--budget-log f] [--counts-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
 
@@ -236,6 +242,9 @@ int main(int argc, char **argv)
     bool adaptive = false;
     rt_adaptive_params adaptive_params = RayTracerHIP::adaptiveDefaults();
     std::string stop_map_out;
+    bool budget = false;
+    rt_budget_params budget_params = RayTracerHIP::budgetDefaults();
+    std::string budget_log, counts_out;
     float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
@@ -307,8 +316,24 @@ int main(int argc, char **argv)
             if ((v = optional_number(argc, argv, i))) adaptive_params.threshold = (float)std::atof(v);
             continue;
         }
+        if (a == "--budget") { /* an optional pass count follows */
+            budget = true;
+            if ((v = optional_number(argc, argv, i))) budget_params.max_passes = (unsigned)std::atoi(v);
+            continue;
+        }
         if (!(v = next())) return usage();
         if (a == "--scene") scene = v;
+        else if (a == "--budget-limits") { /* (the library checks them) */
+            int k = 0;
+            for (const char *q = v; *q && k < RT_BUDGET_MAX_PASSES - 1; ++k) {
+                char *end = nullptr;
+                budget_params.limits[k] = std::strtof(q, &end);
+                if (end == q) return usage();
+                q = *end == ',' ? end + 1 : end;
+            }
+        }
+        else if (a == "--budget-log") budget_log = v;
+        else if (a == "--counts-out") counts_out = v;
         else if (a == "--adaptive-max-ratio") adaptive_params.max_ratio = (float)std::atof(v); /* ("inf": the term is off) */
         else if (a == "--adaptive-min-frames") adaptive_params.min_frames = (unsigned)std::atoi(v);
         else if (a == "--adaptive-dilate") adaptive_params.dilate = (unsigned)std::atoi(v);
@@ -411,6 +436,14 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --adaptive needs --mesh or --ply (the sphere kernels' seed rows shift with the progression)\n");
         return 2;
     }
+    if (budget && !adaptive) {
+        std::fprintf(stderr, "rt_render: --budget needs --adaptive (the passes go to the tiles it leaves live)\n");
+        return 2;
+    }
+    if (!budget && (!budget_log.empty() || !counts_out.empty())) {
+        std::fprintf(stderr, "rt_render: --budget-log / --counts-out need --budget (there is no count plane without it)\n");
+        return 2;
+    }
     if (!adaptive && !stop_map_out.empty()) {
         std::fprintf(stderr, "rt_render: --stop-map-out needs --adaptive (there is no stop plane without it)\n");
         return 2;
@@ -455,6 +488,8 @@ int main(int argc, char **argv)
             if (!noise_map_out.empty()) view.setNoiseMapReadback(true);
             if (adaptive) view.setAdaptive(true, adaptive_params);
             if (!stop_map_out.empty()) view.setStopMapReadback(true);
+            if (budget) view.setSampleBudget(true, budget_params);
+            if (!counts_out.empty()) view.setSampleCountReadback(true);
             rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
             SphereOffsets sphere_offsets{};            /* the o events so far */
             std::vector<float> poses; /* --poses: K poses of 3 n_verts floats */
@@ -482,6 +517,9 @@ int main(int argc, char **argv)
             if ((!noise_log.empty() && !fn) || (!noise_map_out.empty() && !fm)) return 1;
             FILE *fs = stop_map_out.empty() ? nullptr : std::fopen(stop_map_out.c_str(), "wb");
             if (!stop_map_out.empty() && !fs) return 1;
+            FILE *fb = budget_log.empty() ? nullptr : std::fopen(budget_log.c_str(), "w");
+            FILE *fc = counts_out.empty() ? nullptr : std::fopen(counts_out.c_str(), "wb");
+            if ((!budget_log.empty() && !fb) || (!counts_out.empty() && !fc)) return 1;
             size_t pos = 0;
             while (pos <= events.size()) {
                 const size_t end = std::min(events.find(',', pos), events.size());
@@ -510,6 +548,13 @@ int main(int argc, char **argv)
                     }
                     if (traced && fm && !append(fm, view.noiseMap())) return 1;
                     if (traced && fs && std::fwrite(view.stopMap().data(), 4, view.stopMap().size(), fs) != view.stopMap().size()) return 1;
+                    if (traced && fb) {
+                        const rt_budget_stats &bs = view.budgetStats();
+                        std::fprintf(fb, "%u %u", bs.rounds, bs.tile_passes);
+                        for (uint32_t n : bs.by_passes) std::fprintf(fb, " %u", n);
+                        std::fprintf(fb, "\n");
+                    }
+                    if (traced && fc && std::fwrite(view.sampleCounts().data(), 4, view.sampleCounts().size(), fc) != view.sampleCounts().size()) return 1;
                     if (traced && ff) {
                         std::vector<float> ft((size_t)view.width() * view.height() * 8);
                         rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
@@ -556,6 +601,7 @@ int main(int argc, char **argv)
                 if (mesh_update) std::printf(", \"mesh_update\": \"%s\"", mesh_update);
                 if (converge) std::printf(", \"converged\": %s", view.converged() ? "true" : "false");
                 if (adaptive) std::printf(", \"tiles_active\": %u", view.adaptiveStats().active);
+                if (budget) std::printf(", \"rounds\": %u, \"tile_passes\": %u", view.budgetStats().rounds, view.budgetStats().tile_passes);
                 std::printf("}\n");
             }
             if (fo) std::fclose(fo);
@@ -566,6 +612,8 @@ int main(int argc, char **argv)
             if (fn) std::fclose(fn);
             if (fm) std::fclose(fm);
             if (fs) std::fclose(fs);
+            if (fb) std::fclose(fb);
+            if (fc) std::fclose(fc);
             if (!ppm.empty() && (view.pixels8().empty() || !write_ppm(ppm, view.pixels8(), view.width(), view.height()))) return 1;
             std::printf("{\"progression\": %u, \"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, "
                         "\"height\": %u}\n",

@@ -694,6 +694,79 @@ class RayTracer:
         """Device time of the last stop rule, or (order=True) of the last masked order kernel, ms."""
         return self._last_ms("rt_last_adaptive_ms", 2, 1 if order else 0)
 
+    # ---- per-tile sample counts (pathtracer_rt.h, DESIGN.md §4.19) ----
+    def budgetDefaults(self) -> dict:
+        """rt_budget_defaults: `max_passes` and the `limits` it reads (max_passes - 1 floats)."""
+        prm = _abi.RtBudgetParams()
+        self._check(self._lib.rt_budget_defaults(ctypes.byref(prm)), "rt_budget_defaults")
+        return dict(max_passes=int(prm.max_passes), limits=[float(v) for v in prm.limits][:prm.max_passes - 1])
+
+    def foldTiles(self, sample_rgba, acc_rgba, count, passes, pass_: int, width: int, height: int, mom_in=None, mom_out=None,
+                  len_out=None, stream=None, sync: bool = True) -> None:
+        """The progressive mix of a frame's own sample `sample_rgba` into `acc_rgba` with a weight per 8x8
+        tile: tile t is folded when `passes` is None or passes[t] > pass_; its count c = count[t] becomes
+        c + 1 = n, its pixels old + (sample - old) (1 / n), its moments (`mom_in` to `mom_out`, both or
+        neither, may be one buffer) momentsAccumulate's with n_cur = n, `len_out` n.  Other tiles keep
+        frame, count and moments, and get len_out = count[t].  All numpy arrays or all torch CUDA tensors."""
+        px, n = int(width) * int(height), self._tiles(width, height)
+        flags = self._same_kind("foldTiles", [
+            (sample_rgba, px * 4, "sample frame"), (acc_rgba, px * 4, "accumulation buffer"), (count, n, "count plane", self._WORDS),
+            (passes, n, "passes plane", self._WORDS), (mom_in, px * 4, "moments"), (mom_out, px * 4, "destination moments"),
+            (len_out, px, "destination history lengths")])
+        args = (self._h, _abi.ptr(sample_rgba), _abi.ptr(acc_rgba), _abi.ptr(count), _abi.ptr(passes), int(pass_),
+                _abi.ptr(mom_in), _abi.ptr(mom_out), _abi.ptr(len_out), int(width), int(height), flags)
+        self._aux_call("rt_fold_tiles", args, stream, sync)
+
+    def tileBudget(self, tiles, stop, passes_out, width: int, height: int, max_passes: int | None = None, limits=None,
+                   stats=None, stream=None, sync: bool = True):
+        """The budget rule on noiseMeter's tile map `tiles`: passes_out[t] = 0 where stop[t] != 0 (`stop`
+        may be None), else 1 + the number of the first max_passes - 1 `limits` the tile's mean lies above.
+        None for a parameter: the library's default.  Returns the stats as a dict (`tiles`, `rounds`,
+        `tile_passes`, `by_passes`); `stats` (13 words of the buffers' kind) receives the struct's words as
+        well; with sync=False it must be given, nothing is read back and None is returned."""
+        n = self._tiles(width, height)
+        flags = self._same_kind("tileBudget", [(tiles, 2 * n, "tile map"), (stop, n, "stop plane", self._WORDS),
+                                               (passes_out, n, "passes plane", self._WORDS), (stats, 13, "stats", self._WORDS)])
+        if stats is None:
+            if not sync:
+                raise ValueError("tileBudget: sync=False needs a stats buffer")
+            if flags:
+                import torch
+
+                stats = torch.zeros(13, dtype=torch.int32, device=tiles.device)
+            else:
+                stats = np.zeros(13, np.uint32)
+        prm = _abi.RtBudgetParams()
+        self._check(self._lib.rt_budget_defaults(ctypes.byref(prm)), "rt_budget_defaults")
+        if max_passes is not None:
+            prm.max_passes = int(max_passes)
+        if limits is not None:
+            if len(limits) > _abi.RT_BUDGET_MAX_PASSES - 1:
+                raise ValueError("tileBudget: more than 7 limits")
+            for k, v in enumerate(limits):
+                prm.limits[k] = float(v)
+        args = (self._h, _abi.ptr(tiles), _abi.ptr(stop), _abi.ptr(passes_out), _abi.ptr(stats), int(width), int(height),
+                ctypes.byref(prm), flags)
+        self._aux_call("rt_tile_budget", args, stream, sync)
+        if not sync:
+            return None
+        w = stats if isinstance(stats, np.ndarray) else stats.cpu().numpy()
+        w = np.ascontiguousarray(w).view(np.uint32)
+        return dict(tiles=int(w[0]), rounds=int(w[1]), tile_passes=int(w[2]), by_passes=[int(v) for v in w[4:13]])
+
+    def tilePassMask(self, stop, passes, pass_: int, mask_out, width: int, height: int, stream=None, sync: bool = True) -> None:
+        """The stop plane (setTileStop's sense) of pass `pass_`: mask_out[t] = 0 where stop[t] == 0 (`stop`
+        may be None) and passes[t] > pass_, else 1.  All numpy arrays or all torch CUDA tensors."""
+        n = self._tiles(width, height)
+        flags = self._same_kind("tilePassMask", [(stop, n, "stop plane", self._WORDS), (passes, n, "passes plane", self._WORDS),
+                                                 (mask_out, n, "destination mask", self._WORDS)])
+        args = (self._h, _abi.ptr(stop), _abi.ptr(passes), int(pass_), _abi.ptr(mask_out), int(width), int(height), flags)
+        self._aux_call("rt_tile_pass_mask", args, stream, sync)
+
+    def lastBudgetMs(self, which: str = "fold") -> float:
+        """Device time of the last fold ("fold"), budget rule ("budget") or pass mask ("mask"), ms."""
+        return self._last_ms("rt_last_budget_ms", 3, ("fold", "budget", "mask").index(which))
+
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
         if host.dtype != np.float32 or not host.flags["C_CONTIGUOUS"]:
