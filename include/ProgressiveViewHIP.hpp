@@ -104,7 +104,7 @@
  *                    a redisplay as they do after maxProgression.  What is displayed does not change.  Off
  *                    (the default), nothing changes, allocation included.
  *   setAdaptive(on, params)  (no counterpart in the reference) with setConverge, in a view of RT_KERNEL_TRIS without
- *                    setTemporal: stop tracing the 8x8 tiles the noise meter calls quiet.  The
+ *                    setTemporal (or with it and setAdaptiveHistory, below): stop tracing the 8x8 tiles the noise meter calls quiet.  The
  *                    view keeps a stop plane on the device (a word per tile: 0 = refined, k = stopped after k
  *                    frames) that masks its renders (rt_set_tile_stop); the moments and the history lengths
  *                    follow it (rt_moments_accumulate_tiles), the meter's tile map is always computed, and once
@@ -125,6 +125,21 @@
  *                    for the next display from the same tile map.  With max_passes 1 every byte displayed is the
  *                    one setAdaptive alone displays.  Until it takes effect, where setAdaptive is not in effect
  *                    and off (the default), every byte and every call is what it was.
+ *   setAdaptiveHistory(on)  (no counterpart in the reference) lets setAdaptive (and with it setSampleBudget) take effect
+ *                    in a view with setTemporal too.  The stop plane, the masked renders, the
+ *                    moments, the pass loop and the fold run as they do without setTemporal; both merges (colour and
+ *                    moments) and setHistoryTrust's test take the accumulation buffer's frame count per pixel, from
+ *                    the plane of lengths the masked moments and the fold keep (rt_temporal_merge_len,
+ *                    rt_history_trust_len), so the kept lengths are min(own count + carried length, max_history) per
+ *                    pixel and a stopped tile's merged pixels stop changing.  After the meter rt_tile_len_min takes
+ *                    every tile's shortest kept length among its surface pixels, and the stop rule runs at every
+ *                    traced display through rt_tile_stop_select_frames: a tile can stop once that length reaches
+ *                    min(params.min_frames, max_history), whatever the view's own frame count — after a move, a tile
+ *                    that long, quiet history covers stops at once, and the passes go to the disoccluded ones.
+ *                    setConverge's minFrames gates the frame-wide rule alone.  The planes are zeroed where setAdaptive
+ *                    zeroes them; the history survives those events as setTemporal, the carries and setHistoryTrust
+ *                    decide.  Off (the default), every byte and every call is what it was: setAdaptive is not in
+ *                    effect with setTemporal.
  *   setFloatReadback(on)  with setToneMap: off, display() reads back only the 8-bit frame (a quarter of
  *                    the bytes) and pixels() keeps its last contents — those of the last display with the
  *                    readback on, zeros before any; rawPixels() still fetches the accumulation buffer.  On
@@ -355,7 +370,21 @@ public:
         adaptiveParams_ = params;
         converged_ = false; /* the next traced display decides afresh */
     }
-    bool adaptiveInEffect() const { return adaptive_ && converge_ && kernel_ == RT_KERNEL_TRIS && !temporal_; }
+    bool adaptiveInEffect() const { return adaptive_ && converge_ && kernel_ == RT_KERNEL_TRIS && (!temporal_ || adaptHistory_); }
+    /* (no counterpart in the reference) setAdaptive under setTemporal, by per-pixel frame counts: see
+       the file comment.  In effect where setAdaptive, setConverge, setTemporal and this are all on, in a view of
+       RT_KERNEL_TRIS. */
+    void setAdaptiveHistory(bool on)
+    {
+        if (on != adaptHistory_) stopReset_ = true;
+        adaptHistory_ = on;
+        converged_ = false; /* the next traced display decides afresh */
+    }
+    bool adaptiveHistoryInEffect() const { return adaptiveInEffect() && temporal_; }
+    /* With setTemporal: also read the colour history's kept lengths back at every traced display into
+       historyLengths(): W*H floats, bottom row first. */
+    void setHistoryLengthReadback(bool on) { histLenReadback_ = on; }
+    const std::vector<float> &historyLengths() const { return histLen_; }
     /* the stop rule's figures after the last traced display with setAdaptive in effect (zeros before one) */
     const rt_adaptive_stats &adaptiveStats() const { return adaptiveStats_; }
     /* With setAdaptive in effect: also read the stop plane back at every traced display into stopMap():
@@ -496,6 +525,7 @@ private:
         /* setAdaptive: the stop plane (a word per tile) and the stop rule's stats (four words); the per-pixel
            history lengths are in `len` */
         DeviceFloats stop, adaptStats;
+        DeviceFloats tileLen; /* setAdaptiveHistory: every tile's shortest kept history length (a float per tile) */
         /* setSampleBudget: the frame a pass is rendered into, the count, passes and mask planes (a word per tile)
            and the budget rule's stats */
         DeviceFloats sample, count, passes, mask, budgetStats;
@@ -527,6 +557,7 @@ private:
         budgetActive_ = haveBudget_ = false;
         sampleCounts_.clear();
         stopMap_.clear();
+        histLen_.clear();
         stopReset_ = true;
         converged_ = false;
         frames_ = 0;
@@ -554,8 +585,9 @@ private:
     }
     /* The merged frame of this display into the colour history's kept pair; with kept moments (setVarianceGuided,
        setConverge) the view's moments go the same way into theirs.  Both take their lengths from the colour history:
-       they keep one length. */
-    void mergeTemporal(const float *histFeat, float n)
+       they keep one length.  The accumulation buffer's frame count is n, or with curLen (setAdaptiveHistory in effect)
+       each pixel's own of that plane. */
+    void mergeTemporal(const float *histFeat, float n, const float *curLen)
     {
         Buffers &b = *buf_;
         const size_t px = (size_t)width_ * height_;
@@ -607,12 +639,22 @@ private:
            accumulation buffer leaves of the colour's (one plane for both) */
         if (judged) {
             b.trustLen.need(px, "trusted history length buffer");
-            rt_.historyTrust(b.colour.carried.rgba(), b.colour.carried.len(), b.dev.p, n, b.feat.p, b.trustLen.p, width_, height_,
-                             trustParams_, true);
+            if (curLen)
+                rt_.historyTrustLen(b.colour.carried.rgba(), b.colour.carried.len(), b.dev.p, curLen, b.feat.p, b.trustLen.p, width_,
+                                    height_, trustParams_, true);
+            else
+                rt_.historyTrust(b.colour.carried.rgba(), b.colour.carried.len(), b.dev.p, n, b.feat.p, b.trustLen.p, width_, height_,
+                                 trustParams_, true);
         }
-        for (int i = 0; i < nHist; ++i)
-            rt_.temporalMerge(hist[i]->carried.rgba(), judged ? b.trustLen.p : hist[i]->carried.len(), cur[i], n,
-                              temporalParams_.max_history, hist[i]->kept.rgba(), hist[i]->kept.len(), width_, height_, true);
+        for (int i = 0; i < nHist; ++i) {
+            const float *histLen = judged ? b.trustLen.p : hist[i]->carried.len();
+            if (curLen)
+                rt_.temporalMergeLen(hist[i]->carried.rgba(), histLen, cur[i], curLen, temporalParams_.max_history,
+                                     hist[i]->kept.rgba(), hist[i]->kept.len(), width_, height_, true);
+            else
+                rt_.temporalMerge(hist[i]->carried.rgba(), histLen, cur[i], n, temporalParams_.max_history, hist[i]->kept.rgba(),
+                                  hist[i]->kept.len(), width_, height_, true);
+        }
         histCam_ = cam;
         haveHist_ = true;
     }
@@ -739,6 +781,7 @@ private:
         const size_t px = (size_t)width_ * height_;
         const float n = (float)(progression_ > 1 ? progression_ : 1);
         const bool adapt = adaptiveInEffect();
+        const bool adaptHist = adapt && temporal_; /* setAdaptiveHistory in effect: the frame counts are b.len's */
         /* setSampleBudget begins where the frame count starts afresh — the planes are zeroed (restart() and allocate()
            ask for it) before progression 0, or before progression 1, the first display after a restart(), whose
            weight is 1 — and ends with what it depends on, or where the planes are zeroed in mid-accumulation */
@@ -773,7 +816,7 @@ private:
         /* what is displayed, its moments and its history lengths */
         const float *shown = b.dev.p, *moments = b.mom.p, *len = nullptr;
         if (temporal_) {
-            mergeTemporal(histFeat, n);
+            mergeTemporal(histFeat, n, adaptHist ? b.len.p : nullptr);
             shown = b.colour.kept.rgba();
             moments = b.moments.kept.rgba();
             len = b.colour.kept.len();
@@ -786,12 +829,22 @@ private:
             rt_.variance(shown, moments, len, b.feat.p, b.var.p, width_, height_, varParams_, true);
         }
         /* (the last of these calls waits for the stream, unless a filter's call does) */
-        const bool select = adapt && frames_ >= convergeMinFrames_;
+        /* (with setAdaptiveHistory at every display: the gate is each tile's own, by its shortest merged history) */
+        const bool select = adapt && (adaptHist || frames_ >= convergeMinFrames_);
         /* the budget rule follows every fold, and a stop rule that ran at progression 0 (minFrames <= 1): the fold
            goes by the passes plane alone, where a stopped tile must read 0 */
         const bool budget = passes || (budgetActive_ && select);
         if (converge_) meterShown(shown, /*sync=*/!varGuided_ && !denoise_ && !select && !budget, noiseMapReadback_ || adapt);
-        if (select) /* the plane the next render is masked by, from this display's tile map */
+        if (select && adaptHist) { /* ... gated by the shortest kept length of each tile's surface pixels */
+            b.tileLen.need(noiseTileCount(), "tile history lengths");
+            rt_.tileLenMin(len, b.feat.p, b.tileLen.p, width_, height_, true, /*sync=*/false);
+            rt_adaptive_params prm = adaptiveParams_; /* (a cap under min_frames must not keep every tile live for ever) */
+            const float cap = temporalParams_.max_history;
+            if (cap < (float)prm.min_frames) prm.min_frames = (uint32_t)cap; /* (cap >= 1: rt_reproject's check) */
+            rt_.tileStopSelectFrames(b.noiseTiles.p, b.tileLen.p, reinterpret_cast<uint32_t *>(b.stop.p), (uint32_t)n,
+                                     reinterpret_cast<rt_adaptive_stats *>(b.adaptStats.p), width_, height_, prm, true,
+                                     /*sync=*/!varGuided_ && !denoise_ && !budget);
+        } else if (select) /* the plane the next render is masked by, from this display's tile map */
             rt_.tileStopSelect(b.noiseTiles.p, reinterpret_cast<uint32_t *>(b.stop.p), (uint32_t)n,
                                reinterpret_cast<rt_adaptive_stats *>(b.adaptStats.p), width_, height_, adaptiveParams_, true,
                                /*sync=*/!varGuided_ && !denoise_ && !budget);
@@ -848,6 +901,11 @@ private:
             if (hipMemcpy(sampleCounts_.data(), b.count.p, sampleCounts_.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
                 throw std::runtime_error("ProgressiveViewHIP: count plane readback failed");
         }
+        if (temporal_ && histLenReadback_) {
+            histLen_.resize(px);
+            if (hipMemcpy(histLen_.data(), b.colour.kept.len(), px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("ProgressiveViewHIP: history length readback failed");
+        }
         if (sphereCarry_ && kernel_ != RT_KERNEL_TRIS) { /* the spheres this frame was displayed with */
             shownSpheres_ = rt_.spheres();
             shownValid_ = true;
@@ -883,6 +941,9 @@ private:
     std::vector<float> noiseMap_;
     /* setAdaptive: on; the plane is to be zeroed before the next render; the plane the tracer borrows (null: none) */
     bool adaptive_ = false, stopReset_ = true, stopMapReadback_ = false;
+    bool adaptHistory_ = false; /* setAdaptiveHistory */
+    bool histLenReadback_ = false;
+    std::vector<float> histLen_;
     const float *plane_ = nullptr;
     /* setSampleBudget: on; in effect (from a display with zeroed planes on); a budget has run since the planes were zeroed */
     bool budget_ = false, budgetActive_ = false, haveBudget_ = false, countReadback_ = false;

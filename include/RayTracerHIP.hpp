@@ -553,6 +553,58 @@ public:
               "lastBudgetMs");
         return ms;
     }
+    /* (no counterpart in the reference) adaptive sampling under the temporal stage */
+    /* temporalMerge with the accumulation buffer's frame count per pixel (cur_len: under 1 reads as 1). */
+    void temporalMergeLen(const float *hist_rgba, const float *hist_len, const float *cur_rgba, const float *cur_len,
+                          float max_history, float *out_rgba, float *out_len, unsigned width, unsigned height,
+                          bool on_device = false, bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_temporal_merge_len(ctx_, hist_rgba, hist_len, cur_rgba, cur_len, max_history, out_rgba, out_len, width,
+                                           height, flags)
+                   : rt_temporal_merge_len_async(ctx_, hist_rgba, hist_len, cur_rgba, cur_len, max_history, out_rgba, out_len,
+                                                 width, height, flags, nullptr),
+              "temporalMergeLen");
+    }
+    /* historyTrust with the frame count of each pixel's own test taken from cur_len. */
+    void historyTrustLen(const float *hist_rgba, const float *hist_len, const float *cur_rgba, const float *cur_len,
+                         const float *feat, float *out_len, unsigned width, unsigned height,
+                         const rt_trust_params &params = trustDefaults(), bool on_device = false, bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_history_trust_len(ctx_, hist_rgba, hist_len, cur_rgba, cur_len, feat, out_len, width, height, &params,
+                                          flags)
+                   : rt_history_trust_len_async(ctx_, hist_rgba, hist_len, cur_rgba, cur_len, feat, out_len, width, height,
+                                                &params, flags, nullptr),
+              "historyTrustLen");
+    }
+    /* Per 8x8 tile the shortest of the lengths `len` among its pixels that met a surface (feat NULL: among all). */
+    void tileLenMin(const float *len, const float *feat, float *tiles_out, unsigned width, unsigned height, bool on_device = false,
+                    bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_tile_len_min(ctx_, len, feat, tiles_out, width, height, flags)
+                   : rt_tile_len_min_async(ctx_, len, feat, tiles_out, width, height, flags, nullptr),
+              "tileLenMin");
+    }
+    float lastTileLenMs() const
+    {
+        float ms = 0.0f;
+        check(rt_last_tile_len_ms(ctx_, &ms), "lastTileLenMs");
+        return ms;
+    }
+    /* tileStopSelect with the frame gate per tile: tile_frames (tileLenMin's tiles_out) against params.min_frames. */
+    void tileStopSelectFrames(const float *tiles_mean_max, const float *tile_frames, uint32_t *stop_io, uint32_t n_frames,
+                              rt_adaptive_stats *stats_out, unsigned width, unsigned height,
+                              const rt_adaptive_params &params = adaptiveDefaults(), bool on_device = false, bool sync = true)
+    {
+        const int flags = on_device ? RT_OUT_DEVICE : 0;
+        check(sync ? rt_tile_stop_select_frames(ctx_, tiles_mean_max, tile_frames, stop_io, n_frames, stats_out, width, height,
+                                                &params, flags)
+                   : rt_tile_stop_select_frames_async(ctx_, tiles_mean_max, tile_frames, stop_io, n_frames, stats_out, width,
+                                                      height, &params, flags, nullptr),
+              "tileStopSelectFrames");
+    }
 
     rt_counters counters() const
     {

@@ -798,6 +798,62 @@ int rt_tile_pass_mask_async(rt_ctx *ctx, const uint32_t *stop, const uint32_t *p
    NULL (not all).  RT_ERR_STATE when a stage asked for has not run. */
 int rt_last_budget_ms(const rt_ctx *ctx, float *fold_ms, float *budget_ms, float *mask_ms);
 
+/* ---- adaptive sampling under the temporal stage: per-pixel frame counts.  Under a stop
+   plane or a count plane the accumulation buffer's frame count differs from tile to tile; these are the
+   temporal merge and the trust test with that count as a plane (rt_moments_accumulate_tiles' and
+   rt_fold_tiles' len_out), the shortest merged history of every tile, and the stop rule gated by it.  The
+   rules of their scalar twins hold for all four: display only — no render state is changed —, `flags`
+   takes RT_OUT_DEVICE only, host buffers are staged, the same stream ordering, no contraction and IEEE
+   division. ---- */
+/* rt_temporal_merge with the frame count per pixel: n = cur_len[p] >= 1 ? cur_len[p] : 1.0f (a NaN and a 0
+   read as 1: a tile stopped before its first fold has count 0), then that entry's arithmetic with this n —
+   where m = hist_len[p] > 0: l = n + m, f = n / l, out = h + (c - h) f on rgb; elsewhere c's bits and l = n;
+   out.a = c.a and out_len = l < max_history ? l : max_history in both.  out_rgba == hist_rgba and out_len
+   == hist_len are allowed; cur_len (W*H floats) lies apart from both outputs.  out_rgba == cur_rgba, a
+   null pointer, an empty frame, max_history < 1 or NaN, cur_len overlapping an output: RT_ERR_ARG.  Its
+   device time is rt_last_reproject_ms' merge_ms. */
+int rt_temporal_merge_len(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                          const float *cur_len, float max_history, float *out_rgba, float *out_len, uint32_t width,
+                          uint32_t height, int flags);
+int rt_temporal_merge_len_async(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                                const float *cur_len, float max_history, float *out_rgba, float *out_len, uint32_t width,
+                                uint32_t height, int flags, void *hip_stream);
+/* rt_history_trust with n_cur replaced, in both places it appears (vh max(m, 1) / n and 1 + n / m), by the
+   centre pixel's n (the clamp above).  The window's taps are unchanged: where the 7 x 7 window reaches into
+   tiles of other counts their taps are weighed as if they had the centre's — an approximation (DESIGN.md
+   §8).  tolerance = +INFINITY returns hist_len bit for bit.  out_len == hist_len is allowed, cur_len lies
+   apart from out_len; otherwise rt_history_trust's rules and errors.  Its device time is rt_last_trust_ms. */
+int rt_history_trust_len(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                         const float *cur_len, const float *feat, float *out_len, uint32_t width, uint32_t height,
+                         const rt_trust_params *params, int flags);
+int rt_history_trust_len_async(rt_ctx *ctx, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                               const float *cur_len, const float *feat, float *out_len, uint32_t width, uint32_t height,
+                               const rt_trust_params *params, int flags, void *hip_stream);
+/* One float per 8x8 tile on the noise meter's tile grid (ceil(width / 8) x ceil(height / 8), row-major):
+   the minimum of v = len[p] > 0 ? len[p] : 0.0f (a negative length, a NaN and -0 read as +0) over the
+   tile's pixels inside the frame — with feat (the two feature planes; NULL: every pixel counts) over
+   those that met a surface (id != RT_FEAT_NONE): a background pixel never gets a history and must not keep
+   its tile alive.  A tile with no counted pixel reads +INFINITY.  A minimum is exact in any order.  tiles_out
+   apart from both inputs.  Null len or tiles_out, an empty frame, an overlap: RT_ERR_ARG. */
+int rt_tile_len_min(rt_ctx *ctx, const float *len, const float *feat, float *tiles_out, uint32_t width, uint32_t height,
+                    int flags);
+int rt_tile_len_min_async(rt_ctx *ctx, const float *len, const float *feat, float *tiles_out, uint32_t width,
+                          uint32_t height, int flags, void *hip_stream);
+/* Device time of the last rt_tile_len_min, ms.  RT_ERR_STATE when it has not run. */
+int rt_last_tile_len_ms(const rt_ctx *ctx, float *ms);
+/* rt_tile_stop_select with the frame gate per tile: tile t can be quiet only when tile_frames[t] >=
+   (float)min_frames (a NaN does not pass), where the scalar form asks n_frames >= min_frames.  Everything
+   else is that entry's: the dilation, monotone stopping, stop_io[t] = n_frames for a tile stopped now — the
+   stop word remains the accumulation buffer's own frame count, which rt_moments_accumulate_tiles reads as
+   such —, the stats, the errors.  tile_frames (a float per tile) is only read and lies apart from stop_io
+   and stats_out.  Its device time is rt_last_adaptive_ms' select_ms. */
+int rt_tile_stop_select_frames(rt_ctx *ctx, const float *tiles_mean_max, const float *tile_frames, uint32_t *stop_io,
+                               uint32_t n_frames, rt_adaptive_stats *stats_out, uint32_t width, uint32_t height,
+                               const rt_adaptive_params *params, int flags);
+int rt_tile_stop_select_frames_async(rt_ctx *ctx, const float *tiles_mean_max, const float *tile_frames, uint32_t *stop_io,
+                                     uint32_t n_frames, rt_adaptive_stats *stats_out, uint32_t width, uint32_t height,
+                                     const rt_adaptive_params *params, int flags, void *hip_stream);
+
 /* ---- synthetic meshes (deterministic, host-independent: rt_math.h only) ----
    A displaced lat-long sphere truncated to exactly n_tris triangles, centred at
    (cx, cy, cz) with base radius r.  verts must hold rt_mesh_vertex_count(n_tris)

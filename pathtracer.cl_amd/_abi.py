@@ -357,6 +357,17 @@ SIGNATURES = {
     "rt_tile_pass_mask": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32]),
     "rt_tile_pass_mask_async": (_i32, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _i32, _vp]),
     "rt_last_budget_ms": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32), ctypes.POINTER(_f32)]),
+    "rt_temporal_merge_len": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32]),
+    "rt_temporal_merge_len_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "rt_history_trust_len": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTrustParams), _i32]),
+    "rt_history_trust_len_async": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, ctypes.POINTER(RtTrustParams), _i32,
+                                          _vp]),
+    "rt_tile_len_min": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32]),
+    "rt_tile_len_min_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _vp]),
+    "rt_last_tile_len_ms": (_i32, [_vp, ctypes.POINTER(_f32)]),
+    "rt_tile_stop_select_frames": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, ctypes.POINTER(RtAdaptiveParams), _i32]),
+    "rt_tile_stop_select_frames_async": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, ctypes.POINTER(RtAdaptiveParams),
+                                                _i32, _vp]),
     "rt_mesh_vertex_count": (_u32, [_u32]),
     "rt_make_mesh": (_i32, [_u32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "rt_ply_open": (_i32, [ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),

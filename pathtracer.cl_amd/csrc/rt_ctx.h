@@ -104,7 +104,7 @@ static_assert((kCounterBytes + kWorkWords * sizeof(uint32_t)) % sizeof(unsigned 
 constexpr bool kLightCone = true;
 
 /* the display-side stages with a kernel time of their own (rt_display.cpp) */
-enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_METER, RT_ST_TONEMAP, RT_ST_WARP_SPH, RT_ST_NOISE, RT_ST_STOP_SELECT, RT_ST_STOP_ORDER, RT_ST_FOLD, RT_ST_BUDGET, RT_ST_PASS_MASK, RT_ST_COUNT };
+enum RtStage { RT_ST_FEATURES, RT_ST_DENOISE, RT_ST_REPROJECT, RT_ST_MERGE, RT_ST_MOMENTS, RT_ST_VARIANCE, RT_ST_DENOISE_VAR, RT_ST_WARP, RT_ST_TRUST, RT_ST_METER, RT_ST_TONEMAP, RT_ST_WARP_SPH, RT_ST_NOISE, RT_ST_STOP_SELECT, RT_ST_STOP_ORDER, RT_ST_FOLD, RT_ST_BUDGET, RT_ST_PASS_MASK, RT_ST_TILE_LEN, RT_ST_COUNT };
 
 struct rt_ctx {
     int device = 0;

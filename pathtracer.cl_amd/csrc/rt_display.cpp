@@ -13,12 +13,14 @@
  *   the noise meter                                           rt_noise.hip      §4.17
  *   the stop rule, the masked order, the masked moments       rt_adaptive.hip, rt_filter.hip   §4.18
  *   the fold, the budget rule, the pass mask                  rt_filter.hip, rt_budget.hip     §4.19
+ *   the merge, the trust test and the stop rule on per-pixel frame counts   rt_temporal.hip, rt_adaptive.hip   §4.20
  *
  * Every call runs through one driver (AuxCall), which also lays out the staging area of a call on
  * host buffers.
  */
 #include <cmath>
 #include <initializer_list>
+#include <string>
 
 #include "rt_ctx.h"
 #include "rt_math.h"
@@ -221,6 +223,129 @@ int atrous_passes(AuxCall &x, const Plane *pl, const float *in, const float *in_
     return x.end();
 }
 
+/* rt_temporal_merge (cur_len null: the frame count is n_cur) and rt_temporal_merge_len (the count is cur_len's,
+   per pixel), `who` in the messages */
+int temporal_merge(rt_ctx *c, const char *who, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                   const float *cur_len, float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags,
+                   void *stream)
+{
+    if (!c) return RT_ERR_ARG;
+    const std::string w = who;
+    if (!hist_rgba || !hist_len || !cur_rgba || !out_rgba || !out_len) return fail(c, RT_ERR_ARG, (w + ": null argument").c_str());
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, (w + ": flags other than RT_OUT_DEVICE").c_str());
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, (w + ": n_cur below 1 or NaN").c_str());
+    if (!(max_history >= 1.0f)) return fail(c, RT_ERR_ARG, (w + ": max_history below 1 or NaN").c_str());
+    if (out_rgba == cur_rgba) return fail(c, RT_ERR_ARG, (w + ": the output is the current frame's buffer").c_str());
+    const size_t px = (size_t)W * H;
+    if (overlaps(cur_len, px * sizeof(float), out_rgba, 4 * px * sizeof(float)) ||
+        overlaps(cur_len, px * sizeof(float), out_len, px * sizeof(float)))
+        return fail(c, RT_ERR_ARG, (w + ": cur_len overlaps an output").c_str());
+    AuxCall x = {c, RT_ST_MERGE};
+    if (const int r = x.open(stream, flags)) return r;
+    /* staged, and merged in place there */
+    const Plane pl[] = {{hist_rgba, out_rgba, 4 * px}, {cur_rgba, nullptr, 4 * px}, {hist_len, out_len, px},
+                        {cur_len, nullptr, cur_len ? px : 0u}};
+    if (const int r = x.begin(pl, 4)) return r;
+    const int e = rt_launch_temporal_merge(x.at(0, hist_rgba), x.at(2, hist_len), x.at(1, cur_rgba), n_cur,
+                                           cur_len ? x.at(3, cur_len) : nullptr, max_history, x.at(0, out_rgba), x.at(2, out_len),
+                                           W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "temporal merge kernel launch");
+    return x.end();
+}
+
+/* rt_history_trust (cur_len null) and rt_history_trust_len, as temporal_merge */
+int history_trust(rt_ctx *c, const char *who, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
+                  const float *cur_len, const float *feat, float *out_len, uint32_t W, uint32_t H, const rt_trust_params *prm,
+                  int flags, void *stream)
+{
+    if (!c) return RT_ERR_ARG;
+    const std::string w = who;
+    if (!hist_rgba || !hist_len || !cur_rgba || !feat || !out_len || !prm) return fail(c, RT_ERR_ARG, (w + ": null argument").c_str());
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, (w + ": flags other than RT_OUT_DEVICE").c_str());
+    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, (w + ": n_cur below 1 or NaN").c_str());
+    if (!(prm->tolerance > 0.0f)) return fail(c, RT_ERR_ARG, (w + ": tolerance is not positive").c_str()); /* <= 0 or NaN */
+    if (!(prm->sigma_normal > 0.0f) || !(prm->sigma_plane > 0.0f))
+        return fail(c, RT_ERR_ARG, (w + ": a sigma is not positive").c_str()); /* <= 0 or NaN */
+    if (out_len == hist_rgba || out_len == cur_rgba || out_len == feat)
+        return fail(c, RT_ERR_ARG, (w + ": the output is an input other than hist_len").c_str());
+    const size_t px = (size_t)W * H;
+    if (overlaps(cur_len, px * sizeof(float), out_len, px * sizeof(float)))
+        return fail(c, RT_ERR_ARG, (w + ": cur_len overlaps the output").c_str());
+    const bool all = prm->tolerance == rt_inff(); /* everything is trusted: hist_len's bits, no kernel */
+    AuxCall x = {c, RT_ST_TRUST};
+    if (const int r = x.open(stream, flags)) return r;
+    /* the kernel's output lies apart from hist_len, whose neighbours' flags other blocks still read:
+       in the staging area a plane of its own, for device buffers in place a scratch plane */
+    const bool in_place = !x.host && out_len == hist_len;
+    if (in_place && !all)
+        if (const int r = ensure_dev(c, c->d_var_tmp[0], px)) return r;
+    const Plane pl[] = {{all ? nullptr : hist_rgba, nullptr, 4 * px},
+                        {all ? nullptr : cur_rgba, nullptr, 4 * px},
+                        {all ? nullptr : feat, nullptr, 8 * px},
+                        {hist_len, nullptr, px},
+                        {nullptr, out_len, px},
+                        {all ? nullptr : cur_len, nullptr, cur_len ? px : 0u}};
+    if (const int r = x.begin(pl, 6)) return r;
+    const float *dlen = x.at(3, hist_len);
+    float *dout = x.at(4, out_len);
+    if (all) {
+        if (dout != dlen) HIPCHK(c, hipMemcpyAsync(dout, dlen, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+        return x.end();
+    }
+    float *dst = in_place ? c->d_var_tmp[0].p : dout;
+    const int e = rt_launch_history_trust(x.at(0, hist_rgba), dlen, x.at(1, cur_rgba), n_cur, cur_len ? x.at(5, cur_len) : nullptr,
+                                          x.at(2, feat), dst, W, H, prm->tolerance * prm->tolerance, inv_sq(prm->sigma_normal),
+                                          inv_sq(prm->sigma_plane), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "history trust kernel launch");
+    if (in_place) HIPCHK(c, hipMemcpyAsync(dout, dst, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
+    return x.end();
+}
+
+/* rt_tile_stop_select (tile_frames null: the frame gate is n_frames >= min_frames) and rt_tile_stop_select_frames
+   (the gate is the tile's own), as temporal_merge */
+int stop_select(rt_ctx *c, const char *who, const float *tiles_mean_max, const float *tile_frames, uint32_t *stop_io,
+                uint32_t n_frames, rt_adaptive_stats *stats_out, uint32_t W, uint32_t H, const rt_adaptive_params *prm, int flags,
+                void *stream)
+{
+    if (!c) return RT_ERR_ARG;
+    const std::string w = who;
+    if (!tiles_mean_max || !stop_io || !stats_out || !prm) return fail(c, RT_ERR_ARG, (w + ": null argument").c_str());
+    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, (w + ": flags other than RT_OUT_DEVICE").c_str());
+    if (n_frames == 0) return fail(c, RT_ERR_ARG, (w + ": n_frames is 0").c_str());
+    if (!(prm->threshold >= 0.0f)) return fail(c, RT_ERR_ARG, (w + ": threshold negative or NaN").c_str());
+    if (!(prm->max_ratio >= 1.0f)) return fail(c, RT_ERR_ARG, (w + ": max_ratio below 1 or NaN").c_str());
+    if (prm->dilate > 4) return fail(c, RT_ERR_ARG, (w + ": dilate above 4").c_str());
+    const size_t tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    const size_t tb = 2 * tiles * sizeof(float), sb = tiles * sizeof(uint32_t), qb = sizeof(rt_adaptive_stats);
+    if (overlaps(tiles_mean_max, tb, stop_io, sb) || overlaps(tiles_mean_max, tb, stats_out, qb) ||
+        overlaps(stop_io, sb, stats_out, qb) || overlaps(tile_frames, sb, stop_io, sb) || overlaps(tile_frames, sb, stats_out, qb))
+        return fail(c, RT_ERR_ARG, (w + ": the buffers overlap").c_str());
+    /* one float product, formed here; +INFINITY switches the term off (0 x INFINITY would be a NaN) */
+    const float max_limit = prm->max_ratio == rt_inff() ? rt_inff() : prm->threshold * prm->max_ratio;
+    AuxCall x = {c, RT_ST_STOP_SELECT};
+    if (const int r = x.open(stream, flags)) return r;
+    if (const int r = ensure_dev(c, c->d_stop_settled, tiles)) return r;
+    /* staged: the tile pairs, the plane's words (updated in place there), the stats' words, then the tiles' frames */
+    constexpr size_t kStatWords = sizeof(rt_adaptive_stats) / sizeof(float);
+    const Plane pl[] = {{tiles_mean_max, nullptr, 2 * tiles},
+                        {reinterpret_cast<const float *>(stop_io), reinterpret_cast<float *>(stop_io), tiles},
+                        {nullptr, reinterpret_cast<float *>(stats_out), kStatWords},
+                        {tile_frames, nullptr, tile_frames ? tiles : 0u}};
+    if (const int r = x.begin(pl, 4)) return r;
+    const int e = tile_frames
+                      ? rt_launch_stop_select_frames(x.at(0, tiles_mean_max), x.at(3, tile_frames), x.words(1, stop_io),
+                                                     c->d_stop_settled, W, H, n_frames, (float)prm->min_frames, prm->threshold,
+                                                     max_limit, prm->dilate, x.words(2, stats_out), x.st)
+                      : rt_launch_stop_select(x.at(0, tiles_mean_max), x.words(1, stop_io), c->d_stop_settled, W, H, n_frames,
+                                              n_frames >= prm->min_frames, prm->threshold, max_limit, prm->dilate,
+                                              x.words(2, stats_out), x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "stop rule kernel launch");
+    return x.end();
+}
+
 } // namespace
 
 extern "C" {
@@ -368,24 +493,25 @@ int rt_temporal_merge_async(rt_ctx *c, const float *hist_rgba, const float *hist
                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags,
                             void *stream)
 try {
+    return temporal_merge(c, "rt_temporal_merge", hist_rgba, hist_len, cur_rgba, n_cur, nullptr, max_history, out_rgba, out_len,
+                          W, H, flags, stream);
+} RT_CATCH(err_of(c))
+
+int rt_temporal_merge_len_async(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                                const float *cur_len, float max_history, float *out_rgba, float *out_len, uint32_t W,
+                                uint32_t H, int flags, void *stream)
+try {
     if (!c) return RT_ERR_ARG;
-    if (!hist_rgba || !hist_len || !cur_rgba || !out_rgba || !out_len)
-        return fail(c, RT_ERR_ARG, "rt_temporal_merge: null argument");
-    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
-    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_temporal_merge: flags other than RT_OUT_DEVICE");
-    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_temporal_merge: n_cur below 1 or NaN");
-    if (!(max_history >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_temporal_merge: max_history below 1 or NaN");
-    if (out_rgba == cur_rgba) return fail(c, RT_ERR_ARG, "rt_temporal_merge: the output is the current frame's buffer");
-    AuxCall x = {c, RT_ST_MERGE};
-    if (const int r = x.open(stream, flags)) return r;
-    const size_t px = (size_t)W * H;
-    /* staged, and merged in place there */
-    const Plane pl[] = {{hist_rgba, out_rgba, 4 * px}, {cur_rgba, nullptr, 4 * px}, {hist_len, out_len, px}};
-    if (const int r = x.begin(pl, 3)) return r;
-    const int e = rt_launch_temporal_merge(x.at(0, hist_rgba), x.at(2, hist_len), x.at(1, cur_rgba), n_cur, max_history,
-                                           x.at(0, out_rgba), x.at(2, out_len), W, H, x.st);
-    if (e) return hip_fail(c, (hipError_t)e, "temporal merge kernel launch");
-    return x.end();
+    if (!cur_len) return fail(c, RT_ERR_ARG, "rt_temporal_merge_len: null argument");
+    return temporal_merge(c, "rt_temporal_merge_len", hist_rgba, hist_len, cur_rgba, 1.0f, cur_len, max_history, out_rgba,
+                          out_len, W, H, flags, stream);
+} RT_CATCH(err_of(c))
+
+int rt_temporal_merge_len(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, const float *cur_len,
+                          float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_temporal_merge_len_async(c, hist_rgba, hist_len, cur_rgba, cur_len, max_history, out_rgba, out_len,
+                                                      W, H, flags, nullptr));
 } RT_CATCH(err_of(c))
 
 int rt_temporal_merge(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
@@ -415,45 +541,25 @@ int rt_history_trust_async(rt_ctx *c, const float *hist_rgba, const float *hist_
                            const float *feat, float *out_len, uint32_t W, uint32_t H, const rt_trust_params *prm, int flags,
                            void *stream)
 try {
+    return history_trust(c, "rt_history_trust", hist_rgba, hist_len, cur_rgba, n_cur, nullptr, feat, out_len, W, H, prm, flags,
+                         stream);
+} RT_CATCH(err_of(c))
+
+int rt_history_trust_len_async(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba,
+                               const float *cur_len, const float *feat, float *out_len, uint32_t W, uint32_t H,
+                               const rt_trust_params *prm, int flags, void *stream)
+try {
     if (!c) return RT_ERR_ARG;
-    if (!hist_rgba || !hist_len || !cur_rgba || !feat || !out_len || !prm)
-        return fail(c, RT_ERR_ARG, "rt_history_trust: null argument");
-    if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
-    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_history_trust: flags other than RT_OUT_DEVICE");
-    if (!(n_cur >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_history_trust: n_cur below 1 or NaN");
-    if (!(prm->tolerance > 0.0f)) return fail(c, RT_ERR_ARG, "rt_history_trust: tolerance is not positive"); /* <= 0 or NaN */
-    if (!(prm->sigma_normal > 0.0f) || !(prm->sigma_plane > 0.0f))
-        return fail(c, RT_ERR_ARG, "rt_history_trust: a sigma is not positive"); /* <= 0 or NaN */
-    if (out_len == hist_rgba || out_len == cur_rgba || out_len == feat)
-        return fail(c, RT_ERR_ARG, "rt_history_trust: the output is an input other than hist_len");
-    const bool all = prm->tolerance == rt_inff(); /* everything is trusted: hist_len's bits, no kernel */
-    AuxCall x = {c, RT_ST_TRUST};
-    if (const int r = x.open(stream, flags)) return r;
-    const size_t px = (size_t)W * H;
-    /* the kernel's output lies apart from hist_len, whose neighbours' flags other blocks still read:
-       in the staging area a plane of its own, for device buffers in place a scratch plane */
-    const bool in_place = !x.host && out_len == hist_len;
-    if (in_place && !all)
-        if (const int r = ensure_dev(c, c->d_var_tmp[0], px)) return r;
-    const Plane pl[] = {{all ? nullptr : hist_rgba, nullptr, 4 * px},
-                        {all ? nullptr : cur_rgba, nullptr, 4 * px},
-                        {all ? nullptr : feat, nullptr, 8 * px},
-                        {hist_len, nullptr, px},
-                        {nullptr, out_len, px}};
-    if (const int r = x.begin(pl, 5)) return r;
-    const float *dlen = x.at(3, hist_len);
-    float *dout = x.at(4, out_len);
-    if (all) {
-        if (dout != dlen) HIPCHK(c, hipMemcpyAsync(dout, dlen, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
-        return x.end();
-    }
-    float *dst = in_place ? c->d_var_tmp[0].p : dout;
-    const int e = rt_launch_history_trust(x.at(0, hist_rgba), dlen, x.at(1, cur_rgba), n_cur, x.at(2, feat), dst, W, H,
-                                          prm->tolerance * prm->tolerance, inv_sq(prm->sigma_normal),
-                                          inv_sq(prm->sigma_plane), x.st);
-    if (e) return hip_fail(c, (hipError_t)e, "history trust kernel launch");
-    if (in_place) HIPCHK(c, hipMemcpyAsync(dout, dst, px * sizeof(float), hipMemcpyDeviceToDevice, x.st));
-    return x.end();
+    if (!cur_len) return fail(c, RT_ERR_ARG, "rt_history_trust_len: null argument");
+    return history_trust(c, "rt_history_trust_len", hist_rgba, hist_len, cur_rgba, 1.0f, cur_len, feat, out_len, W, H, prm, flags,
+                         stream);
+} RT_CATCH(err_of(c))
+
+int rt_history_trust_len(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, const float *cur_len,
+                         const float *feat, float *out_len, uint32_t W, uint32_t H, const rt_trust_params *prm, int flags)
+try {
+    return finish_sync(c, rt_history_trust_len_async(c, hist_rgba, hist_len, cur_rgba, cur_len, feat, out_len, W, H, prm, flags,
+                                                     nullptr));
 } RT_CATCH(err_of(c))
 
 int rt_history_trust(rt_ctx *c, const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
@@ -883,35 +989,56 @@ int rt_tile_stop_select_async(rt_ctx *c, const float *tiles_mean_max, uint32_t *
                               rt_adaptive_stats *stats_out, uint32_t W, uint32_t H, const rt_adaptive_params *prm, int flags,
                               void *stream)
 try {
+    return stop_select(c, "rt_tile_stop_select", tiles_mean_max, nullptr, stop_io, n_frames, stats_out, W, H, prm, flags, stream);
+} RT_CATCH(err_of(c))
+
+int rt_tile_stop_select_frames_async(rt_ctx *c, const float *tiles_mean_max, const float *tile_frames, uint32_t *stop_io,
+                                     uint32_t n_frames, rt_adaptive_stats *stats_out, uint32_t W, uint32_t H,
+                                     const rt_adaptive_params *prm, int flags, void *stream)
+try {
     if (!c) return RT_ERR_ARG;
-    if (!tiles_mean_max || !stop_io || !stats_out || !prm) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: null argument");
+    if (!tile_frames) return fail(c, RT_ERR_ARG, "rt_tile_stop_select_frames: null argument");
+    return stop_select(c, "rt_tile_stop_select_frames", tiles_mean_max, tile_frames, stop_io, n_frames, stats_out, W, H, prm, flags,
+                       stream);
+} RT_CATCH(err_of(c))
+
+int rt_tile_stop_select_frames(rt_ctx *c, const float *tiles_mean_max, const float *tile_frames, uint32_t *stop_io,
+                               uint32_t n_frames, rt_adaptive_stats *stats_out, uint32_t W, uint32_t H,
+                               const rt_adaptive_params *prm, int flags)
+try {
+    return finish_sync(c, rt_tile_stop_select_frames_async(c, tiles_mean_max, tile_frames, stop_io, n_frames, stats_out, W, H, prm,
+                                                           flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_tile_len_min_async(rt_ctx *c, const float *len, const float *feat, float *tiles_out, uint32_t W, uint32_t H, int flags,
+                          void *stream)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (!len || !tiles_out) return fail(c, RT_ERR_ARG, "rt_tile_len_min: null argument");
     if (!frame_ok(W, H)) return fail(c, RT_ERR_ARG, "bad frame size");
-    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: flags other than RT_OUT_DEVICE");
-    if (n_frames == 0) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: n_frames is 0");
-    if (!(prm->threshold >= 0.0f)) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: threshold negative or NaN");
-    if (!(prm->max_ratio >= 1.0f)) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: max_ratio below 1 or NaN");
-    if (prm->dilate > 4) return fail(c, RT_ERR_ARG, "rt_tile_stop_select: dilate above 4");
-    const size_t tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
-    const size_t tb = 2 * tiles * sizeof(float), sb = tiles * sizeof(uint32_t), qb = sizeof(rt_adaptive_stats);
-    if (overlaps(tiles_mean_max, tb, stop_io, sb) || overlaps(tiles_mean_max, tb, stats_out, qb) ||
-        overlaps(stop_io, sb, stats_out, qb))
-        return fail(c, RT_ERR_ARG, "rt_tile_stop_select: the buffers overlap");
-    /* one float product, formed here; +INFINITY switches the term off (0 x INFINITY would be a NaN) */
-    const float max_limit = prm->max_ratio == rt_inff() ? rt_inff() : prm->threshold * prm->max_ratio;
-    AuxCall x = {c, RT_ST_STOP_SELECT};
+    if (flags & ~RT_OUT_DEVICE) return fail(c, RT_ERR_ARG, "rt_tile_len_min: flags other than RT_OUT_DEVICE");
+    const size_t px = (size_t)W * H, tiles = (size_t)((W + 7u) / 8u) * ((H + 7u) / 8u);
+    if (overlaps(tiles_out, tiles * sizeof(float), len, px * sizeof(float)) ||
+        overlaps(tiles_out, tiles * sizeof(float), feat, 8 * px * sizeof(float)))
+        return fail(c, RT_ERR_ARG, "rt_tile_len_min: the output overlaps an input");
+    AuxCall x = {c, RT_ST_TILE_LEN};
     if (const int r = x.open(stream, flags)) return r;
-    if (const int r = ensure_dev(c, c->d_stop_settled, tiles)) return r;
-    /* staged: the tile pairs, the plane's words (updated in place there), then the stats' words */
-    constexpr size_t kStatWords = sizeof(rt_adaptive_stats) / sizeof(float);
-    const Plane pl[] = {{tiles_mean_max, nullptr, 2 * tiles},
-                        {reinterpret_cast<const float *>(stop_io), reinterpret_cast<float *>(stop_io), tiles},
-                        {nullptr, reinterpret_cast<float *>(stats_out), kStatWords}};
+    /* staged: the lengths, the normal plane of the features (the position plane is not read), then the tiles */
+    const Plane pl[] = {{len, nullptr, px}, {feat ? feat + 4 * px : nullptr, nullptr, feat ? 4 * px : 0u}, {nullptr, tiles_out, tiles}};
     if (const int r = x.begin(pl, 3)) return r;
-    const int e = rt_launch_stop_select(x.at(0, tiles_mean_max), x.words(1, stop_io), c->d_stop_settled, W, H, n_frames,
-                                        n_frames >= prm->min_frames, prm->threshold, max_limit, prm->dilate,
-                                        x.words(2, stats_out), x.st);
-    if (e) return hip_fail(c, (hipError_t)e, "stop rule kernel launch");
+    const int e = rt_launch_tile_len_min(x.at(0, len), feat ? x.at(1, feat + 4 * px) : nullptr, x.at(2, tiles_out), W, H, x.st);
+    if (e) return hip_fail(c, (hipError_t)e, "tile length kernel launch");
     return x.end();
+} RT_CATCH(err_of(c))
+
+int rt_tile_len_min(rt_ctx *c, const float *len, const float *feat, float *tiles_out, uint32_t W, uint32_t H, int flags)
+try {
+    return finish_sync(c, rt_tile_len_min_async(c, len, feat, tiles_out, W, H, flags, nullptr));
+} RT_CATCH(err_of(c))
+
+int rt_last_tile_len_ms(const rt_ctx *c, float *ms)
+try {
+    return last_ms(c, {{RT_ST_TILE_LEN, ms}});
 } RT_CATCH(err_of(c))
 
 int rt_tile_stop_select(rt_ctx *c, const float *tiles_mean_max, uint32_t *stop_io, uint32_t n_frames,

@@ -438,18 +438,21 @@ int rt_launch_features(const RtFeatLaunch &a, int trav, void *stream);
 #define RT_TILE_BY 8
 /* -- rt_temporal.hip -- */
 /* Temporal reprojection of the displayed frame: device buffers;
-   the outputs of the reprojection apart from its inputs, those of the merge possibly its history. */
+   the outputs of the reprojection apart from its inputs, those of the merge possibly its history.
+   The merge and the trust test take the accumulation buffer's frame count as n_cur, or with cur_len (not
+   null, apart from the outputs) per pixel as cur_len[p], 1 where that is under 1 or a NaN (§4.20). */
 int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const float *prev_feat, const rt_camera &prev_cam,
                         const float *cur_feat, float *out_rgba, float *out_len, uint32_t W, uint32_t H, float plane_tol,
                         float normal_min, float max_history, void *stream);
 int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
-                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream);
+                             const float *cur_len, float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H,
+                             void *stream);
 /* The history length each pixel of a carried history still deserves: device
    buffers, out_len apart from every input; k2 the squared tolerance, isn / isp the inverse variances
    of the window's normal and plane terms. */
 int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
-                            const float *feat, float *out_len, uint32_t W, uint32_t H, float k2, float isn, float isp,
-                            void *stream);
+                            const float *cur_len, const float *feat, float *out_len, uint32_t W, uint32_t H, float k2,
+                            float isn, float isp, void *stream);
 /* -- rt_motion.hip -- */
 /* The features of a moving mesh in an earlier pose: device buffers; idx the mesh's
    indices (3 n_tris), pose / prev_verts its current and the earlier vertices (3 n_verts floats each).
@@ -523,6 +526,15 @@ int rt_launch_order_stop(const uint32_t *base, const uint32_t *stop, uint32_t n_
    min_frames; max_limit: the product threshold max_ratio, or +INFINITY. */
 int rt_launch_stop_select(const float *tiles, uint32_t *stop, uint32_t *settled, uint32_t W, uint32_t H, uint32_t n_frames,
                           int quiet_ok, float threshold, float max_limit, uint32_t dilate, uint32_t *stats, void *stream);
+/* The stop rule with the frame gate per tile: tile t can be quiet only where
+   tile_frames[t] >= min_frames (a float per tile, only read; a NaN does not pass); all else as above. */
+int rt_launch_stop_select_frames(const float *tiles, const float *tile_frames, uint32_t *stop, uint32_t *settled, uint32_t W,
+                                 uint32_t H, uint32_t n_frames, float min_frames, float threshold, float max_limit,
+                                 uint32_t dilate, uint32_t *stats, void *stream);
+/* Per 8x8 tile the minimum of max(len, 0) (a NaN: 0) over its pixels inside the frame — with normals (the
+   features' second plane, N and the surface id; may be null) over those that met a surface; +INFINITY
+   where none counts. */
+int rt_launch_tile_len_min(const float *len, const float *normals, float *tiles_out, uint32_t W, uint32_t H, void *stream);
 /* -- rt_budget.hip, and the fold in rt_filter.hip -- */
 /* Per-tile sample counts: device buffers.  The fold of a frame's own sample into acc_rgba
    by the weight 1 / (count[t] + 1) of every tile whose word of `passes` exceeds `pass` (passes null: of

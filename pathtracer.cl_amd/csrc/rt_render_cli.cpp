@@ -63,6 +63,11 @@
  *              [--budget-log FILE] (per traced display one line: rounds, tile_passes, then the tiles with 0, 1, ... 8
  *              passes, as the budget rule left them for the next display) [--counts-out FILE] (the count planes
  *              after the traced displays, appended as words)
+ *             [--adaptive-history]   (with --adaptive and --temporal, which are refused together without it: the tiles
+ *              stop by the length of their merged history (ProgressiveViewHIP::setAdaptiveHistory); --stop-map-out,
+ *              --counts-out, --noise-log, --budget-log and "tiles_active" as under --adaptive)
+ *              [--history-len-out FILE] (with --temporal: the kept history lengths after the traced displays, appended
+ *              as W*H floats)
  *             [--features-out FILE]   (the first-hit feature buffer, 2 planes of W*H float4, of the last
  *              frame; with --events appended for every displayed frame)
  *             [--tile STRIPE,N,R]   (this process renders rank R's row stripes of N: the raw output
@@ -167,7 +172,7 @@ int usage()
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
                          "[--noise-log f] [--noise-map-out f] [--adaptive [THRESHOLD]] [--adaptive-max-ratio R] [--adaptive-min-frames N] "
-                         "[--adaptive-dilate D] [--stop-map-out f] [--budget [MAXPASSES]] [--budget-limits a,b,...] [--budget-log f] [--counts-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
+                         "[--adaptive-dilate D] [--stop-map-out f] [--budget [MAXPASSES]] [--budget-limits a,b,...] [--budget-log f] [--counts-out f] [--adaptive-history] [--history-len-out f] [--tile STRIPE,N,R] [--comm-ranks N --comm-rank R --comm-id FILE]\n");
     return 2;
 }
 
@@ -245,6 +250,8 @@ int main(int argc, char **argv)
     bool budget = false;
     rt_budget_params budget_params = RayTracerHIP::budgetDefaults();
     std::string budget_log, counts_out;
+    bool adaptive_history = false;
+    std::string history_len_out;
     float motion_max_history = 8.0f;
     rt_denoise_var_params var_params = RayTracerHIP::denoiseVarDefaults();
     rt_reproject_params temporal_params = RayTracerHIP::reprojectDefaults();
@@ -259,6 +266,10 @@ int main(int argc, char **argv)
         const char *v = nullptr;
         if (a == "--linear") {
             linear = true;
+            continue;
+        }
+        if (a == "--adaptive-history") {
+            adaptive_history = true;
             continue;
         }
         if (a == "--no-srgb" || a == "--no-dither") {
@@ -334,6 +345,7 @@ int main(int argc, char **argv)
         }
         else if (a == "--budget-log") budget_log = v;
         else if (a == "--counts-out") counts_out = v;
+        else if (a == "--history-len-out") history_len_out = v;
         else if (a == "--adaptive-max-ratio") adaptive_params.max_ratio = (float)std::atof(v); /* ("inf": the term is off) */
         else if (a == "--adaptive-min-frames") adaptive_params.min_frames = (unsigned)std::atoi(v);
         else if (a == "--adaptive-dilate") adaptive_params.dilate = (unsigned)std::atoi(v);
@@ -428,7 +440,19 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "rt_render: --adaptive needs --converge (it stops tiles by the noise meter's map)\n");
         return 2;
     }
-    if (adaptive && temporal) {
+    if (adaptive_history && !adaptive) {
+        std::fprintf(stderr, "rt_render: --adaptive-history needs --adaptive (it lets the stop rule run under --temporal)\n");
+        return 2;
+    }
+    if (adaptive_history && !temporal) {
+        std::fprintf(stderr, "rt_render: --adaptive-history needs --temporal (the tiles stop by their merged history)\n");
+        return 2;
+    }
+    if (!history_len_out.empty() && !temporal) {
+        std::fprintf(stderr, "rt_render: --history-len-out needs --temporal (there is no history without it)\n");
+        return 2;
+    }
+    if (adaptive && temporal && !adaptive_history) {
         std::fprintf(stderr, "rt_render: --adaptive does not go with --temporal (the merged history has no per-tile frame count)\n");
         return 2;
     }
@@ -488,6 +512,8 @@ int main(int argc, char **argv)
             if (!noise_map_out.empty()) view.setNoiseMapReadback(true);
             if (adaptive) view.setAdaptive(true, adaptive_params);
             if (!stop_map_out.empty()) view.setStopMapReadback(true);
+            if (adaptive_history) view.setAdaptiveHistory(true);
+            if (!history_len_out.empty()) view.setHistoryLengthReadback(true);
             if (budget) view.setSampleBudget(true, budget_params);
             if (!counts_out.empty()) view.setSampleCountReadback(true);
             rt_vec3 light_offset = {0.0f, 0.0f, 0.0f}; /* the e events so far */
@@ -520,6 +546,8 @@ int main(int argc, char **argv)
             FILE *fb = budget_log.empty() ? nullptr : std::fopen(budget_log.c_str(), "w");
             FILE *fc = counts_out.empty() ? nullptr : std::fopen(counts_out.c_str(), "wb");
             if ((!budget_log.empty() && !fb) || (!counts_out.empty() && !fc)) return 1;
+            FILE *fl = history_len_out.empty() ? nullptr : std::fopen(history_len_out.c_str(), "wb");
+            if (!history_len_out.empty() && !fl) return 1;
             size_t pos = 0;
             while (pos <= events.size()) {
                 const size_t end = std::min(events.find(',', pos), events.size());
@@ -555,6 +583,7 @@ int main(int argc, char **argv)
                         std::fprintf(fb, "\n");
                     }
                     if (traced && fc && std::fwrite(view.sampleCounts().data(), 4, view.sampleCounts().size(), fc) != view.sampleCounts().size()) return 1;
+                    if (traced && fl && !append(fl, view.historyLengths())) return 1;
                     if (traced && ff) {
                         std::vector<float> ft((size_t)view.width() * view.height() * 8);
                         rt.renderFeatures(ft.data(), view.width(), view.height(), kernel);
@@ -614,6 +643,7 @@ int main(int argc, char **argv)
             if (fs) std::fclose(fs);
             if (fb) std::fclose(fb);
             if (fc) std::fclose(fc);
+            if (fl) std::fclose(fl);
             if (!ppm.empty() && (view.pixels8().empty() || !write_ppm(ppm, view.pixels8(), view.width(), view.height()))) return 1;
             std::printf("{\"progression\": %u, \"azimuth\": %.9g, \"elevation\": %.9g, \"width\": %u, "
                         "\"height\": %u}\n",

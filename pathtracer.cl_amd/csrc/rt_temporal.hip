@@ -5,10 +5,12 @@
  *                      view, gather the four bilinear taps of the previous displayed frame that lie
  *                      on the same surface, and carry their colour and history length over
  *   k_temporal_merge   per pixel: blend the carried history with the accumulation buffer by their
- *                      frame counts
+ *                      frame counts — the accumulation's one count for the frame, or (PER_PIXEL) a
+ *                      plane of them
  *   k_history_trust    per pixel: test the carried history against the accumulation buffer over a
  *                      7 x 7 feature-weighted window staged in LDS, and shorten the history length
- *                      where the two disagree by more than the window's noise explains
+ *                      where the two disagree by more than the window's noise explains; the
+ *                      accumulation's frame count as in the merge
  *
  * Nothing in the reference corresponds to these kernels; their arithmetic is pinned in
  * DESIGN.md §4.10 and §4.14 under the model of include/rt_math.h (no contraction, IEEE division,
@@ -113,16 +115,27 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_reproject(ReprojArgs
     a.out_len[p] = ol;
 }
 
+/* the accumulation buffer's frame count at a pixel of a plane of them: 1 under 1 (a NaN and the 0 of a
+   tile stopped before its first fold among them) */
+__device__ __forceinline__ float frames_at(const float *cur_len, size_t p)
+{
+    const float v = cur_len[p];
+    return v >= 1.0f ? v : 1.0f;
+}
+
 /* out = h + (c - h) (n / (n + m)) where the history is m > 0 frames long, c's bits elsewhere; h, m
-   and the outputs may be the same buffers (each lane reads its pixel before it writes it). */
+   and the outputs may be the same buffers (each lane reads its pixel before it writes it).  PER_PIXEL:
+   n is the pixel's own of cur_len (apart from the outputs), else n_all. */
+template <bool PER_PIXEL>
 __global__ __launch_bounds__(kPixelBlock) void k_temporal_merge(const float4 *hist, const float *hist_len, const float4 *cur,
-                                                        float n, float max_history, float4 *out, float *out_len,
-                                                        uint32_t npx)
+                                                        float n_all, const float *cur_len, float max_history, float4 *out,
+                                                        float *out_len, uint32_t npx)
 {
     const uint32_t p = blockIdx.x * kPixelBlock + threadIdx.x;
     if (p >= npx) return;
     const float4 c = cur[p];
     const float m = hist_len[p];
+    const float n = PER_PIXEL ? frames_at(cur_len, p) : n_all;
     float4 o = c;
     float l = n;
     if (m > 0.0f) {
@@ -142,6 +155,7 @@ struct TrustArgs {
     const float4 *cur;
     const float *hist_len;
     const float4 *feat;
+    const float *cur_len; /* PER_PIXEL: the accumulation's frame counts; else n */
     float *out_len;
     uint32_t W, H;
     float n, k2, isn, isp;
@@ -160,8 +174,11 @@ constexpr int TRUST_TW = RT_TILE_BX + 2 * TRUST_R, TRUST_TH = RT_TILE_BY + 2 * T
    is loaded or read.  (A centre pixel that has a history length and a surface is itself such a
    cell that counts, so its own P, N and id come from the tile.)  The taps are summed in the
    definition's order, dy outer, dx inner, whatever the staging.  out_len apart from every input:
-   a neighbouring block reads hist_len for its halo (the host keeps an in-place call apart). */
-__global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustArgs a)
+   a neighbouring block reads hist_len for its halo (the host keeps an in-place call apart).
+   PER_PIXEL: the accumulation's frame count is the centre pixel's own of cur_len — one dword more a
+   lane, the staging as it is: the taps of a window that reaches into tiles of other counts are
+   weighed as if they had the centre's. */
+template <bool PER_PIXEL> __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustArgs a)
 {
     __shared__ float4 s_p[TRUST_CELLS], s_n[TRUST_CELLS];
     __shared__ float s_lc[TRUST_CELLS], s_lh[TRUST_CELLS];
@@ -191,6 +208,7 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustA
     if (x >= W || y >= H) return;
     const size_t p = (size_t)y * a.W + x;
     const float m = a.hist_len[p];
+    const float n = PER_PIXEL ? frames_at(a.cur_len, p) : a.n;
     if (!(m > 0.0f)) { /* no history (false for a NaN too) */
         a.out_len[p] = 0.0f;
         return;
@@ -232,9 +250,9 @@ __global__ __launch_bounds__(RT_TILE_BX *RT_TILE_BY) void k_history_trust(TrustA
     const float ne = w2 / (ws * ws);
     float o = m;
     if (!(ne > 0.5f)) { /* two effective taps at least: there is something to judge by */
-        const float vs = vh * ((m > 1.0f ? m : 1.0f) / a.n);
+        const float vs = vh * ((m > 1.0f ? m : 1.0f) / n);
         const float v = vc > vs ? vc : vs;
-        const float vd = (v * ne) * (1.0f + a.n / m) + 1e-12f;
+        const float vd = (v * ne) * (1.0f + n / m) + 1e-12f;
         const float d = mc - mh;
         const float z2 = (d * d) / vd;
         if (z2 > a.k2) o = m * (a.k2 / z2);
@@ -280,24 +298,27 @@ int rt_launch_reproject(const float *prev_rgba, const float *prev_len, const flo
 }
 
 int rt_launch_temporal_merge(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
-                             float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H, void *stream)
+                             const float *cur_len, float max_history, float *out_rgba, float *out_len, uint32_t W, uint32_t H,
+                             void *stream)
 {
     const uint32_t npx = W * H; /* < 2^28 (the host's frame check) */
-    hipLaunchKernelGGL(k_temporal_merge, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
+    const auto kernel = cur_len ? k_temporal_merge<true> : k_temporal_merge<false>;
+    hipLaunchKernelGGL(kernel, pixel_grid(npx), dim3(kPixelBlock), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(hist_rgba), hist_len, reinterpret_cast<const float4 *>(cur_rgba),
-                       n_cur, max_history, reinterpret_cast<float4 *>(out_rgba), out_len, npx);
+                       n_cur, cur_len, max_history, reinterpret_cast<float4 *>(out_rgba), out_len, npx);
     return (int)hipGetLastError();
 }
 
 int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const float *cur_rgba, float n_cur,
-                            const float *feat, float *out_len, uint32_t W, uint32_t H, float k2, float isn, float isp,
-                            void *stream)
+                            const float *cur_len, const float *feat, float *out_len, uint32_t W, uint32_t H, float k2,
+                            float isn, float isp, void *stream)
 {
     TrustArgs a;
     a.hist = reinterpret_cast<const float4 *>(hist_rgba);
     a.cur = reinterpret_cast<const float4 *>(cur_rgba);
     a.hist_len = hist_len;
     a.feat = reinterpret_cast<const float4 *>(feat);
+    a.cur_len = cur_len;
     a.out_len = out_len;
     a.W = W;
     a.H = H;
@@ -305,6 +326,7 @@ int rt_launch_history_trust(const float *hist_rgba, const float *hist_len, const
     a.k2 = k2;
     a.isn = isn;
     a.isp = isp;
-    hipLaunchKernelGGL(k_history_trust, tile_grid(W, H), tile_block(), 0, (hipStream_t)stream, a);
+    const auto kernel = cur_len ? k_history_trust<true> : k_history_trust<false>;
+    hipLaunchKernelGGL(kernel, tile_grid(W, H), tile_block(), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -637,12 +637,18 @@ class RayTracer:
         Returns the stats as a dict (`tiles`, `active`, `stopped_now`, `frames`).  All numpy arrays or all
         torch CUDA tensors; `stats` (4 words of the buffers' kind) receives the struct's words as well;
         with sync=False it must be given, nothing is read back and None is returned."""
+        return self._stop_select("tileStopSelect", tiles, None, stop, n_frames, width, height, threshold, max_ratio, min_frames,
+                                 dilate, stats, stream, sync)
+
+    def _stop_select(self, who, tiles, tile_frames, stop, n_frames, width, height, threshold, max_ratio, min_frames, dilate,
+                     stats, stream, sync):
+        """tileStopSelect (`tile_frames` None) and tileStopSelectFrames."""
         n = self._tiles(width, height)
-        flags = self._same_kind("tileStopSelect", [(tiles, 2 * n, "tile map"), (stop, n, "stop plane", self._WORDS),
-                                                   (stats, 4, "stats", self._WORDS)])
+        flags = self._same_kind(who, [(tiles, 2 * n, "tile map"), (tile_frames, n, "tile frames"),
+                                      (stop, n, "stop plane", self._WORDS), (stats, 4, "stats", self._WORDS)])
         if stats is None:
             if not sync:
-                raise ValueError("tileStopSelect: sync=False needs a stats buffer")
+                raise ValueError(f"{who}: sync=False needs a stats buffer")
             if flags:
                 import torch
 
@@ -654,9 +660,11 @@ class RayTracer:
             if v is not None:
                 d[k] = v
         prm = _abi.RtAdaptiveParams(float(d["threshold"]), float(d["max_ratio"]), int(d["min_frames"]), int(d["dilate"]))
-        args = (self._h, _abi.ptr(tiles), _abi.ptr(stop), int(n_frames), _abi.ptr(stats), int(width), int(height),
-                ctypes.byref(prm), flags)
-        self._aux_call("rt_tile_stop_select", args, stream, sync)
+        tail = (_abi.ptr(stop), int(n_frames), _abi.ptr(stats), int(width), int(height), ctypes.byref(prm), flags)
+        if tile_frames is None:
+            self._aux_call("rt_tile_stop_select", (self._h, _abi.ptr(tiles)) + tail, stream, sync)
+        else:
+            self._aux_call("rt_tile_stop_select_frames", (self._h, _abi.ptr(tiles), _abi.ptr(tile_frames)) + tail, stream, sync)
         if not sync:
             return None
         w = stats if isinstance(stats, np.ndarray) else stats.cpu().numpy()
@@ -766,6 +774,61 @@ class RayTracer:
     def lastBudgetMs(self, which: str = "fold") -> float:
         """Device time of the last fold ("fold"), budget rule ("budget") or pass mask ("mask"), ms."""
         return self._last_ms("rt_last_budget_ms", 3, ("fold", "budget", "mask").index(which))
+
+    # ---- adaptive sampling under the temporal stage: per-pixel frame counts (pathtracer_rt.h, DESIGN.md §4.20) ----
+    def temporalMergeLen(self, hist_rgba, hist_len, cur_rgba, cur_len, out_rgba, out_len, width: int, height: int,
+                         max_history: float = 32.0, stream=None, sync: bool = True) -> None:
+        """temporalMerge with the accumulation buffer's frame count per pixel: `cur_len` (W*H floats, as
+        momentsAccumulateTiles and foldTiles write them; a value under 1 or a NaN reads as 1), apart from
+        both outputs.  All numpy arrays or all torch CUDA tensors."""
+        px = int(width) * int(height)
+        flags = self._same_kind("temporalMergeLen", [
+            (hist_rgba, px * 4, "history frame"), (hist_len, px, "history lengths"), (cur_rgba, px * 4, "current frame"),
+            (cur_len, px, "current frame counts"), (out_rgba, px * 4, "destination frame"),
+            (out_len, px, "destination history lengths")])
+        args = (self._h, _abi.ptr(hist_rgba), _abi.ptr(hist_len), _abi.ptr(cur_rgba), _abi.ptr(cur_len), float(max_history),
+                _abi.ptr(out_rgba), _abi.ptr(out_len), int(width), int(height), flags)
+        self._aux_call("rt_temporal_merge_len", args, stream, sync)
+
+    def historyTrustLen(self, hist_rgba, hist_len, cur_rgba, cur_len, feat, out_len, width: int, height: int,
+                        tolerance: float | None = None, sigma_normal: float = 0.3, sigma_plane: float = 0.1, stream=None,
+                        sync: bool = True) -> None:
+        """historyTrust with the frame count of each pixel's test taken from `cur_len` (temporalMergeLen's) at
+        the pixel itself: its window's taps in tiles of other counts are weighed as if they had the centre's.
+        All numpy arrays or all torch CUDA tensors."""
+        px = int(width) * int(height)
+        flags = self._same_kind("historyTrustLen", [
+            (hist_rgba, px * 4, "history frame"), (hist_len, px, "history lengths"), (cur_rgba, px * 4, "current frame"),
+            (cur_len, px, "current frame counts"), (feat, px * 8, "feature buffer"), (out_len, px, "destination history lengths")])
+        if tolerance is None:
+            tolerance = self.trustDefaults()["tolerance"]
+        prm = _abi.RtTrustParams(float(tolerance), float(sigma_normal), float(sigma_plane))
+        args = (self._h, _abi.ptr(hist_rgba), _abi.ptr(hist_len), _abi.ptr(cur_rgba), _abi.ptr(cur_len), _abi.ptr(feat),
+                _abi.ptr(out_len), int(width), int(height), ctypes.byref(prm), flags)
+        self._aux_call("rt_history_trust_len", args, stream, sync)
+
+    def tileLenMin(self, length, feat, tiles_out, width: int, height: int, stream=None, sync: bool = True) -> None:
+        """Per 8x8 tile (noiseMeter's grid) the shortest of the history lengths `length` (W*H floats; negative
+        and NaN read as 0) among the tile's pixels that met a surface by `feat` (None: among all its pixels):
+        `tiles_out`, a float per tile, +inf where no pixel counts.  All numpy arrays or all torch CUDA tensors."""
+        px = int(width) * int(height)
+        flags = self._same_kind("tileLenMin", [(length, px, "history lengths"), (feat, px * 8, "feature buffer"),
+                                               (tiles_out, self._tiles(width, height), "tile lengths")])
+        args = (self._h, _abi.ptr(length), _abi.ptr(feat), _abi.ptr(tiles_out), int(width), int(height), flags)
+        self._aux_call("rt_tile_len_min", args, stream, sync)
+
+    def lastTileLenMs(self) -> float:
+        """Device time of the last tileLenMin kernel, ms."""
+        return self._last_ms("rt_last_tile_len_ms")
+
+    def tileStopSelectFrames(self, tiles, tile_frames, stop, n_frames: int, width: int, height: int,
+                             threshold: float | None = None, max_ratio: float | None = None, min_frames: int | None = None,
+                             dilate: int | None = None, stats=None, stream=None, sync: bool = True):
+        """tileStopSelect with the frame gate per tile: tile t can be quiet only where tile_frames[t] >=
+        min_frames (`tile_frames`: a float per tile, tileLenMin's output; a NaN does not pass).  A tile
+        stopped now still gets the word `n_frames`."""
+        return self._stop_select("tileStopSelectFrames", tiles, tile_frames, stop, n_frames, width, height, threshold, max_ratio,
+                                 min_frames, dilate, stats, stream, sync)
 
     def read(self, host: np.ndarray) -> None:
         """Blocking readback of the last frame into `host` (GlutCLWindow.cpp:214-225)."""
