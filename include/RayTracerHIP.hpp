@@ -167,7 +167,8 @@ public:
         return i;
     }
     void setTraversal(int traversal) { check(rt_set_traversal(ctx_, traversal), "setTraversal"); }
-    /* BVH builder for the next setMesh: RT_BUILD_HOST (binned SAH) or RT_BUILD_GPU (LBVH). */
+    /* BVH builder for the next setMesh: RT_BUILD_HOST (binned SAH), RT_BUILD_GPU (LBVH) or
+       RT_BUILD_GPU_PLOC (PLOC: device-built, merged by surface area). */
     void setBuilder(int builder) { check(rt_set_builder(ctx_, builder), "setBuilder"); }
 
     /* plymain.cpp's PLYLoader (PLYLoader.cpp:4-90) with the mesh actually handed over:

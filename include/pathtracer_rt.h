@@ -121,7 +121,7 @@ typedef struct rt_mesh_stats {
     uint32_t n_nodes4, depth4; /* 4-wide tree */
     uint32_t stack4;           /* worst-case traversal stack of the 4-wide tree */
     double build_seconds;
-    uint32_t builder; /* RT_BUILD_HOST or RT_BUILD_GPU */
+    uint32_t builder; /* RT_BUILD_HOST, RT_BUILD_GPU or RT_BUILD_GPU_PLOC */
     uint32_t n_tris_tree; /* triangles in the tree: the host build leaves out those no ray can
                              hit (|det| < 1e-4 for every unit direction, geometryFuncs.h:167) */
     uint32_t n_nodes4_shadow; /* the shadow queries' 4-wide tree (host build with lights: its cost
@@ -133,10 +133,12 @@ typedef struct rt_mesh_stats {
     uint32_t n_tris_cone; /* that subtree's triangles */
 } rt_mesh_stats;
 /* BVH builder used by the next rt_set_mesh: the host binned-SAH build (default: the best
-   trees) or the GPU build (LBVH over Morton codes, collapsed on the device: seconds-to-
-   milliseconds for large meshes, somewhat slower traversal).  Results are identical
-   either way. */
-enum { RT_BUILD_HOST = 0, RT_BUILD_GPU = 1 };
+   trees), the GPU build (LBVH over Morton codes, collapsed on the device: seconds-to-
+   milliseconds for large meshes, somewhat slower traversal), or the GPU PLOC build (the same
+   sorted order, merged bottom-up by surface area in rounds of mutual nearest neighbours: a
+   few times the LBVH's build time, trees nearer the host build's).  Both GPU builds make one
+   tree and keep every triangle.  Results are identical under all three. */
+enum { RT_BUILD_HOST = 0, RT_BUILD_GPU = 1, RT_BUILD_GPU_PLOC = 2 };
 int rt_set_builder(rt_ctx *ctx, int builder);
 int rt_mesh_info(const rt_ctx *ctx, rt_mesh_stats *out);
 

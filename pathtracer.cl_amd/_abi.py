@@ -39,6 +39,7 @@ RT_TRAVERSAL_BVH4F = 4
 
 RT_BUILD_HOST = 0
 RT_BUILD_GPU = 1
+RT_BUILD_GPU_PLOC = 2
 
 RT_MESH_VERTS_DEVICE = 1
 RT_MESH_UPDATE_REFIT = 1

@@ -12,9 +12,15 @@
  *   3. binary radix tree over the sorted codes (Karras 2012; equal codes broken by the
  *      slot index), one thread per inner node; every node covers a contiguous slot range;
  *   4. boxes bottom-up: one thread per leaf climbs, the second arrival at a node merges;
+ *   3'-4'. (RT_BUILD_GPU_PLOC, instead of 3-4) PLOC: the sorted triangles are clusters; per
+ *      round every cluster finds the neighbour within 16 positions whose union with it has
+ *      the smallest area, pairs that chose each other merge into a node, a prefix sum
+ *      numbers the nodes and compacts the array; flat launches, the count read back once
+ *      per round, halving rounds past a cap;
  *   5. collapse to the 4-wide tree top-down, one launch per level (largest-area child
  *      expanded first, as the host collapse; a subtree of <= kLeafMax triangles becomes a
- *      leaf over its slot range), nodes numbered breadth-first (root 0);
+ *      leaf over its slot range, or over its gathered slots under PLOC), nodes numbered
+ *      breadth-first (root 0);
  *   6. quantisation of every node (same rounding rule as rt_bvh.cpp) and the triangle
  *      records in slot order, e1/e2 formed by the reference's get_triangle subtraction.
  *
@@ -27,7 +33,10 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rt_internal.h"
@@ -213,27 +222,140 @@ __device__ __forceinline__ float box_area(const float *b)
     return 2.0f * (dx * dy + dy * dz + dz * dx);
 }
 
+/* 3'-4'. PLOC (Meister & Bittner 2018): the binary tree by rounds of merges of mutual nearest
+   neighbours in the sorted order, instead of 3-4.  A cluster is (id, box): id >= 0 a binary
+   node, id < 0 the leaf ~slot.  DESIGN.md §4.6a has the rule. */
+constexpr int kPlocR = 16; /* search radius, in positions of the cluster array */
+
+__global__ void k_ploc_init(const float *__restrict__ tbox, const uint32_t *__restrict__ perm, int n,
+                            int *__restrict__ cid, float *__restrict__ cbox)
+{
+    const int s = blockIdx.x * kB + threadIdx.x;
+    if (s >= n) return;
+    cid[s] = ~s;
+    const float *src = tbox + 6ull * perm[s];
+    for (int a = 0; a < 6; ++a) cbox[6ull * s + a] = src[a];
+}
+
+/* nn[i]: among the positions j != i within kPlocR of i, the one with the smallest
+   (area of the union, j == i ^ 1 ? 0 : 1, j).  A block stages its positions' boxes and a halo
+   of kPlocR on each side in LDS, one array per plane so that a wave's reads are consecutive.
+   halving: nn[i] = i ^ 1 (or none, -1, for the last of an odd count). */
+__global__ __launch_bounds__(kB) void k_ploc_nn(const float *__restrict__ cbox, int C, int halving,
+                                                 int *__restrict__ nn)
+{
+    constexpr int kW = kB + 2 * kPlocR;
+    __shared__ float s_box[6][kW];
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (halving) { /* the same in every thread of the launch */
+        if (i < C) nn[i] = (i ^ 1) < C ? (i ^ 1) : -1;
+        return;
+    }
+    const int base = blockIdx.x * kB - kPlocR; /* position of s_box[.][0] */
+    const int first = base < 0 ? 0 : base;
+    const int last = base + kW < C ? base + kW : C; /* staged positions: [first, last) */
+    const float *src = cbox + 6ull * (uint32_t)first;
+    for (int f = threadIdx.x; f < 6 * (last - first); f += kB) s_box[f % 6][first - base + f / 6] = src[f];
+    __syncthreads();
+    if (i >= C) return;
+    const int e0 = threadIdx.x + kPlocR;
+    float b[6];
+    for (int a = 0; a < 6; ++a) b[a] = s_box[a][e0];
+    int best_j = -1;
+    float best_d = 0.0f;
+    for (int k = -kPlocR; k <= kPlocR; ++k) {
+        const int j = i + k;
+        if (k == 0 || j < 0 || j >= C) continue;
+        float u[6];
+        for (int a = 0; a < 3; ++a) {
+            u[a] = fminf(b[a], s_box[a][e0 + k]);
+            u[3 + a] = fmaxf(b[3 + a], s_box[3 + a][e0 + k]);
+        }
+        const float d = box_area(u);
+        if (best_j < 0 || d < best_d || (d == best_d && j == (i ^ 1))) {
+            best_d = d;
+            best_j = j;
+        }
+    }
+    nn[i] = best_j;
+}
+
+/* A pair is merged when each is the other's choice; its lower position (the leader) keeps
+   the place.  flags[i] = leader << 32 | kept: one exclusive sum numbers the new nodes and
+   the surviving positions. */
+__global__ void k_ploc_flags(const int *__restrict__ nn, int C, uint64_t *__restrict__ flags)
+{
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i >= C) return;
+    const int j = nn[i];
+    const bool mutual = j >= 0 && j < C && nn[j] == i;
+    flags[i] = ((uint64_t)(mutual && i < j) << 32) | (uint64_t)!(mutual && i > j);
+}
+
+/* The round's merges and the compaction: a leader at position i makes node K + (leaders before
+   i) with the children (cid[i], cid[nn[i]]); every kept cluster moves to (kept before it). */
+__global__ void k_ploc_merge(const int *__restrict__ cid, const float *__restrict__ cbox,
+                             const int *__restrict__ nn, const uint64_t *__restrict__ flags,
+                             const uint64_t *__restrict__ scan, int C, int K, int n_inner, int *__restrict__ cid_out,
+                             float *__restrict__ cbox_out, int2 *__restrict__ child, float *__restrict__ nbox,
+                             uint32_t *__restrict__ nsize, uint32_t *__restrict__ c_out)
+{
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i >= C) return;
+    const uint64_t fl = flags[i], sc = scan[i];
+    const uint32_t pos = (uint32_t)sc;
+    if (i == C - 1) *c_out = pos + (uint32_t)(fl & 1u);
+    if (!(fl & 1u)) return;
+    float b[6];
+    for (int a = 0; a < 6; ++a) b[a] = cbox[6ull * i + a];
+    int id = cid[i];
+    if (fl >> 32) {
+        const int j = nn[i];
+        const int node = K + (int)(sc >> 32);
+        if (node >= n_inner) return; /* cannot happen: n - 1 merges in all (the host checks the count) */
+        const int idj = cid[j];
+        for (int a = 0; a < 3; ++a) {
+            b[a] = fminf(b[a], cbox[6ull * j + a]);
+            b[3 + a] = fmaxf(b[3 + a], cbox[6ull * j + 3 + a]);
+        }
+        child[node] = make_int2(id, idj);
+        for (int a = 0; a < 6; ++a) nbox[6ull * node + a] = b[a];
+        nsize[node] = (id >= 0 ? nsize[id] : 1u) + (idj >= 0 ? nsize[idj] : 1u);
+        id = node;
+    }
+    cid_out[pos] = id;
+    for (int a = 0; a < 6; ++a) cbox_out[6ull * pos + a] = b[a];
+}
+
 struct Frontier {
     int bin;   /* binary inner node (or ~slot for a single-triangle mesh) */
     int out;   /* 4-wide node index */
     int stack; /* traversal stack entries live on entry */
 };
 
-/* 5. one level of the top-down collapse */
+/* 5. one level of the top-down collapse.  kPloc = false: the radix tree, whose nodes cover
+   contiguous slot ranges (`range`).  kPloc = true: the PLOC tree, whose nodes cover any set of
+   slots: a subtree's triangle count is read from `nsize`, and a leaf's slots are gathered by a
+   walk of its (at most 2 kLeafMax - 1) nodes, left child first. */
+template <bool kPloc>
 __global__ void k_collapse(const Frontier *__restrict__ cur, const uint32_t *__restrict__ n_cur,
                            Frontier *__restrict__ next, uint32_t *__restrict__ n_next, uint32_t *__restrict__ n_nodes,
                            uint32_t *__restrict__ max_stack, const int2 *__restrict__ child,
-                           const int2 *__restrict__ range, const float *__restrict__ nbox,
-                           const float *__restrict__ tbox, const uint32_t *__restrict__ perm, int n,
-                           float *__restrict__ nodes4, uint32_t *__restrict__ n_tris_out,
-                           uint32_t *__restrict__ perm2)
+                           const int2 *__restrict__ range, const uint32_t *__restrict__ nsize,
+                           const float *__restrict__ nbox, const float *__restrict__ tbox,
+                           const uint32_t *__restrict__ perm, int n, float *__restrict__ nodes4,
+                           uint32_t *__restrict__ n_tris_out, uint32_t *__restrict__ perm2)
 {
     const uint32_t e = blockIdx.x * kB + threadIdx.x;
     if (e >= *n_cur) return;
     const Frontier f = cur[e];
     int kids[4] = {0, 0, 0, 0};
     int nk = 0;
-    auto size_of = [&](int c) -> int { return c >= 0 ? range[c].y - range[c].x + 1 : 1; };
+    auto size_of = [&](int c) -> int {
+        if (c < 0) return 1;
+        if constexpr (kPloc) return (int)nsize[c];
+        else return range[c].y - range[c].x + 1;
+    };
     auto expandable = [&](int c) -> bool { return c >= 0 && size_of(c) > (int)kLeafMax; };
     if (f.bin < 0 || n < 2 || size_of(f.bin) <= (int)kLeafMax) {
         kids[nk++] = f.bin; /* the whole (small) mesh as one leaf */
@@ -292,15 +414,32 @@ __global__ void k_collapse(const Frontier *__restrict__ cur, const uint32_t *__r
                     count = 1;
                     for (int a = 0; a < 6; ++a) b[a] = tbox[6ull * perm[first_old] + a];
                 } else if (n >= 2) {
-                    first_old = (uint32_t)range[c].x;
-                    count = (uint32_t)(range[c].y - range[c].x + 1);
+                    if constexpr (!kPloc) first_old = (uint32_t)range[c].x;
+                    count = (uint32_t)size_of(c);
                     for (int a = 0; a < 6; ++a) b[a] = nbox[6ull * c + a];
                 } else {
                     for (int a = 0; a < 6; ++a) b[a] = tbox[6ull * perm[0] + a];
                 }
                 const uint32_t first = next_tri;
                 next_tri += count;
-                for (uint32_t q = 0; q < count; ++q) perm2[first + q] = first_old + q;
+                if (kPloc && c >= 0 && n >= 2) {
+                    /* count <= kLeafMax: at most 2 kLeafMax - 1 nodes, the stack never holds
+                       more than kLeafMax of them */
+                    int stack[kLeafMax + 1], sp = 0;
+                    uint32_t q = 0;
+                    stack[sp++] = c;
+                    for (uint32_t it = 0; it < 2 * kLeafMax - 1 && sp > 0; ++it) {
+                        const int x = stack[--sp];
+                        if (x < 0) {
+                            if (q < count) perm2[first + q++] = (uint32_t)(~x);
+                        } else if (sp + 2 <= (int)kLeafMax + 1) {
+                            stack[sp++] = child[x].y;
+                            stack[sp++] = child[x].x;
+                        }
+                    }
+                } else {
+                    for (uint32_t q = 0; q < count; ++q) perm2[first + q] = first_old + q;
+                }
                 code = ~(int32_t)((first << 3) | (count - 1));
             }
         }
@@ -421,14 +560,136 @@ struct DevBuf {
         }                                                                                                              \
     } while (0)
 
+namespace {
+/* Stage times of one build by HIP events, for profiles/ploc/measure.py: with RT_BUILD_PROFILE
+   naming a file, every build appends one JSON line to it.  Without it nothing is recorded and
+   nothing waits. */
+struct BuildProfile {
+    bool on = false, ploc = false;
+    const char *path = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<std::pair<std::string, float>> ms;
+    explicit BuildProfile(bool ploc_) : ploc(ploc_)
+    {
+        path = getenv("RT_BUILD_PROFILE");
+        on = path && *path && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    }
+    ~BuildProfile()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void begin(hipStream_t st)
+    {
+        if (on) (void)hipEventRecord(ev[0], st);
+    }
+    /* the time since begin() or the last lap(), added to `name` */
+    void lap(hipStream_t st, const char *name)
+    {
+        if (!on) return;
+        float t = 0.0f;
+        (void)hipEventRecord(ev[1], st);
+        (void)hipEventSynchronize(ev[1]);
+        (void)hipEventElapsedTime(&t, ev[0], ev[1]);
+        for (auto &m : ms)
+            if (m.first == name) {
+                m.second += t;
+                t = -1.0f;
+                break;
+            }
+        if (t >= 0.0f) ms.emplace_back(name, t);
+        (void)hipEventRecord(ev[0], st);
+    }
+    void write(uint32_t n_tris, uint32_t rounds, double seconds) const
+    {
+        if (!on) return;
+        FILE *f = fopen(path, "a");
+        if (!f) return;
+        fprintf(f, "{\"builder\": \"%s\", \"n_tris\": %u, \"rounds\": %u, \"build_seconds\": %.6f, \"ms\": {",
+                ploc ? "ploc" : "gpu", n_tris, rounds, seconds);
+        for (size_t i = 0; i < ms.size(); ++i) fprintf(f, "%s\"%s\": %.4f", i ? ", " : "", ms[i].first.c_str(), ms[i].second);
+        fprintf(f, "}}\n");
+        fclose(f);
+    }
+};
+} // namespace
+
+/* The PLOC rounds (k_ploc_*): child / nbox / nsize of the n - 1 binary nodes, the root last
+   (node n - 2).  Rounds search until `cap`, then halve (nn = i ^ 1), so the count is bounded
+   whatever the boxes are; the cluster count is read back once per round. */
+static int ploc_tree(const float *tbox, const uint32_t *perm, int n, int2 *child, float *nbox, uint32_t *nsize,
+                     hipStream_t st, BuildProfile &prof, uint32_t &rounds, std::string &err)
+{
+    DevBuf d_cid[2], d_cbox[2], d_nn, d_flags, d_scan, d_tmp, d_c;
+    for (int k = 0; k < 2; ++k) {
+        GCHK(hipMalloc(&d_cid[k].p, 4ull * n));
+        GCHK(hipMalloc(&d_cbox[k].p, 24ull * n));
+    }
+    GCHK(hipMalloc(&d_nn.p, 4ull * n));
+    GCHK(hipMalloc(&d_flags.p, 8ull * n));
+    GCHK(hipMalloc(&d_scan.p, 8ull * n));
+    GCHK(hipMalloc(&d_c.p, sizeof(uint32_t)));
+    size_t tmp_bytes = 0;
+    GCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint64_t *)d_flags.p, (uint64_t *)d_scan.p, n, st));
+    GCHK(hipMalloc(&d_tmp.p, tmp_bytes ? tmp_bytes : 1));
+    hipLaunchKernelGGL(k_ploc_init, dim3(blocks_for(n)), dim3(kB), 0, st, tbox, perm, n, (int *)d_cid[0].p,
+                       (float *)d_cbox[0].p);
+    GCHK(hipGetLastError());
+    prof.lap(st, "ploc_init");
+    int log2n = 0;
+    while ((1ll << log2n) < n) ++log2n;
+    const uint32_t cap = 6u * log2n + 16u, bound = cap + log2n;
+    int C = n, K = 0, cur = 0;
+    for (rounds = 0; C > 1; ++rounds) {
+        if (rounds >= bound) {
+            err = "PLOC build: round bound passed";
+            return -1;
+        }
+        const unsigned g = blocks_for(C);
+        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(kB), 0, st, (const float *)d_cbox[cur].p, C,
+                           rounds >= cap ? 1 : 0, (int *)d_nn.p);
+        GCHK(hipGetLastError());
+        prof.lap(st, "ploc_nn");
+        hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(kB), 0, st, (const int *)d_nn.p, C, (uint64_t *)d_flags.p);
+        GCHK(hipGetLastError());
+        prof.lap(st, "ploc_flags");
+        size_t tb = tmp_bytes;
+        GCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, (const uint64_t *)d_flags.p, (uint64_t *)d_scan.p, C, st));
+        prof.lap(st, "ploc_scan");
+        hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(kB), 0, st, (const int *)d_cid[cur].p,
+                           (const float *)d_cbox[cur].p, (const int *)d_nn.p, (const uint64_t *)d_flags.p,
+                           (const uint64_t *)d_scan.p, C, K, n - 1, (int *)d_cid[1 - cur].p, (float *)d_cbox[1 - cur].p,
+                           child, nbox, nsize, (uint32_t *)d_c.p);
+        GCHK(hipGetLastError());
+        uint32_t c_new = 0;
+        GCHK(hipMemcpyAsync(&c_new, d_c.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        GCHK(hipStreamSynchronize(st));
+        prof.lap(st, "ploc_merge");
+        if (c_new < 1 || c_new >= (uint32_t)C) {
+            err = "PLOC build: no progress";
+            return -1;
+        }
+        K += C - (int)c_new;
+        C = (int)c_new;
+        cur = 1 - cur;
+    }
+    if (K != n - 1) {
+        err = "PLOC build: node count";
+        return -1;
+    }
+    return 0;
+}
+
 int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_h, uint32_t n_tris, RtGpuBvh &out,
-                     std::string &err, void *stream, bool det_cull)
+                     std::string &err, void *stream, bool det_cull, bool ploc)
 {
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)n_tris;
     DevBuf d_verts, d_idx, d_tbox, d_cent, d_bounds, d_keys, d_keys2, d_vals, d_perm, d_child, d_range, d_pin,
-        d_pleaf, d_nbox, d_flags, d_front[2], d_counts, d_tmp, d_perm2;
+        d_pleaf, d_nbox, d_flags, d_front[2], d_counts, d_tmp, d_perm2, d_nsize;
+    BuildProfile prof(ploc);
+    prof.begin(st);
     GCHK(hipMalloc(&d_verts.p, 12ull * n_verts));
     GCHK(hipMalloc(&d_idx.p, 12ull * n_tris));
     GCHK(hipMemcpyAsync(d_verts.p, verts_h, 12ull * n_verts, hipMemcpyHostToDevice, st));
@@ -457,24 +718,37 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
     GCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (uint64_t *)d_keys.p, (uint64_t *)d_keys2.p,
                                             (uint32_t *)d_vals.p, (uint32_t *)d_perm.p, n, 0, 63, st));
 
+    prof.lap(st, "sort");
     const uint64_t n_inner = n >= 2 ? (uint64_t)n - 1 : 1;
     GCHK(hipMalloc(&d_child.p, 8ull * n_inner));
-    GCHK(hipMalloc(&d_range.p, 8ull * n_inner));
-    GCHK(hipMalloc(&d_pin.p, 4ull * n_inner));
-    GCHK(hipMalloc(&d_pleaf.p, 4ull * n_tris));
     GCHK(hipMalloc(&d_nbox.p, 24ull * n_inner));
-    GCHK(hipMalloc(&d_flags.p, 4ull * n_inner));
-    GCHK(hipMemsetAsync(d_flags.p, 0, 4ull * n_inner, st));
-    GCHK(hipMemsetAsync(d_pin.p, 0xFF, 4ull * n_inner, st));
-    if (n >= 2) {
-        hipLaunchKernelGGL(k_radix_tree, dim3(blocks_for(n - 1)), dim3(kB), 0, st, (const uint64_t *)d_keys2.p, n,
-                           (int2 *)d_child.p, (int2 *)d_range.p, (int *)d_pin.p, (int *)d_pleaf.p);
-        GCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_boxes, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const float *)d_tbox.p,
-                           (const uint32_t *)d_perm.p, n, (const int2 *)d_child.p, (const int *)d_pin.p,
-                           (const int *)d_pleaf.p, (float *)d_nbox.p, (int *)d_flags.p);
-        GCHK(hipGetLastError());
+    int root_bin = n >= 2 ? 0 : ~0;
+    if (ploc) {
+        GCHK(hipMalloc(&d_nsize.p, 4ull * n_inner));
+        if (n >= 2) {
+            const int e = ploc_tree((const float *)d_tbox.p, (const uint32_t *)d_perm.p, n, (int2 *)d_child.p,
+                                    (float *)d_nbox.p, (uint32_t *)d_nsize.p, st, prof, out.rounds, err);
+            if (e) return e;
+            root_bin = n - 2;
+        }
+    } else {
+        GCHK(hipMalloc(&d_range.p, 8ull * n_inner));
+        GCHK(hipMalloc(&d_pin.p, 4ull * n_inner));
+        GCHK(hipMalloc(&d_pleaf.p, 4ull * n_tris));
+        GCHK(hipMalloc(&d_flags.p, 4ull * n_inner));
+        GCHK(hipMemsetAsync(d_flags.p, 0, 4ull * n_inner, st));
+        GCHK(hipMemsetAsync(d_pin.p, 0xFF, 4ull * n_inner, st));
+        if (n >= 2) {
+            hipLaunchKernelGGL(k_radix_tree, dim3(blocks_for(n - 1)), dim3(kB), 0, st, (const uint64_t *)d_keys2.p, n,
+                               (int2 *)d_child.p, (int2 *)d_range.p, (int *)d_pin.p, (int *)d_pleaf.p);
+            GCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_boxes, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const float *)d_tbox.p,
+                               (const uint32_t *)d_perm.p, n, (const int2 *)d_child.p, (const int *)d_pin.p,
+                               (const int *)d_pleaf.p, (float *)d_nbox.p, (int *)d_flags.p);
+            GCHK(hipGetLastError());
+        }
     }
+    prof.lap(st, "tree");
 
     /* collapse: the 4-wide tree has fewer nodes than the binary tree has inner nodes */
     const uint64_t cap4 = n_inner + 1;
@@ -487,7 +761,7 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
     GCHK(hipMalloc(&d_perm2.p, 4ull * n_tris));
     /* counts: [0] frontier A size, [1] frontier B size, [2] nodes, [3] max stack,
        [4] triangle slots handed out, [5] quantisation failure flag */
-    const Frontier root = {n >= 2 ? 0 : ~0, 0, 0};
+    const Frontier root = {root_bin, 0, 0};
     GCHK(hipMemcpyAsync(d_front[0].p, &root, sizeof(root), hipMemcpyHostToDevice, st));
     const uint32_t init_counts[8] = {1u, 0u, 1u, 0u, 0u, 0u, 0u, 0u};
     GCHK(hipMemcpyAsync(d_counts.p, init_counts, sizeof(init_counts), hipMemcpyHostToDevice, st));
@@ -498,11 +772,11 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
     while (level_size > 0) {
         ++depth;
         GCHK(hipMemsetAsync(cnt + (1 - cur), 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_collapse, dim3(blocks_for(level_size)), dim3(kB), 0, st,
+        hipLaunchKernelGGL(ploc ? k_collapse<true> : k_collapse<false>, dim3(blocks_for(level_size)), dim3(kB), 0, st,
                            (const Frontier *)d_front[cur].p, cnt + cur, (Frontier *)d_front[1 - cur].p,
                            cnt + (1 - cur), cnt + 2, cnt + 3, (const int2 *)d_child.p, (const int2 *)d_range.p,
-                           (const float *)d_nbox.p, (const float *)d_tbox.p, (const uint32_t *)d_perm.p, n, nodes4,
-                           cnt + 4, (uint32_t *)d_perm2.p);
+                           (const uint32_t *)d_nsize.p, (const float *)d_nbox.p, (const float *)d_tbox.p,
+                           (const uint32_t *)d_perm.p, n, nodes4, cnt + 4, (uint32_t *)d_perm2.p);
         GCHK(hipGetLastError());
         GCHK(hipMemcpyAsync(&level_size, cnt + (1 - cur), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         uint32_t n_alloc = 0;
@@ -518,6 +792,7 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
     uint32_t counts[8];
     GCHK(hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, st));
     GCHK(hipStreamSynchronize(st));
+    prof.lap(st, "collapse");
     out.n_nodes4 = counts[2];
     out.depth4 = depth;
     out.stack4 = counts[3];
@@ -558,6 +833,8 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
         (void)hipFree(q4);
         out.nodes4q = nullptr;
     }
+    prof.lap(st, "records");
     out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    prof.write(n_tris, out.rounds, out.build_seconds);
     return 0;
 }

@@ -367,7 +367,7 @@ try {
 
 int rt_set_builder(rt_ctx *c, int builder)
 try {
-    if (!c || (builder != RT_BUILD_HOST && builder != RT_BUILD_GPU)) return RT_ERR_ARG;
+    if (!c || (builder != RT_BUILD_HOST && builder != RT_BUILD_GPU && builder != RT_BUILD_GPU_PLOC)) return RT_ERR_ARG;
     c->builder = builder;
     return RT_OK;
 } RT_CATCH(err_of(c))

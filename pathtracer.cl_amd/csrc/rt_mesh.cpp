@@ -88,10 +88,11 @@ static void drop_mesh(rt_ctx *c)
     c->n_tris = 0;
 }
 
-/* set_mesh_build with the GPU builder (rt_build_gpu.hip): one tree for every query, its arrays
-   made on the device and taken over here. */
+/* set_mesh_build with a GPU builder (rt_build_gpu.hip; `kind`: RT_BUILD_GPU or
+   RT_BUILD_GPU_PLOC): one tree for every query, its arrays made on the device and taken over
+   here. */
 static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                              bool dynamic)
+                              int kind, bool dynamic)
 {
     std::string err;
     if (!rt_validate_mesh(verts, n_verts, idx, n_tris, err)) return fail(c, RT_ERR_ARG, err);
@@ -99,7 +100,7 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
     RtGpuBvh g;
     bool det_cull = true;
     if (const char *v = getenv("RT_DET_CULL")) det_cull = atoi(v) != 0; /* A/B knob */
-    const int e = rt_build_bvh_gpu(verts, n_verts, idx, n_tris, g, err, c->stream, det_cull);
+    const int e = rt_build_bvh_gpu(verts, n_verts, idx, n_tris, g, err, c->stream, det_cull, kind == RT_BUILD_GPU_PLOC);
     c->d_nodes4.adopt(g.nodes4, 32ull * g.n_nodes4);
     c->d_nodes4q.adopt(g.nodes4q, (size_t)RT_QNODE_DWORDS * g.n_nodes4);
     c->d_tris.adopt(g.tris, 12ull * n_tris);
@@ -128,7 +129,7 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
         HIPCHK(c, hipMemcpy(hq.data(), g.nodes4q, hq.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         c->shadow_levels = tree_levels(hq.data(), g.n_nodes4, 0u);
     }
-    c->mesh_builder = RT_BUILD_GPU;
+    c->mesh_builder = kind;
     c->mesh_bounds_ok = mesh_bounds(verts, idx, n_tris, c->mesh_lo, c->mesh_hi);
     c->mesh_det_cull = det_cull;
     c->mesh_dynamic = dynamic;
@@ -142,7 +143,8 @@ static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const
 {
     std::string err;
     c->mesh_bounds_ok = false;
-    if (builder == RT_BUILD_GPU) return set_mesh_build_gpu(c, verts, n_verts, idx, n_tris, dynamic);
+    if (builder == RT_BUILD_GPU || builder == RT_BUILD_GPU_PLOC)
+        return set_mesh_build_gpu(c, verts, n_verts, idx, n_tris, builder, dynamic);
     /* Two host trees over the same triangles: the closest-hit queries (camera rays, bounces, the
        seed passes) walk one split by surface area, the shadow queries one whose cost area leans
        toward the scene's lights (rt_bvh.cpp Builder::area) — three quarters of the dragon frame's

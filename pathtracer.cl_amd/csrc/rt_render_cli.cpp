@@ -8,6 +8,8 @@
  *   rt_render [--scene main|ply] [--width W] [--height H] [--frames F]
  *             [--sample-rate S] [--depth D] [--mesh N_TRIS | --ply FILE] [--linear]
  *             [--raw out.f32] [--pfm out.pfm] [--device K]
+ *             [--builder host|gpu|ploc]   (the mesh's BVH builder, RayTracerHIP::setBuilder; default host.
+ *              Every builder gives the same frames)
  *             [--events d,d,l,d,m:5:-3,s:64:32,d,...]   (interactive replay: ProgressiveViewHIP
  *              display / arrow keys l r u n / drag motion / reshape, GlutCLWindow.cpp:136-301;
  *              one JSON line per event on stdout: the view state and whether a redisplay was
@@ -167,7 +169,7 @@ void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0
 int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
-                         "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--raw f] [--pfm f] "
+                         "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--builder host|gpu|ploc] [--raw f] [--pfm f] "
                          "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--sphere-carry [MAXHIST]] (--events o:I:DX:DY:DZ[:DR] moves sphere I) [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
@@ -260,6 +262,7 @@ int main(int argc, char **argv)
     int device = 0, comm_ranks = 0, comm_rank = 0;
     rt_tile tile{8, 1, 0};
     bool linear = false;
+    int builder = RT_BUILD_HOST;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -373,6 +376,12 @@ int main(int argc, char **argv)
         else if (a == "--depth") depth = (unsigned)std::atoi(v);
         else if (a == "--mesh") n_tris = (unsigned)std::atoi(v);
         else if (a == "--ply") ply_path = v;
+        else if (a == "--builder") {
+            if (!std::strcmp(v, "host")) builder = RT_BUILD_HOST;
+            else if (!std::strcmp(v, "gpu")) builder = RT_BUILD_GPU;
+            else if (!std::strcmp(v, "ploc")) builder = RT_BUILD_GPU_PLOC;
+            else return usage();
+        }
         else if (a == "--events") events = v;
         else if (a == "--poses") poses_path = v;
         else if (a == "--max-progression") max_prog = (unsigned)std::atoi(v);
@@ -481,6 +490,7 @@ int main(int argc, char **argv)
         if (ply) rt.setCameraSpherical(target, 40.0f, 105.0f, 5.0f); /* plymain.cpp:115-117 */
         else rt.setCameraSpherical(target, 14.0f, 118.0f, 5.0f);     /* main.cpp:127-128 */
         int kernel = RT_KERNEL_SPHERES;
+        rt.setBuilder(builder);
         uint32_t n_verts = 0; /* of the mesh (--poses) */
         if (!ply_path.empty()) { /* plymain.cpp:121, with the mesh actually handed to the tracer */
             rt.setMeshFromPly(ply_path.c_str());

@@ -109,8 +109,9 @@ class RayTracer:
         self._check(self._lib.rt_set_traversal(self._h, t), "rt_set_traversal")
 
     def setBuilder(self, builder: str) -> None:
-        """BVH builder for the next setMesh: "host" (binned SAH, default) or "gpu" (LBVH on the device)."""
-        b = {"host": _abi.RT_BUILD_HOST, "gpu": _abi.RT_BUILD_GPU}[builder]
+        """BVH builder for the next setMesh: "host" (binned SAH, default), "gpu" (LBVH on the device) or
+        "ploc" (PLOC on the device: slower to build than "gpu", trees that trace nearer the host build's)."""
+        b = {"host": _abi.RT_BUILD_HOST, "gpu": _abi.RT_BUILD_GPU, "ploc": _abi.RT_BUILD_GPU_PLOC}[builder]
         self._check(self._lib.rt_set_builder(self._h, b), "rt_set_builder")
 
     def setNDRange(self, nd_y: int) -> None:
