@@ -170,6 +170,15 @@ public:
     /* BVH builder for the next setMesh: RT_BUILD_HOST (binned SAH), RT_BUILD_GPU (LBVH) or
        RT_BUILD_GPU_PLOC (PLOC: device-built, merged by surface area). */
     void setBuilder(int builder) { check(rt_set_builder(ctx_, builder), "setBuilder"); }
+    /* Options of the device builders for the next setMesh (RT_BUILD_OPT_LIGHTS: never-hit
+       triangles left out, and a shadow tree split by what can occlude the lights). */
+    void setBuildOptions(uint32_t opts) { check(rt_set_build_options(ctx_, opts), "setBuildOptions"); }
+    uint32_t buildOptions() const
+    {
+        uint32_t o = 0;
+        check(rt_get_build_options(ctx_, &o), "buildOptions");
+        return o;
+    }
 
     /* plymain.cpp's PLYLoader (PLYLoader.cpp:4-90) with the mesh actually handed over:
        read a PLY file, optionally normalise it (extent 3, resting on y = -5, centred on

@@ -122,11 +122,13 @@ typedef struct rt_mesh_stats {
     uint32_t stack4;           /* worst-case traversal stack of the 4-wide tree */
     double build_seconds;
     uint32_t builder; /* RT_BUILD_HOST, RT_BUILD_GPU or RT_BUILD_GPU_PLOC */
-    uint32_t n_tris_tree; /* triangles in the tree: the host build leaves out those no ray can
-                             hit (|det| < 1e-4 for every unit direction, geometryFuncs.h:167) */
+    uint32_t n_tris_tree; /* triangles in the tree: the host build (and a device build with
+                             RT_BUILD_OPT_LIGHTS) leaves out those no ray can hit (|det| < 1e-4
+                             for every unit direction, geometryFuncs.h:167) */
     uint32_t n_nodes4_shadow; /* the shadow queries' 4-wide tree (host build with lights: its cost
                                  area leans toward them); 0: they walk the closest-hit tree */
-    uint32_t cone_root;   /* the lights' cone split of the shadow tree (host build, RT_LIGHT_CONE): the node
+    uint32_t cone_root;   /* the lights' cone split of the shadow tree (host build, or a device build with
+                             RT_BUILD_OPT_LIGHTS; RT_LIGHT_CONE): the node
                              of the subtree over the triangles that can occlude the lights it was built for —
                              the shadow queries start there while the lights and the tree stay as they were
                              (rt_render_info.shadow_start); 0: no split */
@@ -137,9 +139,24 @@ typedef struct rt_mesh_stats {
    milliseconds for large meshes, somewhat slower traversal), or the GPU PLOC build (the same
    sorted order, merged bottom-up by surface area in rounds of mutual nearest neighbours: a
    few times the LBVH's build time, trees nearer the host build's).  Both GPU builds make one
-   tree and keep every triangle.  Results are identical under all three. */
+   tree and keep every triangle unless rt_set_build_options says otherwise.  Results are
+   identical under all three. */
 enum { RT_BUILD_HOST = 0, RT_BUILD_GPU = 1, RT_BUILD_GPU_PLOC = 2 };
 int rt_set_builder(rt_ctx *ctx, int builder);
+/* Options of the device builders for the next rt_set_mesh (default 0: one tree over every
+   triangle).  RT_BUILD_OPT_LIGHTS: what the host build does around its trees, done on the
+   device — the triangles no unit ray can accept are left out (n_tris_tree), and the shadow
+   queries get a second tree (n_nodes4_shadow) whose root has exactly two children, A over the
+   triangles that can occlude the lights of the last rt_set_spheres (cone_root, n_tris_cone) and B
+   over the rest; without such a split (no lights, a part of at most one leaf, nodes the
+   compressed form cannot hold, rt_set_mesh_dynamic) the build makes one tree.  The host builder
+   ignores the options.  The mesh remembers them as it remembers its builder: a rebuild inside
+   rt_update_mesh uses the mesh's own, and after a refit of such a mesh the split is checked in
+   the new pose and kept while it still holds.  Culling only: no result bit depends on it.
+   Unknown bits: RT_ERR_ARG, the options stay as they were. */
+enum { RT_BUILD_OPT_LIGHTS = 1 };
+int rt_set_build_options(rt_ctx *ctx, uint32_t opts);
+int rt_get_build_options(const rt_ctx *ctx, uint32_t *opts);
 int rt_mesh_info(const rt_ctx *ctx, rt_mesh_stats *out);
 
 /* ---- a moving mesh: new positions for the vertices of the last rt_set_mesh (same count, same

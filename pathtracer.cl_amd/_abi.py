@@ -40,6 +40,7 @@ RT_TRAVERSAL_BVH4F = 4
 RT_BUILD_HOST = 0
 RT_BUILD_GPU = 1
 RT_BUILD_GPU_PLOC = 2
+RT_BUILD_OPT_LIGHTS = 1
 
 RT_MESH_VERTS_DEVICE = 1
 RT_MESH_UPDATE_REFIT = 1
@@ -260,6 +261,8 @@ SIGNATURES = {
     "rt_set_params": (_i32, [_vp, _u32, _u32]),
     "rt_set_traversal": (_i32, [_vp, _i32]),
     "rt_set_builder": (_i32, [_vp, _i32]),
+    "rt_set_build_options": (_i32, [_vp, _u32]),
+    "rt_get_build_options": (_i32, [_vp, ctypes.POINTER(_u32)]),
     "rt_set_ndrange": (_i32, [_vp, _u32]),
     "rt_set_seed_layout": (_i32, [_vp, _u32, _u32]),
     "rt_set_seeds": (_i32, [_vp, _vp, _sz]),

@@ -5,6 +5,11 @@
  * default traversal) and the leaf-ordered triangle records, from the mesh arrays of
  * raytrace_tris (tri_verts / tri_vert_idx, raytracer.cl:184-188).
  *
+ *   0. (RT_BUILD_OPT_LIGHTS) one class per triangle by the rules of
+ *      rt_tri_rules.h — left out, parked, possible occluder — and the triangle list in class
+ *      order by one prefix sum; steps 1-5 then run over a list: once over the kept triangles
+ *      (the closest-hit tree), and once each over the occluders (A) and the parked (B) for the
+ *      shadow tree, whose root has exactly these two children;
  *   1. per triangle: padded box (the host builder's pad: ext/512 + 1e-6(1+|coord|)) and
  *      centroid; centroid bounds by ordered-integer atomics;
  *   2. 63-bit Morton codes (21 bits per axis) of the centroids, radix-sorted (hipCUB)
@@ -41,6 +46,7 @@
 
 #include "rt_internal.h"
 #include "rt_quant.h"
+#include "rt_tri_rules.h"
 
 #pragma clang fp contract(off)
 
@@ -59,14 +65,16 @@ __device__ __forceinline__ float key2f(uint32_t k)
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-/* 1. padded triangle boxes + centroids; bounds[0..2] = min key, [3..5] = max key */
-__global__ void k_prep(const float *__restrict__ verts, const int32_t *__restrict__ idx, uint32_t n,
-                       float *__restrict__ tbox, float *__restrict__ cent, uint32_t *__restrict__ bounds)
+/* 1. padded triangle boxes + centroids (by triangle index); bounds[0..2] = min key, [3..5] = max key */
+__global__ void k_prep(const float *__restrict__ verts, const int32_t *__restrict__ idx,
+                       const uint32_t *__restrict__ sub, uint32_t n, float *__restrict__ tbox,
+                       float *__restrict__ cent, uint32_t *__restrict__ bounds)
 {
-    const uint32_t t = blockIdx.x * kB + threadIdx.x;
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
     float c[3] = {0, 0, 0};
-    bool ok = t < n;
+    bool ok = i < n;
     if (ok) {
+        const uint32_t t = sub ? sub[i] : i; /* a part of the mesh: the triangles its list names */
         float lo[3], hi[3], maxabs = 0.0f;
         for (int a = 0; a < 3; ++a) {
             lo[a] = INFINITY;
@@ -121,11 +129,12 @@ __device__ __forceinline__ uint64_t spread21(uint64_t v)
 }
 
 /* 2. Morton codes + identity payload */
-__global__ void k_morton(const float *__restrict__ cent, uint32_t n, const uint32_t *__restrict__ bounds,
-                         uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
+__global__ void k_morton(const float *__restrict__ cent, const uint32_t *__restrict__ sub, uint32_t n,
+                         const uint32_t *__restrict__ bounds, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
 {
-    const uint32_t t = blockIdx.x * kB + threadIdx.x;
-    if (t >= n) return;
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = sub ? sub[i] : i;
     uint64_t code = 0;
     for (int a = 0; a < 3; ++a) {
         const float lo = key2f(bounds[a]), hi = key2f(bounds[3 + a]);
@@ -135,8 +144,8 @@ __global__ void k_morton(const float *__restrict__ cent, uint32_t n, const uint3
         const uint64_t q = (uint64_t)fminf(u * 2097152.0f, 2097151.0f);
         code |= spread21(q) << (2 - a);
     }
-    keys[t] = code;
-    vals[t] = t;
+    keys[i] = code;
+    vals[i] = t;
 }
 
 /* 3. radix tree.  Inner node i in [0, n-2]; child c >= 0 inner, c < 0 leaf ~slot. */
@@ -471,7 +480,7 @@ __global__ void k_tri_records(const float *__restrict__ verts, const int32_t *__
 {
     const uint32_t s = blockIdx.x * kB + threadIdx.x;
     if (s >= n) return;
-    const uint32_t t = perm[perm2[s]];
+    const uint32_t t = perm[perm2 ? perm2[s] : s]; /* (no perm2: the list's own order, the left-out tail) */
     const float *a = verts + 3ull * (uint32_t)idx[3ull * t];
     const float *p1 = verts + 3ull * (uint32_t)idx[3ull * t + 1];
     const float *p2 = verts + 3ull * (uint32_t)idx[3ull * t + 2];
@@ -497,9 +506,10 @@ __global__ void k_tri_records(const float *__restrict__ verts, const int32_t *__
 struct NBox {
     double lo[3], hi[3], err;
 };
-__global__ void k_nbox(const float *__restrict__ nodes4, uint32_t first, uint32_t last, const float *__restrict__ tris,
-                       NBox *__restrict__ nb, uint32_t *__restrict__ q4)
+__global__ void k_nbox(const float *__restrict__ nodes4, uint32_t node_base, uint32_t first, uint32_t last,
+                       const float *__restrict__ tris, NBox *__restrict__ nb, uint32_t *__restrict__ q4)
 {
+    /* nodes4 holds the nodes from node_base on (the shadow tree's, numbered after the first tree's) */
     const uint32_t i = first + blockIdx.x * kB + threadIdx.x;
     if (i >= last) return;
     NBox b;
@@ -508,7 +518,7 @@ __global__ void k_nbox(const float *__restrict__ nodes4, uint32_t first, uint32_
         b.hi[a] = -__builtin_huge_val();
     }
     b.err = 0.0;
-    const float *f = nodes4 + 32ull * i;
+    const float *f = nodes4 + 32ull * (i - node_base);
     for (int k = 0; k < 4; ++k) {
         const int32_t c = __float_as_int(f[24 + k]);
         if (c == RT_EMPTY_CHILD) continue;
@@ -536,6 +546,99 @@ __global__ void k_nbox(const float *__restrict__ nodes4, uint32_t first, uint32_
     }
     nb[i] = b;
     rt_qnode_set_nbox(q4 + (uint64_t)RT_QNODE_DWORDS * i, b.lo, b.hi, b.err);
+}
+
+/* ---- RT_BUILD_OPT_LIGHTS: what the host build does around its trees ---- */
+
+/* 0a. one class byte per triangle by the rules of rt_tri_rules.h on the record's floats:
+   2 left out (never_hit), 1 parked (kept, never_occludes for every light), 0 a possible occluder */
+enum : uint8_t { kClsOccluder = 0, kClsParked = 1, kClsOut = 2 };
+__global__ void k_classify(const float *__restrict__ verts, const int32_t *__restrict__ idx, uint32_t n, int cull,
+                           const float *__restrict__ lights, uint32_t n_lights, uint8_t *__restrict__ cls)
+{
+    const uint32_t t = blockIdx.x * kB + threadIdx.x;
+    if (t >= n) return;
+    const float *a = verts + 3ull * (uint32_t)idx[3ull * t];
+    const float *p1 = verts + 3ull * (uint32_t)idx[3ull * t + 1];
+    const float *p2 = verts + 3ull * (uint32_t)idx[3ull * t + 2];
+    const float A[3] = {a[0], a[1], a[2]};
+    const float e1[3] = {p1[0] - A[0], p1[1] - A[1], p1[2] - A[2]};
+    const float e2[3] = {p2[0] - A[0], p2[1] - A[1], p2[2] - A[2]};
+    uint8_t c = kClsOccluder;
+    if (cull && never_hit_edges(e1, e2)) c = kClsOut;
+    else if (n_lights && never_occludes_edges(A, e1, e2, lights, n_lights)) c = kClsParked;
+    cls[t] = c;
+}
+
+/* 0b. flags[t] = occluder << 32 | parked (without a split the parked count as occluders): one
+   exclusive sum numbers both ranges, the left-out ones take what remains */
+__global__ void k_class_flags(const uint8_t *__restrict__ cls, uint32_t n, int split, uint64_t *__restrict__ flags)
+{
+    const uint32_t t = blockIdx.x * kB + threadIdx.x;
+    if (t >= n) return;
+    const uint8_t c = cls[t];
+    const bool parked = split && c == kClsParked;
+    flags[t] = ((uint64_t)(c != kClsOut && !parked) << 32) | (uint64_t)parked;
+}
+
+/* 0c. the stable compaction to the three slot ranges, in triangle order: the occluders in
+   [0, n0), the parked in [n0, n0 + n1), the left-out after them.  tot[0] = n0, tot[1] = n1. */
+__global__ void k_class_totals(const uint64_t *__restrict__ flags, const uint64_t *__restrict__ scan, uint32_t n,
+                               uint32_t *__restrict__ tot)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    const uint64_t s = scan[n - 1] + flags[n - 1];
+    tot[0] = (uint32_t)(s >> 32);
+    tot[1] = (uint32_t)s;
+}
+__global__ void k_class_scatter(const uint64_t *__restrict__ flags, const uint64_t *__restrict__ scan, uint32_t n,
+                                uint32_t n0, uint32_t n1, uint32_t *__restrict__ order)
+{
+    const uint32_t t = blockIdx.x * kB + threadIdx.x;
+    if (t >= n) return;
+    const uint64_t fl = flags[t], sc = scan[t];
+    const uint32_t s0 = (uint32_t)(sc >> 32), s1 = (uint32_t)sc;
+    uint32_t pos;
+    if (fl >> 32) pos = s0;
+    else if (fl & 1u) pos = n0 + s1;
+    else pos = n0 + n1 + (t - s0 - s1);
+    if (pos < n) order[pos] = t;
+}
+
+/* 5'. the shadow tree's root (node 0 of its array): exactly two children, A (node 1) then B
+   (node 2), each the root of its own binary tree */
+__global__ void k_cone_root(const float *__restrict__ box_a, const float *__restrict__ box_b, float *__restrict__ nd)
+{
+    const int k = threadIdx.x;
+    if (blockIdx.x || k >= 4) return;
+    const float *b = k == 0 ? box_a : box_b;
+    const bool used = k < 2;
+    nd[0 + k] = used ? b[0] : 0.0f;
+    nd[4 + k] = used ? b[3] : 0.0f;
+    nd[8 + k] = used ? b[1] : 0.0f;
+    nd[12 + k] = used ? b[4] : 0.0f;
+    nd[16 + k] = used ? b[2] : 0.0f;
+    nd[20 + k] = used ? b[5] : 0.0f;
+    nd[24 + k] = __int_as_float(used ? k + 1 : RT_EMPTY_CHILD);
+    nd[28 + k] = 0.0f;
+}
+
+/* 5''. the shadow tree's links in the numbering of both trees: its nodes follow the first
+   tree's n_a, its records the first tree's n_tris (rt_mesh.cpp, the host build's layout) */
+__global__ void k_shadow_links(float *__restrict__ nodes4, uint32_t n_nodes, uint32_t n_a, uint32_t n_tris)
+{
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    if (j >= 4u * n_nodes) return;
+    float *w = nodes4 + 32ull * (j >> 2) + 24 + (j & 3u);
+    int32_t code = __float_as_int(*w);
+    if (code == RT_EMPTY_CHILD) return;
+    if (code >= 0) {
+        code += (int32_t)n_a;
+    } else {
+        const uint32_t enc = (uint32_t)(~code);
+        code = ~(int32_t)((((enc >> 3) + n_tris) << 3) | (enc & 7u));
+    }
+    *w = __int_as_float(code);
 }
 
 unsigned blocks_for(uint64_t n) { return (unsigned)((n + kB - 1) / kB); }
@@ -680,14 +783,170 @@ static int ploc_tree(const float *tbox, const uint32_t *perm, int n, int2 *child
     return 0;
 }
 
+
+namespace {
+
+/* Steps 1-4 (or 3'-4') over the m triangles a list names (sub; nullptr: triangles 0 .. m - 1):
+   the sorted order (perm: slot -> triangle) and the binary tree, everything the collapse reads.
+   tbox / cent are per triangle of the mesh, written here for the list's. */
+struct BinTree {
+    DevBuf bounds, keys, keys2, vals, perm, tmp, child, range, pin, pleaf, nbox, flags, nsize;
+    int m = 0, root = 0; /* root: the binary root (~0: the single triangle of m == 1) */
+};
+
+int build_binary(const float *verts, const int32_t *idx, const uint32_t *sub, int m, float *tbox, float *cent,
+                 bool ploc, hipStream_t st, BuildProfile &prof, uint32_t &rounds, BinTree &T, std::string &err)
+{
+    T.m = m;
+    GCHK(hipMalloc(&T.bounds.p, 6 * sizeof(uint32_t)));
+    const uint32_t init_bounds[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
+    GCHK(hipMemcpyAsync(T.bounds.p, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_prep, dim3(blocks_for(m)), dim3(kB), 0, st, verts, idx, sub, (uint32_t)m, tbox, cent,
+                       (uint32_t *)T.bounds.p);
+    GCHK(hipGetLastError());
+
+    GCHK(hipMalloc(&T.keys.p, 8ull * m));
+    GCHK(hipMalloc(&T.keys2.p, 8ull * m));
+    GCHK(hipMalloc(&T.vals.p, 4ull * m));
+    GCHK(hipMalloc(&T.perm.p, 4ull * m));
+    hipLaunchKernelGGL(k_morton, dim3(blocks_for(m)), dim3(kB), 0, st, (const float *)cent, sub, (uint32_t)m,
+                       (const uint32_t *)T.bounds.p, (uint64_t *)T.keys.p, (uint32_t *)T.vals.p);
+    GCHK(hipGetLastError());
+    size_t tmp_bytes = 0;
+    GCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (uint64_t *)T.keys.p, (uint64_t *)T.keys2.p,
+                                            (uint32_t *)T.vals.p, (uint32_t *)T.perm.p, m, 0, 63, st));
+    GCHK(hipMalloc(&T.tmp.p, tmp_bytes));
+    GCHK(hipcub::DeviceRadixSort::SortPairs(T.tmp.p, tmp_bytes, (uint64_t *)T.keys.p, (uint64_t *)T.keys2.p,
+                                            (uint32_t *)T.vals.p, (uint32_t *)T.perm.p, m, 0, 63, st));
+
+    prof.lap(st, "sort");
+    const uint64_t n_inner = m >= 2 ? (uint64_t)m - 1 : 1;
+    GCHK(hipMalloc(&T.child.p, 8ull * n_inner));
+    GCHK(hipMalloc(&T.nbox.p, 24ull * n_inner));
+    T.root = m >= 2 ? 0 : ~0;
+    if (ploc) {
+        GCHK(hipMalloc(&T.nsize.p, 4ull * n_inner));
+        if (m >= 2) {
+            const int e = ploc_tree((const float *)tbox, (const uint32_t *)T.perm.p, m, (int2 *)T.child.p,
+                                    (float *)T.nbox.p, (uint32_t *)T.nsize.p, st, prof, rounds, err);
+            if (e) return e;
+            T.root = m - 2;
+        }
+    } else {
+        GCHK(hipMalloc(&T.range.p, 8ull * n_inner));
+        GCHK(hipMalloc(&T.pin.p, 4ull * n_inner));
+        GCHK(hipMalloc(&T.pleaf.p, 4ull * m));
+        GCHK(hipMalloc(&T.flags.p, 4ull * n_inner));
+        GCHK(hipMemsetAsync(T.flags.p, 0, 4ull * n_inner, st));
+        GCHK(hipMemsetAsync(T.pin.p, 0xFF, 4ull * n_inner, st));
+        if (m >= 2) {
+            hipLaunchKernelGGL(k_radix_tree, dim3(blocks_for(m - 1)), dim3(kB), 0, st, (const uint64_t *)T.keys2.p, m,
+                               (int2 *)T.child.p, (int2 *)T.range.p, (int *)T.pin.p, (int *)T.pleaf.p);
+            GCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_boxes, dim3(blocks_for(m)), dim3(kB), 0, st, (const float *)tbox,
+                               (const uint32_t *)T.perm.p, m, (const int2 *)T.child.p, (const int *)T.pin.p,
+                               (const int *)T.pleaf.p, (float *)T.nbox.p, (int *)T.flags.p);
+            GCHK(hipGetLastError());
+        }
+    }
+    prof.lap(st, "tree");
+    return 0;
+}
+
+/* Step 5 over one binary tree (its root becomes node 0), or over the cone split's two: A's root
+   is node 1 and B's node 2 under the root k_cone_root wrote, the nodes of both are handed out
+   from one counter, and every level is one launch for A's frontier and then one for B's, so a
+   level of the whole tree is an index range in which A's nodes come before B's (what
+   rt_mesh.cpp's tree_levels and the refit read off the links).  A part's leaves take record
+   slots from its own counter, from tri_base[p] on.
+   cnt, 16 words: [2] nodes, [3] max stack, [5] the quantisation failure flag (k_quantize);
+   per part p at 8 p: [0] [1] its two frontiers' sizes, [4] record slots handed out.
+   d_front: the parts' frontier buffers, the caller's (freed with the build's other scratch, after
+   build_seconds is taken, as before). */
+struct Collapsed {
+    uint32_t n_nodes = 0, depth = 0, stack = 0;
+    uint32_t tri_end[2] = {0u, 0u};
+    std::vector<uint32_t> level_end; /* node ids of level L: [level_end[L-1], level_end[L]) */
+};
+
+int collapse(BinTree *const *parts, int n_parts, const uint32_t *tri_base, bool ploc, const float *tbox, float *nodes4,
+             uint32_t *perm2, uint32_t *cnt, DevBuf (*d_front)[2], hipStream_t st, Collapsed &out, std::string &err)
+{
+    const bool two = n_parts == 2;
+    uint32_t init_counts[16] = {0u};
+    init_counts[2] = two ? 3u : 1u;
+    init_counts[3] = two ? 1u : 0u; /* the root's other child waits on the stack */
+    for (int p = 0; p < n_parts; ++p) {
+        const uint64_t cap4 = (parts[p]->m >= 2 ? (uint64_t)parts[p]->m - 1 : 1) + 1;
+        GCHK(hipMalloc(&d_front[p][0].p, sizeof(Frontier) * cap4));
+        GCHK(hipMalloc(&d_front[p][1].p, sizeof(Frontier) * cap4));
+        const Frontier root = {parts[p]->root, two ? p + 1 : 0, two ? 1 : 0};
+        GCHK(hipMemcpyAsync(d_front[p][0].p, &root, sizeof(root), hipMemcpyHostToDevice, st));
+        init_counts[8 * p + 0] = 1u;
+        init_counts[8 * p + 4] = tri_base[p];
+    }
+    GCHK(hipMemcpyAsync(cnt, init_counts, sizeof(init_counts), hipMemcpyHostToDevice, st));
+    uint32_t level_size[2] = {1u, two ? 1u : 0u}, depth = 0;
+    int cur = 0;
+    out.level_end.assign(1, 1u);
+    if (two) out.level_end.push_back(3u);
+    while (level_size[0] > 0 || level_size[1] > 0) {
+        ++depth;
+        uint32_t n_alloc = 0;
+        for (int p = 0; p < n_parts; ++p) {
+            if (!level_size[p]) continue;
+            const BinTree &T = *parts[p];
+            uint32_t *c = cnt + 8 * p;
+            GCHK(hipMemsetAsync(c + (1 - cur), 0, sizeof(uint32_t), st));
+            hipLaunchKernelGGL(ploc ? k_collapse<true> : k_collapse<false>, dim3(blocks_for(level_size[p])), dim3(kB), 0,
+                               st, (const Frontier *)d_front[p][cur].p, c + cur, (Frontier *)d_front[p][1 - cur].p,
+                               c + (1 - cur), cnt + 2, cnt + 3, (const int2 *)T.child.p, (const int2 *)T.range.p,
+                               (const uint32_t *)T.nsize.p, (const float *)T.nbox.p, tbox, (const uint32_t *)T.perm.p,
+                               T.m, nodes4, c + 4, perm2);
+            GCHK(hipGetLastError());
+            GCHK(hipMemcpyAsync(&level_size[p], c + (1 - cur), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        GCHK(hipMemcpyAsync(&n_alloc, cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        GCHK(hipStreamSynchronize(st));
+        if (level_size[0] > 0 || level_size[1] > 0) out.level_end.push_back(n_alloc);
+        cur = 1 - cur;
+        if (depth > 4096) {
+            err = "GPU BVH collapse did not terminate";
+            return -1;
+        }
+    }
+    uint32_t counts[16];
+    GCHK(hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, st));
+    GCHK(hipStreamSynchronize(st));
+    out.n_nodes = counts[2];
+    out.depth = depth;
+    out.stack = counts[3];
+    for (int p = 0; p < n_parts; ++p) out.tri_end[p] = counts[8 * p + 4];
+    return 0;
+}
+
+/* Step 6c for the nodes [base, base + n_nodes) whose full-precision form is nodes4 */
+int nbox_levels(const float *nodes4, uint32_t base, const std::vector<uint32_t> &level_end, const float *tris, NBox *nb,
+                uint32_t *q4, hipStream_t st, std::string &err)
+{
+    for (size_t L = level_end.size(); L-- > 0;) {
+        const uint32_t a = base + (L ? level_end[L - 1] : 0u), b = base + level_end[L];
+        if (b <= a) continue;
+        hipLaunchKernelGGL(k_nbox, dim3(blocks_for(b - a)), dim3(kB), 0, st, nodes4, base, a, b, tris, nb, q4);
+        GCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+} // namespace
+
 int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_h, uint32_t n_tris, RtGpuBvh &out,
-                     std::string &err, void *stream, bool det_cull, bool ploc)
+                     std::string &err, void *stream, bool det_cull, bool ploc, const RtGpuBuildLights *lights)
 {
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = (hipStream_t)stream;
-    const int n = (int)n_tris;
-    DevBuf d_verts, d_idx, d_tbox, d_cent, d_bounds, d_keys, d_keys2, d_vals, d_perm, d_child, d_range, d_pin,
-        d_pleaf, d_nbox, d_flags, d_front[2], d_counts, d_tmp, d_perm2, d_nsize;
+    DevBuf d_verts, d_idx, d_tbox, d_cent, d_counts, d_perm2, d_cls, d_cflags, d_cscan, d_ctmp, d_order, d_tot,
+        d_lights, d_nodes4s, d_perm2s, d_front[1][2], d_front_s[2][2];
     BuildProfile prof(ploc);
     prof.begin(st);
     GCHK(hipMalloc(&d_verts.p, 12ull * n_verts));
@@ -696,139 +955,195 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
     GCHK(hipMemcpyAsync(d_idx.p, idx_h, 12ull * n_tris, hipMemcpyHostToDevice, st));
     GCHK(hipMalloc(&d_tbox.p, 24ull * n_tris));
     GCHK(hipMalloc(&d_cent.p, 12ull * n_tris));
-    GCHK(hipMalloc(&d_bounds.p, 6 * sizeof(uint32_t)));
-    const uint32_t init_bounds[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    GCHK(hipMemcpyAsync(d_bounds.p, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_prep, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const float *)d_verts.p,
-                       (const int32_t *)d_idx.p, n_tris, (float *)d_tbox.p, (float *)d_cent.p,
-                       (uint32_t *)d_bounds.p);
-    GCHK(hipGetLastError());
+    const float *verts = (const float *)d_verts.p;
+    const int32_t *idx = (const int32_t *)d_idx.p;
 
-    GCHK(hipMalloc(&d_keys.p, 8ull * n_tris));
-    GCHK(hipMalloc(&d_keys2.p, 8ull * n_tris));
-    GCHK(hipMalloc(&d_vals.p, 4ull * n_tris));
-    GCHK(hipMalloc(&d_perm.p, 4ull * n_tris));
-    hipLaunchKernelGGL(k_morton, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const float *)d_cent.p, n_tris,
-                       (const uint32_t *)d_bounds.p, (uint64_t *)d_keys.p, (uint32_t *)d_vals.p);
-    GCHK(hipGetLastError());
-    size_t tmp_bytes = 0;
-    GCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (uint64_t *)d_keys.p, (uint64_t *)d_keys2.p,
-                                            (uint32_t *)d_vals.p, (uint32_t *)d_perm.p, n, 0, 63, st));
-    GCHK(hipMalloc(&d_tmp.p, tmp_bytes));
-    GCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, (uint64_t *)d_keys.p, (uint64_t *)d_keys2.p,
-                                            (uint32_t *)d_vals.p, (uint32_t *)d_perm.p, n, 0, 63, st));
-
-    prof.lap(st, "sort");
-    const uint64_t n_inner = n >= 2 ? (uint64_t)n - 1 : 1;
-    GCHK(hipMalloc(&d_child.p, 8ull * n_inner));
-    GCHK(hipMalloc(&d_nbox.p, 24ull * n_inner));
-    int root_bin = n >= 2 ? 0 : ~0;
-    if (ploc) {
-        GCHK(hipMalloc(&d_nsize.p, 4ull * n_inner));
-        if (n >= 2) {
-            const int e = ploc_tree((const float *)d_tbox.p, (const uint32_t *)d_perm.p, n, (int2 *)d_child.p,
-                                    (float *)d_nbox.p, (uint32_t *)d_nsize.p, st, prof, out.rounds, err);
-            if (e) return e;
-            root_bin = n - 2;
+    /* RT_BUILD_OPT_LIGHTS: the classes, and the triangles in class order (d_order): the possible
+       occluders [0, n0), the parked [n0, n_hit), the left-out after them */
+    const bool opt = lights && lights->cull;
+    uint32_t n_hit = n_tris, n0 = 0, n1 = 0;
+    bool split = false;
+    if (opt) {
+        const uint32_t n_lights = lights->lights ? lights->n_lights : 0u;
+        if (n_lights) {
+            GCHK(hipMalloc(&d_lights.p, 16ull * n_lights));
+            GCHK(hipMemcpyAsync(d_lights.p, lights->lights, 16ull * n_lights, hipMemcpyHostToDevice, st));
         }
-    } else {
-        GCHK(hipMalloc(&d_range.p, 8ull * n_inner));
-        GCHK(hipMalloc(&d_pin.p, 4ull * n_inner));
-        GCHK(hipMalloc(&d_pleaf.p, 4ull * n_tris));
-        GCHK(hipMalloc(&d_flags.p, 4ull * n_inner));
-        GCHK(hipMemsetAsync(d_flags.p, 0, 4ull * n_inner, st));
-        GCHK(hipMemsetAsync(d_pin.p, 0xFF, 4ull * n_inner, st));
-        if (n >= 2) {
-            hipLaunchKernelGGL(k_radix_tree, dim3(blocks_for(n - 1)), dim3(kB), 0, st, (const uint64_t *)d_keys2.p, n,
-                               (int2 *)d_child.p, (int2 *)d_range.p, (int *)d_pin.p, (int *)d_pleaf.p);
+        GCHK(hipMalloc(&d_cls.p, n_tris));
+        GCHK(hipMalloc(&d_cflags.p, 8ull * n_tris));
+        GCHK(hipMalloc(&d_cscan.p, 8ull * n_tris));
+        GCHK(hipMalloc(&d_order.p, 4ull * n_tris));
+        GCHK(hipMalloc(&d_tot.p, 2 * sizeof(uint32_t)));
+        size_t tmp_bytes = 0;
+        GCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint64_t *)d_cflags.p, (uint64_t *)d_cscan.p,
+                                              (int)n_tris, st));
+        GCHK(hipMalloc(&d_ctmp.p, tmp_bytes ? tmp_bytes : 1));
+        hipLaunchKernelGGL(k_classify, dim3(blocks_for(n_tris)), dim3(kB), 0, st, verts, idx, n_tris, 1,
+                           (const float *)d_lights.p, n_lights, (uint8_t *)d_cls.p);
+        GCHK(hipGetLastError());
+        uint32_t tot[2] = {0u, 0u};
+        auto number = [&](int with_split) -> int { /* flags, their sum, the totals */
+            hipLaunchKernelGGL(k_class_flags, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const uint8_t *)d_cls.p,
+                               n_tris, with_split, (uint64_t *)d_cflags.p);
             GCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_boxes, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const float *)d_tbox.p,
-                               (const uint32_t *)d_perm.p, n, (const int2 *)d_child.p, (const int *)d_pin.p,
-                               (const int *)d_pleaf.p, (float *)d_nbox.p, (int *)d_flags.p);
+            size_t tb = tmp_bytes;
+            GCHK(hipcub::DeviceScan::ExclusiveSum(d_ctmp.p, tb, (const uint64_t *)d_cflags.p, (uint64_t *)d_cscan.p,
+                                                  (int)n_tris, st));
+            hipLaunchKernelGGL(k_class_totals, dim3(1), dim3(64), 0, st, (const uint64_t *)d_cflags.p,
+                               (const uint64_t *)d_cscan.p, n_tris, (uint32_t *)d_tot.p);
             GCHK(hipGetLastError());
+            GCHK(hipMemcpyAsync(tot, d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+            GCHK(hipStreamSynchronize(st));
+            return 0;
+        };
+        if (int e = number(1)) return e;
+        if (tot[0] + tot[1] == 0) { /* nothing hittable: triangle 0 stays, the tree is never empty */
+            GCHK(hipMemsetAsync(d_cls.p, kClsOccluder, 1, st));
+            if (int e = number(1)) return e;
         }
+        /* the host build's conditions for the split (rt_bvh.cpp, rt_mesh.cpp) */
+        split = n_lights > 0 && tot[0] > kLeafMax && tot[1] > kLeafMax && 2ull * n_tris < (1ull << 28);
+        if (!split && tot[1])
+            if (int e = number(0)) return e;
+        n0 = tot[0];
+        n1 = tot[1];
+        n_hit = n0 + n1;
+        if (n_hit < 1 || n_hit > n_tris) {
+            err = "GPU BVH build: class counts";
+            return -1;
+        }
+        hipLaunchKernelGGL(k_class_scatter, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const uint64_t *)d_cflags.p,
+                           (const uint64_t *)d_cscan.p, n_tris, n0, n1, (uint32_t *)d_order.p);
+        GCHK(hipGetLastError());
+        prof.lap(st, "classify");
     }
-    prof.lap(st, "tree");
+    const uint32_t *order = (const uint32_t *)d_order.p;
+
+    BinTree all;
+    if (int e = build_binary(verts, idx, order, (int)n_hit, (float *)d_tbox.p, (float *)d_cent.p, ploc, st, prof,
+                             out.rounds, all, err))
+        return e;
 
     /* collapse: the 4-wide tree has fewer nodes than the binary tree has inner nodes */
-    const uint64_t cap4 = n_inner + 1;
+    const uint64_t cap4 = (n_hit >= 2 ? (uint64_t)n_hit - 1 : 1) + 1;
     float *nodes4 = nullptr;
     GCHK(hipMalloc(&nodes4, 128ull * cap4));
     out.nodes4 = nodes4;
-    GCHK(hipMalloc(&d_front[0].p, sizeof(Frontier) * cap4));
-    GCHK(hipMalloc(&d_front[1].p, sizeof(Frontier) * cap4));
-    GCHK(hipMalloc(&d_counts.p, 8 * sizeof(uint32_t)));
-    GCHK(hipMalloc(&d_perm2.p, 4ull * n_tris));
-    /* counts: [0] frontier A size, [1] frontier B size, [2] nodes, [3] max stack,
-       [4] triangle slots handed out, [5] quantisation failure flag */
-    const Frontier root = {root_bin, 0, 0};
-    GCHK(hipMemcpyAsync(d_front[0].p, &root, sizeof(root), hipMemcpyHostToDevice, st));
-    const uint32_t init_counts[8] = {1u, 0u, 1u, 0u, 0u, 0u, 0u, 0u};
-    GCHK(hipMemcpyAsync(d_counts.p, init_counts, sizeof(init_counts), hipMemcpyHostToDevice, st));
+    GCHK(hipMalloc(&d_counts.p, 16 * sizeof(uint32_t)));
+    GCHK(hipMalloc(&d_perm2.p, 4ull * n_hit));
     uint32_t *cnt = (uint32_t *)d_counts.p;
-    uint32_t level_size = 1, depth = 0;
-    int cur = 0;
-    std::vector<uint32_t> level_end{1}; /* node ids of level L: [level_end[L-1], level_end[L]) */
-    while (level_size > 0) {
-        ++depth;
-        GCHK(hipMemsetAsync(cnt + (1 - cur), 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(ploc ? k_collapse<true> : k_collapse<false>, dim3(blocks_for(level_size)), dim3(kB), 0, st,
-                           (const Frontier *)d_front[cur].p, cnt + cur, (Frontier *)d_front[1 - cur].p,
-                           cnt + (1 - cur), cnt + 2, cnt + 3, (const int2 *)d_child.p, (const int2 *)d_range.p,
-                           (const uint32_t *)d_nsize.p, (const float *)d_nbox.p, (const float *)d_tbox.p,
-                           (const uint32_t *)d_perm.p, n, nodes4, cnt + 4, (uint32_t *)d_perm2.p);
-        GCHK(hipGetLastError());
-        GCHK(hipMemcpyAsync(&level_size, cnt + (1 - cur), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        uint32_t n_alloc = 0;
-        GCHK(hipMemcpyAsync(&n_alloc, cnt + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        GCHK(hipStreamSynchronize(st));
-        if (level_size > 0) level_end.push_back(n_alloc);
-        cur = 1 - cur;
-        if (depth > 4096) {
-            err = "GPU BVH collapse did not terminate";
-            return -1;
-        }
+    Collapsed ca, cs;
+    {
+        BinTree *parts[1] = {&all};
+        const uint32_t base[1] = {0u};
+        if (int e = collapse(parts, 1, base, ploc, (const float *)d_tbox.p, nodes4, (uint32_t *)d_perm2.p, cnt, d_front,
+                             st, ca, err))
+            return e;
     }
-    uint32_t counts[8];
-    GCHK(hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
     prof.lap(st, "collapse");
-    out.n_nodes4 = counts[2];
-    out.depth4 = depth;
-    out.stack4 = counts[3];
-
-    if (counts[4] != n_tris) {
+    out.n_nodes4 = ca.n_nodes;
+    out.depth4 = ca.depth;
+    out.stack4 = out.stack4_all = ca.stack;
+    out.n_hit = n_hit;
+    if (ca.tri_end[0] != n_hit) {
         err = "GPU BVH collapse lost triangles";
         return -1;
     }
+
+    /* the shadow queries' tree: A over the possible occluders, B over the parked, each built
+       as the first tree was over its own slots, never merged across */
+    BinTree ta, tb;
+    if (split) {
+        uint32_t rounds = 0;
+        if (int e = build_binary(verts, idx, order, (int)n0, (float *)d_tbox.p, (float *)d_cent.p, ploc, st, prof, rounds,
+                                 ta, err))
+            return e;
+        if (int e = build_binary(verts, idx, order + n0, (int)n1, (float *)d_tbox.p, (float *)d_cent.p, ploc, st, prof,
+                                 rounds, tb, err))
+            return e;
+        GCHK(hipMalloc(&d_nodes4s.p, 128ull * ((uint64_t)n0 + n1 + 1)));
+        GCHK(hipMalloc(&d_perm2s.p, 4ull * n_hit));
+        hipLaunchKernelGGL(k_cone_root, dim3(1), dim3(64), 0, st, (const float *)ta.nbox.p + 6ull * ta.root,
+                           (const float *)tb.nbox.p + 6ull * tb.root, (float *)d_nodes4s.p);
+        GCHK(hipGetLastError());
+        BinTree *parts[2] = {&ta, &tb};
+        const uint32_t base[2] = {0u, n0};
+        if (int e = collapse(parts, 2, base, ploc, (const float *)d_tbox.p, (float *)d_nodes4s.p, (uint32_t *)d_perm2s.p,
+                             cnt, d_front_s, st, cs, err))
+            return e;
+        prof.lap(st, "collapse");
+        if (cs.tri_end[0] != n0 || cs.tri_end[1] != n_hit) {
+            err = "GPU BVH collapse lost triangles (shadow tree)";
+            return -1;
+        }
+        hipLaunchKernelGGL(k_shadow_links, dim3(blocks_for(4ull * cs.n_nodes)), dim3(kB), 0, st, (float *)d_nodes4s.p,
+                           cs.n_nodes, out.n_nodes4, n_tris);
+        GCHK(hipGetLastError());
+        out.n_nodes4_shadow = cs.n_nodes;
+        out.n_cone = n0;
+        out.stack4_all = std::max(ca.stack, cs.stack);
+    }
+    const uint32_t n_a = out.n_nodes4, n_s = out.n_nodes4_shadow;
+
     uint32_t *q4 = nullptr;
-    GCHK(hipMalloc(&q4, 4ull * RT_QNODE_DWORDS * out.n_nodes4));
+    GCHK(hipMalloc(&q4, 4ull * RT_QNODE_DWORDS * ((uint64_t)n_a + n_s)));
     out.nodes4q = q4;
-    hipLaunchKernelGGL(k_quantize, dim3(blocks_for(out.n_nodes4)), dim3(kB), 0, st, (const float *)nodes4,
-                       out.n_nodes4, q4, cnt + 5);
+    GCHK(hipMemsetAsync(cnt + 5, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_quantize, dim3(blocks_for(n_a)), dim3(kB), 0, st, (const float *)nodes4, n_a, q4, cnt + 5);
     GCHK(hipGetLastError());
     float *tris = nullptr;
-    GCHK(hipMalloc(&tris, 48ull * n_tris));
+    GCHK(hipMalloc(&tris, 48ull * n_tris * (split ? 2u : 1u)));
     out.tris = tris;
-    hipLaunchKernelGGL(k_tri_records, dim3(blocks_for(n_tris)), dim3(kB), 0, st, (const float *)d_verts.p,
-                       (const int32_t *)d_idx.p, (const uint32_t *)d_perm.p, (const uint32_t *)d_perm2.p, n_tris,
-                       tris);
+    hipLaunchKernelGGL(k_tri_records, dim3(blocks_for(n_hit)), dim3(kB), 0, st, verts, idx, (const uint32_t *)all.perm.p,
+                       (const uint32_t *)d_perm2.p, n_hit, tris);
     GCHK(hipGetLastError());
-    if (det_cull) {
-        DevBuf d_nb;
-        GCHK(hipMalloc(&d_nb.p, sizeof(NBox) * out.n_nodes4));
-        for (size_t L = level_end.size(); L-- > 0;) {
-            const uint32_t a = L ? level_end[L - 1] : 0u, b = level_end[L];
-            if (b <= a) continue;
-            hipLaunchKernelGGL(k_nbox, dim3(blocks_for(b - a)), dim3(kB), 0, st, (const float *)nodes4, a, b,
-                               (const float *)tris, (NBox *)d_nb.p, q4);
+    if (n_hit < n_tris) { /* the left-out triangles' records, in triangle order, for the linear traversal */
+        hipLaunchKernelGGL(k_tri_records, dim3(blocks_for(n_tris - n_hit)), dim3(kB), 0, st, verts, idx, order + n_hit,
+                           (const uint32_t *)nullptr, n_tris - n_hit, tris + 12ull * n_hit);
+        GCHK(hipGetLastError());
+    }
+    if (split) {
+        float *ts = tris + 12ull * n_tris;
+        const uint32_t *p2 = (const uint32_t *)d_perm2s.p;
+        hipLaunchKernelGGL(k_quantize, dim3(blocks_for(n_s)), dim3(kB), 0, st, (const float *)d_nodes4s.p, n_s,
+                           q4 + (uint64_t)RT_QNODE_DWORDS * n_a, cnt + 5);
+        GCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_tri_records, dim3(blocks_for(n0)), dim3(kB), 0, st, verts, idx, (const uint32_t *)ta.perm.p,
+                           p2, n0, ts);
+        GCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_tri_records, dim3(blocks_for(n1)), dim3(kB), 0, st, verts, idx, (const uint32_t *)tb.perm.p,
+                           p2 + n0, n1, ts + 12ull * n0);
+        GCHK(hipGetLastError());
+        if (n_hit < n_tris) {
+            hipLaunchKernelGGL(k_tri_records, dim3(blocks_for(n_tris - n_hit)), dim3(kB), 0, st, verts, idx,
+                               order + n_hit, (const uint32_t *)nullptr, n_tris - n_hit, ts + 12ull * n_hit);
             GCHK(hipGetLastError());
         }
+    }
+    if (det_cull) {
+        DevBuf d_nb;
+        GCHK(hipMalloc(&d_nb.p, sizeof(NBox) * ((uint64_t)n_a + n_s)));
+        if (int e = nbox_levels(nodes4, 0u, ca.level_end, tris, (NBox *)d_nb.p, q4, st, err)) return e;
+        if (split)
+            if (int e = nbox_levels((const float *)d_nodes4s.p, n_a, cs.level_end, tris, (NBox *)d_nb.p, q4, st, err))
+                return e;
         GCHK(hipStreamSynchronize(st));
     }
     uint32_t qfail = 0;
     GCHK(hipMemcpyAsync(&qfail, cnt + 5, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GCHK(hipStreamSynchronize(st));
+    if (qfail && split) {
+        /* the shadow tree lives in compressed nodes alone: without them the build without the split */
+        (void)hipFree(nodes4);
+        (void)hipFree(q4);
+        (void)hipFree(tris);
+        out = RtGpuBvh();
+        RtGpuBuildLights plain = *lights;
+        plain.n_lights = 0;
+        const int e = rt_build_bvh_gpu(verts_h, n_verts, idx_h, n_tris, out, err, stream, det_cull, ploc, &plain);
+        out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return e;
+    }
     if (qfail) { /* not encodable: full-precision nodes only */
         (void)hipFree(q4);
         out.nodes4q = nullptr;

@@ -135,7 +135,8 @@ struct rt_ctx {
     /* the lights' cone split of the shadow tree (rt_bvh.cpp never_occludes): subtree A's node in
        d_nodes4q (0: none), its triangles, its own levels, and the bits of the (centre, radius) of
        every light the split was made for, 4 words each.  The shadow queries start at A while every
-       current light is one of those and the tree is as built (cone_stale: refitted since); else at
+       current light is one of those and the split holds for the records (cone_stale: refitted since —
+       a device build with RT_BUILD_OPT_LIGHTS checks the new pose instead, k_refit_cone); else at
        shadow_root (tri_scene) */
     uint32_t cone_root = 0, n_cone = 0;
     std::vector<std::pair<uint32_t, uint32_t>> cone_levels;
@@ -206,6 +207,8 @@ struct rt_ctx {
     size_t info_list_px = 0;        /* pixels of the render the pending list counts belong to */
     int builder = RT_BUILD_HOST;      /* builder for the next rt_set_mesh */
     int mesh_builder = RT_BUILD_HOST; /* builder of the current mesh */
+    uint32_t build_opts = 0;          /* RT_BUILD_OPT_* for the next rt_set_mesh (the device builders) */
+    uint32_t mesh_build_opts = 0;     /* ... of the current mesh: a rebuild in rt_update_mesh uses these */
     uint64_t mesh_serial = 0;
     /* the moving mesh (rt_update_mesh, rt_refit.hip): the indices of the last rt_set_mesh, on the
        host for a rebuild and on the device for the refit; how that mesh was built; the refit's
@@ -230,6 +233,7 @@ struct rt_ctx {
         DevBuf<uint8_t> d_nbox;         /* binary64 normal-box bounds per node (rt_refit_nbox_bytes each) */
         DevBuf<uint32_t> d_res;         /* RT_REFIT_RES_WORDS */
         DevBuf<double> d_part;          /* RT_REFIT_AREA_BLOCKS partial area sums */
+        DevBuf<float> d_cone_lights;    /* the lights a device build's cone split was made for (k_refit_cone) */
         DevBuf<RtRefitStep> d_steps;
         std::vector<RtRefitStep> steps; /* deepest level first */
         double area0 = 0.0;             /* the build's own area sum */

@@ -372,6 +372,21 @@ try {
     return RT_OK;
 } RT_CATCH(err_of(c))
 
+int rt_set_build_options(rt_ctx *c, uint32_t opts)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (opts & ~(uint32_t)RT_BUILD_OPT_LIGHTS) return fail(c, RT_ERR_ARG, "rt_set_build_options: unknown option bits");
+    c->build_opts = opts;
+    return RT_OK;
+} RT_CATCH(err_of(c))
+
+int rt_get_build_options(const rt_ctx *c, uint32_t *opts)
+try {
+    if (!c || !opts) return RT_ERR_ARG;
+    *opts = c->build_opts;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
 int rt_set_traversal(rt_ctx *c, int t)
 try {
     if (!c || !(t == RT_TRAVERSAL_BVH || t == RT_TRAVERSAL_LINEAR || t == RT_TRAVERSAL_BVH4F)) return RT_ERR_ARG;

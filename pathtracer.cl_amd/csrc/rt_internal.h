@@ -132,9 +132,24 @@ struct RtGpuBvh {
     uint32_t n_nodes4 = 0, depth4 = 0, stack4 = 0;
     uint32_t rounds = 0; /* PLOC: merge rounds */
     double build_seconds = 0.0;
+    /* with RtGpuBuildLights (else n_hit = n_tris and the rest 0): the triangles in the trees (record
+       slots [0, n_hit), the left-out ones after them); the shadow tree's nodes, which follow the
+       closest-hit tree's in nodes4q alone (links offset by n_nodes4, its n_tris records after the
+       first tree's, leaf codes offset), its root's two children A (node n_nodes4 + 1, over the
+       slots [0, n_cone) of its records) and B; the stack of the deeper of the two trees */
+    uint32_t n_hit = 0, n_nodes4_shadow = 0, n_cone = 0, stack4_all = 0;
+};
+/* RT_BUILD_OPT_LIGHTS for the device builders: leave the never_hit triangles out (cull), and with
+   lights (centre, radius: 4 floats each; n_lights 0: no split) give the shadow queries a tree of
+   their own whose root keeps the possible occluders (A) and the rest (B) apart. */
+struct RtGpuBuildLights {
+    bool cull = false;
+    const float *lights = nullptr;
+    uint32_t n_lights = 0;
 };
 int rt_build_bvh_gpu(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, RtGpuBvh &out,
-                     std::string &err, void *stream, bool det_cull = true, bool ploc = false);
+                     std::string &err, void *stream, bool det_cull = true, bool ploc = false,
+                     const RtGpuBuildLights *lights = nullptr);
 /* Input checks shared by both builders (finite coordinates, indices in range, size limit). */
 bool rt_validate_mesh(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, std::string &err);
 
@@ -151,7 +166,8 @@ enum {
     RT_REFIT_RES_QFAIL = 3,
     RT_REFIT_RES_LO = 4,
     RT_REFIT_RES_HI = 7,
-    RT_REFIT_RES_WORDS = 10
+    RT_REFIT_RES_CONE = 10, /* parked triangles (subtree B) a shadow query could now accept (k_refit_cone) */
+    RT_REFIT_RES_WORDS = 11
 };
 #define RT_REFIT_AREA_BLOCKS 256 /* partial sums of k_refit_area */
 /* the nodes of one depth of both trees (index ranges in the compressed nodes' numbering) */
@@ -182,6 +198,11 @@ int rt_launch_refit_levels(const RtRefitLaunch &a, const RtRefitStep *steps_dev,
                            uint32_t n_steps, void *stream);
 /* part: RT_REFIT_AREA_BLOCKS doubles, to be added in index order */
 int rt_launch_refit_area(const float *nodes4, uint32_t n_nodes4, double *part, void *stream);
+/* the cone split in the new pose: never_occludes over the records [first, first + count) (subtree
+   B's, in the shadow tree's half) for the lights (centre, radius: 4 floats each), counted into
+   res[RT_REFIT_RES_CONE] */
+int rt_launch_refit_cone(const float *tris, uint32_t first, uint32_t count, const float *lights, uint32_t n_lights,
+                         uint32_t *res, void *stream);
 size_t rt_refit_nbox_bytes(void);
 
 /* ---- the render kernels' launch structs and launchers (rt_tris.hip, rt_split.hip, rt_spheres.hip,

@@ -89,10 +89,14 @@ static void drop_mesh(rt_ctx *c)
 }
 
 /* set_mesh_build with a GPU builder (rt_build_gpu.hip; `kind`: RT_BUILD_GPU or
-   RT_BUILD_GPU_PLOC): one tree for every query, its arrays made on the device and taken over
-   here. */
+   RT_BUILD_GPU_PLOC): one tree over every triangle for every query, its arrays made on the
+   device and taken over here.  With RT_BUILD_OPT_LIGHTS (`opts`) the device build does what the
+   host build below does around its trees, under the same knobs: the never_hit triangles left out
+   (RT_CULL_UNHITTABLE, not in dynamic mode), and a shadow tree after the first whose root keeps
+   the lights' possible occluders (A) and the rest (B) apart (RT_LIGHT_CONE), in the host
+   build's layout; without a split, one tree. */
 static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                              int kind, bool dynamic)
+                              int kind, bool dynamic, uint32_t opts)
 {
     std::string err;
     if (!rt_validate_mesh(verts, n_verts, idx, n_tris, err)) return fail(c, RT_ERR_ARG, err);
@@ -100,10 +104,29 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
     RtGpuBvh g;
     bool det_cull = true;
     if (const char *v = getenv("RT_DET_CULL")) det_cull = atoi(v) != 0; /* A/B knob */
-    const int e = rt_build_bvh_gpu(verts, n_verts, idx, n_tris, g, err, c->stream, det_cull, kind == RT_BUILD_GPU_PLOC);
+    RtGpuBuildLights bl;
+    std::vector<float> lights;
+    if (opts & RT_BUILD_OPT_LIGHTS) {
+        bl.cull = true;
+        if (const char *v = getenv("RT_CULL_UNHITTABLE")) bl.cull = atoi(v) != 0; /* A/B knob */
+        if (dynamic) bl.cull = false; /* rt_set_mesh_dynamic: every later update can refit */
+        bool cone = kLightCone;
+        if (const char *v = getenv("RT_LIGHT_CONE")) cone = atoi(v) != 0; /* A/B knob */
+        if (cone && bl.cull)
+            for (const rt_sphere &L : c->lights) {
+                const float w[4] = {L.center.x, L.center.y, L.center.z, L.radius};
+                lights.insert(lights.end(), w, w + 4);
+            }
+        bl.lights = lights.data();
+        bl.n_lights = (uint32_t)(lights.size() / 4);
+    }
+    const int e = rt_build_bvh_gpu(verts, n_verts, idx, n_tris, g, err, c->stream, det_cull, kind == RT_BUILD_GPU_PLOC,
+                                   bl.cull ? &bl : nullptr);
+    const bool two = !e && g.n_nodes4_shadow > 0 && g.nodes4q;
+    const uint32_t n_all = g.n_nodes4 + (two ? g.n_nodes4_shadow : 0u);
     c->d_nodes4.adopt(g.nodes4, 32ull * g.n_nodes4);
-    c->d_nodes4q.adopt(g.nodes4q, (size_t)RT_QNODE_DWORDS * g.n_nodes4);
-    c->d_tris.adopt(g.tris, 12ull * n_tris);
+    c->d_nodes4q.adopt(g.nodes4q, (size_t)RT_QNODE_DWORDS * n_all);
+    c->d_tris.adopt(g.tris, 12ull * n_tris * (two ? 2u : 1u));
     if (e) return fail(c, RT_ERR_HIP, "GPU BVH build: " + err);
     c->n_tris = n_tris;
     c->mesh_serial++;
@@ -114,37 +137,48 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
     c->bvh.depth4 = g.depth4;
     c->bvh.stack4 = g.stack4;
     c->bvh.build_seconds = g.build_seconds;
-    c->bvh.n_hit = n_tris; /* the GPU build keeps every triangle */
-    c->tree_recs = n_tris; /* one tree for every query */
-    c->shadow_root = 0;
-    c->n_nodes4_shadow = 0;
-    c->stack4_all = g.stack4;
-    c->cone_root = c->n_cone = 0; /* (the GPU build has no cone split) */
+    c->bvh.n_hit = bl.cull ? g.n_hit : n_tris; /* (without the option the GPU build keeps every triangle) */
+    c->tree_recs = (size_t)n_tris * (two ? 2u : 1u);
+    c->shadow_root = two ? g.n_nodes4 : 0u;
+    c->n_nodes4_shadow = two ? g.n_nodes4_shadow : 0u;
+    c->stack4_all = two ? g.stack4_all : g.stack4;
+    c->cone_root = two ? g.n_nodes4 + 1u : 0u; /* A: the shadow root's first child */
+    c->n_cone = two ? g.n_cone : 0u;
     c->cone_levels.clear();
     c->cone_lights.clear();
     c->cone_stale = false;
     c->shadow_levels.clear();
-    if (c->shadow_cache && g.nodes4q) { /* the one tree's levels, read from its links */
-        std::vector<uint32_t> hq((size_t)RT_QNODE_DWORDS * g.n_nodes4);
+    if ((two || c->shadow_cache) && g.nodes4q) { /* the levels of the shadow queries' tree, read from its links */
+        std::vector<uint32_t> hq((size_t)RT_QNODE_DWORDS * n_all);
         HIPCHK(c, hipMemcpy(hq.data(), g.nodes4q, hq.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        c->shadow_levels = tree_levels(hq.data(), g.n_nodes4, 0u);
+        c->shadow_levels = tree_levels(hq.data(), n_all, c->shadow_root);
+        if (two) {
+            c->cone_levels = tree_levels(hq.data(), n_all, c->cone_root, false);
+            for (float w : lights) {
+                uint32_t bits;
+                memcpy(&bits, &w, sizeof(bits));
+                c->cone_lights.push_back(bits);
+            }
+        }
     }
     c->mesh_builder = kind;
+    c->mesh_build_opts = opts;
     c->mesh_bounds_ok = mesh_bounds(verts, idx, n_tris, c->mesh_lo, c->mesh_hi);
     c->mesh_det_cull = det_cull;
     c->mesh_dynamic = dynamic;
     return RT_OK;
 }
 
-/* The build and the upload of rt_set_mesh (and of rt_update_mesh's rebuild): `builder` and
-   `dynamic` are the context's choices for the next mesh, or the current mesh's own. */
+/* The build and the upload of rt_set_mesh (and of rt_update_mesh's rebuild): `builder`, `dynamic`
+   and `opts` (RT_BUILD_OPT_*: the device builders') are the context's choices for the next mesh,
+   or the current mesh's own. */
 static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                          int builder, bool dynamic)
+                          int builder, bool dynamic, uint32_t opts)
 {
     std::string err;
     c->mesh_bounds_ok = false;
     if (builder == RT_BUILD_GPU || builder == RT_BUILD_GPU_PLOC)
-        return set_mesh_build_gpu(c, verts, n_verts, idx, n_tris, builder, dynamic);
+        return set_mesh_build_gpu(c, verts, n_verts, idx, n_tris, builder, dynamic, opts);
     /* Two host trees over the same triangles: the closest-hit queries (camera rays, bounces, the
        seed passes) walk one split by surface area, the shadow queries one whose cost area leans
        toward the scene's lights (rt_bvh.cpp Builder::area) — three quarters of the dragon frame's
@@ -218,6 +252,7 @@ static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const
         tr.insert(tr.end(), sb.tris.begin(), sb.tris.end());
     }
     c->mesh_builder = RT_BUILD_HOST;
+    c->mesh_build_opts = 0; /* (the host build does all of it anyway) */
     drop_mesh(c);
     HIPCHK(c, c->d_nodes4.reserve(b.nodes4.size()));
     if (!q4.empty()) HIPCHK(c, c->d_nodes4q.reserve(q4.size()));
@@ -301,6 +336,11 @@ static int refit_prepare(rt_ctx *c)
     HIPCHK(c, r.d_nbox.reserve(rt_refit_nbox_bytes() * n_all));
     HIPCHK(c, r.d_res.reserve(RT_REFIT_RES_WORDS));
     HIPCHK(c, r.d_part.reserve(RT_REFIT_AREA_BLOCKS));
+    if (c->cone_root && c->mesh_builder != RT_BUILD_HOST && !c->cone_lights.empty()) { /* k_refit_cone's lights */
+        HIPCHK(c, r.d_cone_lights.reserve(c->cone_lights.size()));
+        HIPCHK(c, hipMemcpy(r.d_cone_lights, c->cone_lights.data(), c->cone_lights.size() * sizeof(uint32_t),
+                            hipMemcpyHostToDevice));
+    }
     HIPCHK(c, r.ev0.create());
     HIPCHK(c, r.ev1.create());
     r.ready = true;
@@ -310,11 +350,11 @@ static int refit_prepare(rt_ctx *c)
 /* rt_set_mesh, and rt_update_mesh's rebuild: the build, then what a later update needs of this
    mesh — its indices on the host and on the device. */
 static int set_mesh_keep(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                         int builder, bool dynamic)
+                         int builder, bool dynamic, uint32_t opts)
 {
     c->refit = rt_ctx::Refit(); /* the refit's workspace: gone with the mesh it was sized for */
     c->have_update = false;
-    const int st = set_mesh_build(c, verts, n_verts, idx, n_tris, builder, dynamic);
+    const int st = set_mesh_build(c, verts, n_verts, idx, n_tris, builder, dynamic, opts);
     if (st != RT_OK) return st;
     if (idx != c->h_idx.data()) c->h_idx.assign(idx, idx + 3ull * n_tris);
     c->n_verts = n_verts;
@@ -331,7 +371,7 @@ int rt_set_mesh(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *
 try {
     if (!c || !verts || !idx || !n_verts || !n_tris) return fail(c, RT_ERR_ARG, "empty mesh");
     HIPCHK(c, hipSetDevice(c->device));
-    return set_mesh_keep(c, verts, n_verts, idx, n_tris, c->builder, c->dynamic);
+    return set_mesh_keep(c, verts, n_verts, idx, n_tris, c->builder, c->dynamic, c->build_opts);
 } RT_CATCH(err_of(c))
 
 int rt_set_mesh_dynamic(rt_ctx *c, int on)
@@ -361,7 +401,8 @@ static int update_rebuild(rt_ctx *c, const float *verts, int flags, uint32_t rea
     }
     const std::vector<int32_t> idx = std::move(c->h_idx);
     c->h_idx.clear();
-    const int st = set_mesh_keep(c, verts, c->n_verts, idx.data(), c->n_tris, c->mesh_builder, c->mesh_dynamic);
+    const int st = set_mesh_keep(c, verts, c->n_verts, idx.data(), c->n_tris, c->mesh_builder, c->mesh_dynamic,
+                                 c->mesh_build_opts);
     if (st != RT_OK) return st;
     c->last_update = {RT_MESH_UPDATE_REBUILT, reason, newly, 0u, 1.0f, 0.0f};
     c->have_update = true;
@@ -384,7 +425,7 @@ try {
     }
     hipStream_t st = c->stream;
     const uint32_t n_tris = c->n_tris, n_hit = c->bvh.n_hit, n_a = c->bvh.n_nodes4;
-    uint32_t res[RT_REFIT_RES_WORDS] = {0u, 0u, 0u, 0u, ~0u, ~0u, ~0u, 0u, 0u, 0u};
+    uint32_t res[RT_REFIT_RES_WORDS] = {0u, 0u, 0u, 0u, ~0u, ~0u, ~0u, 0u, 0u, 0u, 0u};
     HIPCHK(c, hipMemcpyAsync(r.d_verts, verts, 12ull * n_verts,
                              (flags & RT_MESH_VERTS_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(r.d_res, res, sizeof(res), hipMemcpyHostToDevice, st));
@@ -429,12 +470,21 @@ try {
     double now = 0.0;
     if (int e = rt_launch_refit_area(c->d_nodes4, n_a, r.d_part, st))
         return hip_fail(c, (hipError_t)e, "k_refit_area");
+    /* a device build's cone split (RT_BUILD_OPT_LIGHTS): does every parked triangle (B's records,
+       slots [n_cone, n_hit) of the shadow tree's half) still never occlude the lights it was made for? */
+    const bool recheck_cone = c->cone_root && r.d_cone_lights && c->n_cone < n_hit; /* (the rule reads this pose alone) */
+    if (recheck_cone)
+        if (int e = rt_launch_refit_cone(c->d_tris, n_tris + c->n_cone, n_hit - c->n_cone, r.d_cone_lights,
+                                         (uint32_t)(c->cone_lights.size() / 4), r.d_res, st))
+            return hip_fail(c, (hipError_t)e, "k_refit_cone");
     HIPCHK(c, hipEventRecord(r.ev1, st));
     HIPCHK(c, hipMemcpyAsync(res, r.d_res, sizeof(res), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(part, r.d_part, sizeof(part), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     c->mesh_serial++; /* the records have changed: the schedule, the lists and the pilot are the old mesh's */
-    c->cone_stale = true; /* and the cone split was made for the old ones: the whole shadow tree from here on */
+    /* and the cone split was made for the old ones: the whole shadow tree from here on, unless the
+       check above found that it still holds (A's triangles that stopped occluding cost time only) */
+    c->cone_stale = !(recheck_cone && res[RT_REFIT_RES_CONE] == 0u);
     if (res[RT_REFIT_RES_BAD]) return fail(c, RT_ERR_STATE, "rt_update_mesh: a link of the tree is out of range");
     /* the compressed form holds every node, or none: a change either way is a rebuild (the
        half-written nodes are replaced with everything else) */

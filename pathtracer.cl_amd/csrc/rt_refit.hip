@@ -9,13 +9,15 @@
  * encoders of rt_quant.h depend only on the full-precision node and the records.  So
  *
  *   k_refit_check    looks before anything is written: finite coordinates, the triangles the
- *                    host builder left out still never_hit (rt_bvh.cpp, the same binary64
- *                    expression), and the bounds of the referenced vertices;
+ *                    builder left out still never_hit (rt_bvh.cpp's binary64 expression,
+ *                    rt_tri_rules.h), and the bounds of the referenced vertices;
  *   k_refit_records  rewrites every record slot of both trees' halves and the slot's padded box;
  *   k_refit_levels   rewrites the nodes, deepest level first: the full-precision node (the
  *                    closest-hit tree's in place, the shadow tree's in a workspace: the device
  *                    keeps that tree compressed only), rt_quantize_node4, the normal box;
- *   k_refit_area     sums the closest-hit tree's child half-areas (the quality signal).
+ *   k_refit_area     sums the closest-hit tree's child half-areas (the quality signal);
+ *   k_refit_cone     (a device build's cone split) asks whether every parked
+ *                    triangle still never occludes the lights the split was made for.
  *
  * The traversal and k_tris are not touched: a refitted tree is a tree check_tree accepts.
  */
@@ -25,6 +27,7 @@
 
 #include "rt_internal.h"
 #include "rt_quant.h"
+#include "rt_tri_rules.h"
 
 #pragma clang fp contract(off)
 
@@ -36,26 +39,6 @@ __device__ __forceinline__ uint32_t f2key(float f)
 {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-/* rt_bvh.cpp never_hit, term for term: from a record's float edges, or from the vertices */
-__device__ __forceinline__ bool never_hit_edges(const float *e1, const float *e2)
-{
-    const double cx = (double)e2[1] * e1[2] - (double)e2[2] * e1[1];
-    const double cy = (double)e2[2] * e1[0] - (double)e2[0] * e1[2];
-    const double cz = (double)e2[0] * e1[1] - (double)e2[1] * e1[0];
-    const double cr = sqrt(cx * cx + cy * cy + cz * cz);
-    const double n1 = fabs((double)e1[0]) + fabs((double)e1[1]) + fabs((double)e1[2]);
-    const double n2 = fabs((double)e2[0]) + fabs((double)e2[1]) + fabs((double)e2[2]);
-    const double u = 1.0 / 16777216.0;
-    const double bound = 1.001 * (cr + 16.0 * u * n1 * n2);
-    return bound < 0.999 * (double)1e-4f;
-}
-__device__ __forceinline__ bool never_hit(const float *a, const float *p1, const float *p2)
-{
-    const float e1[3] = {p1[0] - a[0], p1[1] - a[1], p1[2] - a[2]};
-    const float e2[3] = {p2[0] - a[0], p2[1] - a[1], p2[2] - a[2]};
-    return never_hit_edges(e1, e2);
 }
 
 /* per-wave sum of a small count, one atomic per wave */
@@ -315,9 +298,35 @@ __global__ void k_refit_area(const float *__restrict__ nodes4, uint32_t n_nodes,
     if (threadIdx.x == 0) part[blockIdx.x] = s_sum[0];
 }
 
+/* The cone split after a refit: the records of subtree B (slots [first, first + count) of the
+   shadow tree's half, as k_refit_records just wrote them) against the lights the split was
+   made for.  One parked triangle that a shadow query could now accept and the split no longer
+   holds: res[RT_REFIT_RES_CONE] counts them. */
+__global__ void k_refit_cone(const float *__restrict__ tris, uint32_t first, uint32_t count,
+                             const float *__restrict__ lights, uint32_t n_lights, uint32_t *__restrict__ res)
+{
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    uint32_t can = 0;
+    if (j < count) {
+        const float *o = tris + 12ull * (first + j);
+        const float a[3] = {o[0], o[1], o[2]}, e1[3] = {o[4], o[5], o[6]}, e2[3] = {o[8], o[9], o[10]};
+        can = never_occludes_edges(a, e1, e2, lights, n_lights) ? 0u : 1u;
+    }
+    wave_add(&res[RT_REFIT_RES_CONE], can);
+}
+
 unsigned blocks_for(uint64_t n) { return (unsigned)((n + kB - 1) / kB); }
 
 } // namespace
+
+int rt_launch_refit_cone(const float *tris, uint32_t first, uint32_t count, const float *lights, uint32_t n_lights,
+                         uint32_t *res, void *stream)
+{
+    if (!count) return 0;
+    hipLaunchKernelGGL(k_refit_cone, dim3(blocks_for(count)), dim3(kB), 0, (hipStream_t)stream, tris, first, count,
+                       lights, n_lights, res);
+    return (int)hipGetLastError();
+}
 
 int rt_launch_refit_check(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, const float *tris,
                           uint32_t n_hit, uint32_t *res, void *stream)

@@ -10,6 +10,8 @@
  *             [--raw out.f32] [--pfm out.pfm] [--device K]
  *             [--builder host|gpu|ploc]   (the mesh's BVH builder, RayTracerHIP::setBuilder; default host.
  *              Every builder gives the same frames)
+ *             [--build-lights]   (with --builder gpu|ploc: RT_BUILD_OPT_LIGHTS, the never-hit triangles left
+ *              out and the shadow tree split by what can occlude the lights; the same frames again)
  *             [--events d,d,l,d,m:5:-3,s:64:32,d,...]   (interactive replay: ProgressiveViewHIP
  *              display / arrow keys l r u n / drag motion / reshape, GlutCLWindow.cpp:136-301;
  *              one JSON line per event on stdout: the view state and whether a redisplay was
@@ -169,7 +171,7 @@ void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0
 int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
-                         "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--builder host|gpu|ploc] [--raw f] [--pfm f] "
+                         "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--builder host|gpu|ploc] [--build-lights] [--raw f] [--pfm f] "
                          "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--sphere-carry [MAXHIST]] (--events o:I:DX:DY:DZ[:DR] moves sphere I) [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
@@ -263,12 +265,17 @@ int main(int argc, char **argv)
     rt_tile tile{8, 1, 0};
     bool linear = false;
     int builder = RT_BUILD_HOST;
+    bool build_lights = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
         const char *v = nullptr;
         if (a == "--linear") {
             linear = true;
+            continue;
+        }
+        if (a == "--build-lights") {
+            build_lights = true;
             continue;
         }
         if (a == "--adaptive-history") {
@@ -491,6 +498,7 @@ int main(int argc, char **argv)
         else rt.setCameraSpherical(target, 14.0f, 118.0f, 5.0f);     /* main.cpp:127-128 */
         int kernel = RT_KERNEL_SPHERES;
         rt.setBuilder(builder);
+        rt.setBuildOptions(build_lights ? RT_BUILD_OPT_LIGHTS : 0u);
         uint32_t n_verts = 0; /* of the mesh (--poses) */
         if (!ply_path.empty()) { /* plymain.cpp:121, with the mesh actually handed to the tracer */
             rt.setMeshFromPly(ply_path.c_str());

@@ -114,6 +114,18 @@ class RayTracer:
         b = {"host": _abi.RT_BUILD_HOST, "gpu": _abi.RT_BUILD_GPU, "ploc": _abi.RT_BUILD_GPU_PLOC}[builder]
         self._check(self._lib.rt_set_builder(self._h, b), "rt_set_builder")
 
+    def setBuildOptions(self, lights: bool) -> None:
+        """Options of the device builders ("gpu", "ploc") for the next setMesh. lights: leave the never-hit
+        triangles out and give the shadow queries a second tree, split by what can occlude the lights of the
+        last setSpheres (as the host build does). Off by default; the host builder ignores it."""
+        o = _abi.RT_BUILD_OPT_LIGHTS if lights else 0
+        self._check(self._lib.rt_set_build_options(self._h, o), "rt_set_build_options")
+
+    def getBuildOptions(self) -> int:
+        o = ctypes.c_uint32(0)
+        self._check(self._lib.rt_get_build_options(self._h, ctypes.byref(o)), "rt_get_build_options")
+        return int(o.value)
+
     def setNDRange(self, nd_y: int) -> None:
         """Work-group height of the reference launch (fixes the padded seed height)."""
         self._check(self._lib.rt_set_ndrange(self._h, int(nd_y)), "rt_set_ndrange")
