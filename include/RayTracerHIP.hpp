@@ -179,6 +179,15 @@ public:
         check(rt_get_build_options(ctx_, &o), "buildOptions");
         return o;
     }
+    /* How the device builders collapse their binary tree for the next setMesh: RT_COLLAPSE_GREEDY
+       (default) or RT_COLLAPSE_SAH (the host build's rule). */
+    void setCollapse(int mode) { check(rt_set_collapse(ctx_, mode), "setCollapse"); }
+    int collapse() const
+    {
+        int m = RT_COLLAPSE_GREEDY;
+        check(rt_get_collapse(ctx_, &m), "collapse");
+        return m;
+    }
 
     /* plymain.cpp's PLYLoader (PLYLoader.cpp:4-90) with the mesh actually handed over:
        read a PLY file, optionally normalise it (extent 3, resting on y = -5, centred on

@@ -133,6 +133,8 @@ typedef struct rt_mesh_stats {
                              the shadow queries start there while the lights and the tree stay as they were
                              (rt_render_info.shadow_start); 0: no split */
     uint32_t n_tris_cone; /* that subtree's triangles */
+    uint32_t collapse;    /* RT_COLLAPSE_*: how the binary tree became the 4-wide one (a host build:
+                             RT_COLLAPSE_SAH) */
 } rt_mesh_stats;
 /* BVH builder used by the next rt_set_mesh: the host binned-SAH build (default: the best
    trees), the GPU build (LBVH over Morton codes, collapsed on the device: seconds-to-
@@ -157,6 +159,18 @@ int rt_set_builder(rt_ctx *ctx, int builder);
 enum { RT_BUILD_OPT_LIGHTS = 1 };
 int rt_set_build_options(rt_ctx *ctx, uint32_t opts);
 int rt_get_build_options(const rt_ctx *ctx, uint32_t *opts);
+/* How the device builders collapse their binary tree to the 4-wide one, for the next rt_set_mesh.
+   RT_COLLAPSE_GREEDY (default): the inner child of largest area is expanded until there are four,
+   and every subtree of at most 4 triangles becomes one leaf.  RT_COLLAPSE_SAH: the host build's
+   rule — by dynamic programming over the binary tree every node becomes a leaf, a wide node of
+   its own or is dissolved into its parent's children, whichever costs fewer area-weighted
+   traversal steps: more and smaller nodes, a stack a few entries deeper.  The
+   host builder ignores the mode; the mesh remembers it as it remembers its builder (a rebuild
+   inside rt_update_mesh uses the mesh's own; rt_mesh_stats.collapse).  Culling only: no result
+   bit depends on it.  Any other value: RT_ERR_ARG, the mode stays as it was. */
+enum { RT_COLLAPSE_GREEDY = 0, RT_COLLAPSE_SAH = 1 };
+int rt_set_collapse(rt_ctx *ctx, int mode);
+int rt_get_collapse(const rt_ctx *ctx, int *mode);
 int rt_mesh_info(const rt_ctx *ctx, rt_mesh_stats *out);
 
 /* ---- a moving mesh: new positions for the vertices of the last rt_set_mesh (same count, same

@@ -41,6 +41,8 @@ RT_BUILD_HOST = 0
 RT_BUILD_GPU = 1
 RT_BUILD_GPU_PLOC = 2
 RT_BUILD_OPT_LIGHTS = 1
+RT_COLLAPSE_GREEDY = 0
+RT_COLLAPSE_SAH = 1
 
 RT_MESH_VERTS_DEVICE = 1
 RT_MESH_UPDATE_REFIT = 1
@@ -123,7 +125,8 @@ class RtMeshStats(ctypes.Structure):
     _fields_ = [("n_tris", ctypes.c_uint32), ("n_nodes2", ctypes.c_uint32), ("depth2", ctypes.c_uint32),
                 ("n_nodes4", ctypes.c_uint32), ("depth4", ctypes.c_uint32), ("stack4", ctypes.c_uint32),
                 ("build_seconds", ctypes.c_double), ("builder", ctypes.c_uint32), ("n_tris_tree", ctypes.c_uint32),
-                ("n_nodes4_shadow", ctypes.c_uint32), ("cone_root", ctypes.c_uint32), ("n_tris_cone", ctypes.c_uint32)]
+                ("n_nodes4_shadow", ctypes.c_uint32), ("cone_root", ctypes.c_uint32), ("n_tris_cone", ctypes.c_uint32),
+                ("collapse", ctypes.c_uint32)]
 
 
 class RtMeshUpdateInfo(ctypes.Structure):
@@ -263,6 +266,8 @@ SIGNATURES = {
     "rt_set_builder": (_i32, [_vp, _i32]),
     "rt_set_build_options": (_i32, [_vp, _u32]),
     "rt_get_build_options": (_i32, [_vp, ctypes.POINTER(_u32)]),
+    "rt_set_collapse": (_i32, [_vp, _i32]),
+    "rt_get_collapse": (_i32, [_vp, ctypes.POINTER(_i32)]),
     "rt_set_ndrange": (_i32, [_vp, _u32]),
     "rt_set_seed_layout": (_i32, [_vp, _u32, _u32]),
     "rt_set_seeds": (_i32, [_vp, _vp, _sz]),

@@ -26,6 +26,10 @@
  *      expanded first, as the host collapse; a subtree of <= kLeafMax triangles becomes a
  *      leaf over its slot range, or over its gathered slots under PLOC), nodes numbered
  *      breadth-first (root 0);
+ *   5a-5b. (RT_COLLAPSE_SAH, instead of 5's rule) the host collapse's dynamic
+ *      programming: bottom-up per binary node the cost of standing for 1..4 children of a wide
+ *      node, as a leaf, a node of its own or dissolved into its parent's; top-down the same
+ *      launches per level with the children the costs chose;
  *   6. quantisation of every node (same rounding rule as rt_bvh.cpp) and the triangle
  *      records in slot order, e1/e2 formed by the reference's get_triangle subtraction.
  *
@@ -463,6 +467,216 @@ __global__ void k_collapse(const Frontier *__restrict__ cur, const uint32_t *__r
     }
 }
 
+/* ---- RT_COLLAPSE_SAH: the collapse by dynamic programming, as the host's ----
+   Per binary node c, D[c][j] (j = 1..4) is the cost of presenting c's triangles as at most j
+   children of a wide node, a step being one wide-node visit or one triangle of a visited leaf,
+   weighted by the box's area.  The word beside it: bits 0-5 split[2..4] (2 bits each: how many of
+   the j children the left child takes, 0: c stays whole), bit 6 as_leaf, bits 8-9 a* (the left
+   child's share when c itself is the wide node), bits 12-14 min(size, 7). */
+constexpr uint32_t kWordLeaf = 1u << 6;
+
+__device__ __forceinline__ float ld_agent(const float *p)
+{
+    return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ void st_agent(float *p, float v)
+{
+    __hip_atomic_store(reinterpret_cast<uint32_t *>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/* the parent links of the PLOC tree (the radix tree's come from k_radix_tree); the root keeps -1 */
+__global__ void k_parents(const int2 *__restrict__ child, int n_inner, int *__restrict__ parent_inner,
+                          int *__restrict__ parent_leaf)
+{
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i >= n_inner) return;
+    const int2 c = child[i];
+    if (c.x >= 0) parent_inner[c.x] = i;
+    else parent_leaf[~c.x] = i;
+    if (c.y >= 0) parent_inner[c.y] = i;
+    else parent_leaf[~c.y] = i;
+}
+
+/* 5a. the bottom-up pass, by k_boxes' climb: one thread per leaf slot, the second arrival at a
+   node computes it from its finished children.  No thread waits.  A node's values depend on its
+   children's alone, so they are a function of the input.  range (radix tree) or nsize (PLOC)
+   gives a node's triangle count. */
+__global__ void k_collapse_cost(const float *__restrict__ tbox, const uint32_t *__restrict__ perm, int n,
+                                const int2 *__restrict__ child, const int2 *__restrict__ range,
+                                const uint32_t *__restrict__ nsize, const int *__restrict__ parent_inner,
+                                const int *__restrict__ parent_leaf, const float *__restrict__ nbox,
+                                int *__restrict__ flags, float *__restrict__ D, uint32_t *__restrict__ word)
+{
+    const int s = blockIdx.x * kB + threadIdx.x;
+    if (s >= n || n < 2) return;
+    int node = parent_leaf[s];
+    while (node >= 0 && node < n - 1) {
+        __threadfence();
+        if (atomicAdd(&flags[node], 1) == 0) return; /* the sibling finishes this node */
+        __threadfence();
+        const int2 c = child[node];
+        float dl[4], dr[4];
+        for (int q = 0; q < 2; ++q) {
+            const int ci = q ? c.y : c.x;
+            float *d = q ? dr : dl;
+            if (ci >= 0) { /* another workgroup may have written them: L1-bypassing loads */
+                for (int a = 0; a < 4; ++a) d[a] = ld_agent(D + 4ull * ci + a);
+            } else {
+                const float ar = box_area(tbox + 6ull * perm[~ci]);
+                for (int a = 0; a < 4; ++a) d[a] = ar;
+            }
+        }
+        const uint32_t size = nsize ? nsize[node] : (uint32_t)(range[node].y - range[node].x + 1);
+        const float area = box_area(nbox + 6ull * node);
+        const bool small = size <= kLeafMax;
+        const float leaf_c = small ? area * (float)size : INFINITY;
+        float best_int = dl[0] + dr[2];
+        uint32_t a_star = 1;
+        for (int a = 2; a <= 3; ++a) {
+            const float v = dl[a - 1] + dr[3 - a];
+            if (v < best_int) {
+                best_int = v;
+                a_star = (uint32_t)a;
+            }
+        }
+        const float inner_c = area + best_int;
+        const bool as_leaf = small && leaf_c <= inner_c;
+        float d[4];
+        d[0] = as_leaf ? leaf_c : inner_c;
+        uint32_t w = (as_leaf ? kWordLeaf : 0u) | (a_star << 8) | ((size < 7u ? size : 7u) << 12);
+        for (int j = 2; j <= 4; ++j) {
+            float best = d[0];
+            uint32_t sp = 0;
+            for (int a = 1; a < j; ++a) {
+                const float v = dl[a - 1] + dr[j - a - 1];
+                if (v < best) {
+                    best = v;
+                    sp = (uint32_t)a;
+                }
+            }
+            d[j - 1] = best;
+            w |= sp << (2 * (j - 2));
+        }
+        for (int a = 0; a < 4; ++a) st_agent(D + 4ull * node + a, d[a]);
+        word[node] = w;
+        node = parent_inner[node];
+    }
+}
+
+/* 5b. one level of the top-down pass, the shape of k_collapse: the wide node over binary node b
+   has the children expand(left, a*) ++ expand(right, 4 - a*), where expand(c, j) is [c] when
+   split[c][j] is 0 (or c is a binary leaf) and expand(left, s) ++ expand(right, j - s) otherwise.
+   A child is an inner child exactly when it is a binary inner node that is not as_leaf; any other
+   is a leaf of its <= kLeafMax slots, gathered left child first. */
+__global__ void k_collapse_sah(const Frontier *__restrict__ cur, const uint32_t *__restrict__ n_cur,
+                               Frontier *__restrict__ next, uint32_t *__restrict__ n_next, uint32_t *__restrict__ n_nodes,
+                               uint32_t *__restrict__ max_stack, const int2 *__restrict__ child,
+                               const uint32_t *__restrict__ word, const float *__restrict__ nbox,
+                               const float *__restrict__ tbox, const uint32_t *__restrict__ perm, int n,
+                               float *__restrict__ nodes4, uint32_t *__restrict__ n_tris_out, uint32_t *__restrict__ perm2)
+{
+    const uint32_t e = blockIdx.x * kB + threadIdx.x;
+    if (e >= *n_cur) return;
+    const Frontier f = cur[e];
+    int kids[4] = {0, 0, 0, 0};
+    int nk = 0;
+    if (f.bin < 0 || n < 2) {
+        kids[nk++] = f.bin; /* the single triangle */
+    } else {
+        /* the sum of the shares on the stack and the children made is 4, every share >= 1: at
+           most 4 entries, at most 6 nodes popped */
+        int sc[4], sj[4], sp = 0;
+        const int2 ch = child[f.bin];
+        int a = (int)((word[f.bin] >> 8) & 3u);
+        a = a < 1 ? 1 : a;
+        sc[sp] = ch.y, sj[sp++] = 4 - a;
+        sc[sp] = ch.x, sj[sp++] = a;
+        for (int it = 0; it < 6 && sp > 0; ++it) {
+            --sp;
+            const int c = sc[sp], j = sj[sp];
+            int s = (c < 0 || j < 2) ? 0 : (int)((word[c] >> (2 * (j - 2))) & 3u);
+            if (s >= j) s = 0; /* (cannot happen: k_collapse_cost takes a < j) */
+            if (s == 0) {
+                if (nk < 4) kids[nk++] = c;
+            } else if (sp + 2 <= 4) {
+                const int2 cc = child[c];
+                sc[sp] = cc.y, sj[sp++] = j - s;
+                sc[sp] = cc.x, sj[sp++] = s;
+            }
+        }
+    }
+    const int stk = f.stack + (nk > 0 ? nk - 1 : 0);
+    atomicMax(max_stack, (uint32_t)stk);
+    /* as k_collapse: consecutive node indices for the inner children, consecutive record slots for
+       the leaf children, one block each */
+    uint32_t cnt[4] = {0u, 0u, 0u, 0u}; /* 0: an inner child; else the leaf's triangles */
+    int n_in = 0;
+    uint32_t n_leaf_tris = 0;
+    for (int k = 0; k < nk; ++k) {
+        const int c = kids[k];
+        uint32_t m = 1;
+        if (c >= 0 && n >= 2) {
+            const uint32_t w = word[c];
+            m = (w & kWordLeaf) ? (w >> 12) & 7u : 0u;
+            if (m > kLeafMax) m = kLeafMax; /* (cannot happen: as_leaf implies size <= kLeafMax) */
+        }
+        cnt[k] = m;
+        if (m) n_leaf_tris += m;
+        else ++n_in;
+    }
+    const uint32_t node_base = n_in ? atomicAdd(n_nodes, (uint32_t)n_in) : 0u;
+    const uint32_t tri_base = n_leaf_tris ? atomicAdd(n_tris_out, n_leaf_tris) : 0u;
+    uint32_t next_node = node_base, next_tri = tri_base;
+    float *nd = nodes4 + 32ull * f.out;
+    for (int k = 0; k < 4; ++k) {
+        int32_t code = RT_EMPTY_CHILD;
+        float b[6] = {0, 0, 0, 0, 0, 0};
+        if (k < nk) {
+            const int c = kids[k];
+            const uint32_t count = cnt[k];
+            const float *src = (c >= 0 && n >= 2) ? nbox + 6ull * c : tbox + 6ull * perm[n >= 2 ? ~c : 0];
+            for (int a = 0; a < 6; ++a) b[a] = src[a];
+            if (count == 0) {
+                const uint32_t id = next_node++;
+                code = (int32_t)id;
+                const uint32_t q = atomicAdd(n_next, 1u);
+                next[q] = Frontier{c, (int)id, stk};
+            } else {
+                const uint32_t first = next_tri;
+                next_tri += count;
+                if (c >= 0 && n >= 2) {
+                    /* count <= kLeafMax: at most 2 kLeafMax - 1 nodes, the stack never holds more
+                       than kLeafMax of them */
+                    int stack[kLeafMax + 1], sp = 0;
+                    uint32_t q = 0;
+                    stack[sp++] = c;
+                    for (uint32_t it = 0; it < 2 * kLeafMax - 1 && sp > 0; ++it) {
+                        const int x = stack[--sp];
+                        if (x < 0) {
+                            if (q < count) perm2[first + q++] = (uint32_t)(~x);
+                        } else if (sp + 2 <= (int)kLeafMax + 1) {
+                            stack[sp++] = child[x].y;
+                            stack[sp++] = child[x].x;
+                        }
+                    }
+                } else {
+                    perm2[first] = n >= 2 ? (uint32_t)(~c) : 0u;
+                }
+                code = ~(int32_t)((first << 3) | (count - 1));
+            }
+        }
+        nd[0 + k] = b[0];
+        nd[4 + k] = b[3];
+        nd[8 + k] = b[1];
+        nd[12 + k] = b[4];
+        nd[16 + k] = b[2];
+        nd[20 + k] = b[5];
+        nd[24 + k] = __int_as_float(code);
+        nd[28 + k] = 0.0f;
+    }
+}
+
 /* 6a. compressed nodes (rt_quant.h, the host builder's encoder); flag = 1 if any
    node cannot be encoded (the traversal then uses the full-precision nodes) */
 __global__ void k_quantize(const float *__restrict__ nodes4, uint32_t n_nodes, uint32_t *__restrict__ q4,
@@ -791,6 +1005,7 @@ namespace {
    tbox / cent are per triangle of the mesh, written here for the list's. */
 struct BinTree {
     DevBuf bounds, keys, keys2, vals, perm, tmp, child, range, pin, pleaf, nbox, flags, nsize;
+    DevBuf cost, word, cflags; /* RT_COLLAPSE_SAH: k_collapse_cost's D, words and arrival flags */
     int m = 0, root = 0; /* root: the binary root (~0: the single triangle of m == 1) */
 };
 
@@ -869,10 +1084,35 @@ struct Collapsed {
     std::vector<uint32_t> level_end; /* node ids of level L: [level_end[L-1], level_end[L]) */
 };
 
-int collapse(BinTree *const *parts, int n_parts, const uint32_t *tri_base, bool ploc, const float *tbox, float *nodes4,
-             uint32_t *perm2, uint32_t *cnt, DevBuf (*d_front)[2], hipStream_t st, Collapsed &out, std::string &err)
+int collapse(BinTree *const *parts, int n_parts, const uint32_t *tri_base, bool ploc, bool sah, const float *tbox,
+             float *nodes4, uint32_t *perm2, uint32_t *cnt, DevBuf (*d_front)[2], hipStream_t st, BuildProfile &prof,
+             Collapsed &out, std::string &err)
 {
     const bool two = n_parts == 2;
+    /* RT_COLLAPSE_SAH: the bottom-up pass over every part, each on its own */
+    for (int p = 0; sah && p < n_parts; ++p) {
+        BinTree &T = *parts[p];
+        if (T.m < 2) continue;
+        const uint64_t n_inner = (uint64_t)T.m - 1;
+        GCHK(hipMalloc(&T.cost.p, 16ull * n_inner));
+        GCHK(hipMalloc(&T.word.p, 4ull * n_inner));
+        GCHK(hipMalloc(&T.cflags.p, 4ull * n_inner));
+        GCHK(hipMemsetAsync(T.cflags.p, 0, 4ull * n_inner, st));
+        if (ploc) { /* the PLOC tree has no parent links yet */
+            GCHK(hipMalloc(&T.pin.p, 4ull * n_inner));
+            GCHK(hipMalloc(&T.pleaf.p, 4ull * T.m));
+            GCHK(hipMemsetAsync(T.pin.p, 0xFF, 4ull * n_inner, st));
+            hipLaunchKernelGGL(k_parents, dim3(blocks_for(n_inner)), dim3(kB), 0, st, (const int2 *)T.child.p,
+                               (int)n_inner, (int *)T.pin.p, (int *)T.pleaf.p);
+            GCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_collapse_cost, dim3(blocks_for(T.m)), dim3(kB), 0, st, tbox, (const uint32_t *)T.perm.p, T.m,
+                           (const int2 *)T.child.p, (const int2 *)T.range.p, (const uint32_t *)T.nsize.p,
+                           (const int *)T.pin.p, (const int *)T.pleaf.p, (const float *)T.nbox.p, (int *)T.cflags.p,
+                           (float *)T.cost.p, (uint32_t *)T.word.p);
+        GCHK(hipGetLastError());
+    }
+    if (sah) prof.lap(st, "collapse_cost");
     uint32_t init_counts[16] = {0u};
     init_counts[2] = two ? 3u : 1u;
     init_counts[3] = two ? 1u : 0u; /* the root's other child waits on the stack */
@@ -898,6 +1138,12 @@ int collapse(BinTree *const *parts, int n_parts, const uint32_t *tri_base, bool 
             const BinTree &T = *parts[p];
             uint32_t *c = cnt + 8 * p;
             GCHK(hipMemsetAsync(c + (1 - cur), 0, sizeof(uint32_t), st));
+            if (sah)
+                hipLaunchKernelGGL(k_collapse_sah, dim3(blocks_for(level_size[p])), dim3(kB), 0, st,
+                                   (const Frontier *)d_front[p][cur].p, c + cur, (Frontier *)d_front[p][1 - cur].p,
+                                   c + (1 - cur), cnt + 2, cnt + 3, (const int2 *)T.child.p, (const uint32_t *)T.word.p,
+                                   (const float *)T.nbox.p, tbox, (const uint32_t *)T.perm.p, T.m, nodes4, c + 4, perm2);
+            else
             hipLaunchKernelGGL(ploc ? k_collapse<true> : k_collapse<false>, dim3(blocks_for(level_size[p])), dim3(kB), 0,
                                st, (const Frontier *)d_front[p][cur].p, c + cur, (Frontier *)d_front[p][1 - cur].p,
                                c + (1 - cur), cnt + 2, cnt + 3, (const int2 *)T.child.p, (const int2 *)T.range.p,
@@ -941,7 +1187,7 @@ int nbox_levels(const float *nodes4, uint32_t base, const std::vector<uint32_t> 
 } // namespace
 
 int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_h, uint32_t n_tris, RtGpuBvh &out,
-                     std::string &err, void *stream, bool det_cull, bool ploc, const RtGpuBuildLights *lights)
+                     std::string &err, void *stream, bool det_cull, bool ploc, const RtGpuBuildLights *lights, bool sah)
 {
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = (hipStream_t)stream;
@@ -1036,8 +1282,8 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
     {
         BinTree *parts[1] = {&all};
         const uint32_t base[1] = {0u};
-        if (int e = collapse(parts, 1, base, ploc, (const float *)d_tbox.p, nodes4, (uint32_t *)d_perm2.p, cnt, d_front,
-                             st, ca, err))
+        if (int e = collapse(parts, 1, base, ploc, sah, (const float *)d_tbox.p, nodes4, (uint32_t *)d_perm2.p, cnt,
+                             d_front, st, prof, ca, err))
             return e;
     }
     prof.lap(st, "collapse");
@@ -1068,8 +1314,8 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
         GCHK(hipGetLastError());
         BinTree *parts[2] = {&ta, &tb};
         const uint32_t base[2] = {0u, n0};
-        if (int e = collapse(parts, 2, base, ploc, (const float *)d_tbox.p, (float *)d_nodes4s.p, (uint32_t *)d_perm2s.p,
-                             cnt, d_front_s, st, cs, err))
+        if (int e = collapse(parts, 2, base, ploc, sah, (const float *)d_tbox.p, (float *)d_nodes4s.p,
+                             (uint32_t *)d_perm2s.p, cnt, d_front_s, st, prof, cs, err))
             return e;
         prof.lap(st, "collapse");
         if (cs.tri_end[0] != n0 || cs.tri_end[1] != n_hit) {
@@ -1140,7 +1386,7 @@ int rt_build_bvh_gpu(const float *verts_h, uint32_t n_verts, const int32_t *idx_
         out = RtGpuBvh();
         RtGpuBuildLights plain = *lights;
         plain.n_lights = 0;
-        const int e = rt_build_bvh_gpu(verts_h, n_verts, idx_h, n_tris, out, err, stream, det_cull, ploc, &plain);
+        const int e = rt_build_bvh_gpu(verts_h, n_verts, idx_h, n_tris, out, err, stream, det_cull, ploc, &plain, sah);
         out.build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return e;
     }

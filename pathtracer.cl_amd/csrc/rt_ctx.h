@@ -209,6 +209,8 @@ struct rt_ctx {
     int mesh_builder = RT_BUILD_HOST; /* builder of the current mesh */
     uint32_t build_opts = 0;          /* RT_BUILD_OPT_* for the next rt_set_mesh (the device builders) */
     uint32_t mesh_build_opts = 0;     /* ... of the current mesh: a rebuild in rt_update_mesh uses these */
+    int collapse = RT_COLLAPSE_GREEDY;      /* RT_COLLAPSE_* for the next rt_set_mesh (the device builders) */
+    int mesh_collapse = RT_COLLAPSE_GREEDY; /* ... of the current mesh (a host build: RT_COLLAPSE_SAH) */
     uint64_t mesh_serial = 0;
     /* the moving mesh (rt_update_mesh, rt_refit.hip): the indices of the last rt_set_mesh, on the
        host for a rebuild and on the device for the refit; how that mesh was built; the refit's

@@ -387,6 +387,21 @@ try {
     return RT_OK;
 } RT_CATCH(nullptr)
 
+int rt_set_collapse(rt_ctx *c, int mode)
+try {
+    if (!c) return RT_ERR_ARG;
+    if (mode != RT_COLLAPSE_GREEDY && mode != RT_COLLAPSE_SAH) return fail(c, RT_ERR_ARG, "rt_set_collapse: unknown mode");
+    c->collapse = mode;
+    return RT_OK;
+} RT_CATCH(err_of(c))
+
+int rt_get_collapse(const rt_ctx *c, int *mode)
+try {
+    if (!c || !mode) return RT_ERR_ARG;
+    *mode = c->collapse;
+    return RT_OK;
+} RT_CATCH(nullptr)
+
 int rt_set_traversal(rt_ctx *c, int t)
 try {
     if (!c || !(t == RT_TRAVERSAL_BVH || t == RT_TRAVERSAL_LINEAR || t == RT_TRAVERSAL_BVH4F)) return RT_ERR_ARG;

@@ -123,7 +123,8 @@ bool rt_build_bvh(const float *verts, uint32_t n_verts, const int32_t *idx, uint
 
 /* GPU build (rt_build_gpu.hip): a binary tree over the sorted 63-bit Morton codes — the
    radix tree (LBVH), or with `ploc` the tree of PLOC's merges by surface area — collapsed
-   to the 4-wide layouts; device buffers owned by the caller afterwards (hipFree).  No
+   to the 4-wide layouts (greedily, or with `sah_collapse` by the host collapse's dynamic
+   programming: RT_COLLAPSE_SAH); device buffers owned by the caller afterwards (hipFree).  No
    binary-tree layout is produced.  Returns a hipError_t as int (or -1), err set. */
 struct RtGpuBvh {
     float *nodes4 = nullptr;     /* 32 floats per node */
@@ -149,7 +150,7 @@ struct RtGpuBuildLights {
 };
 int rt_build_bvh_gpu(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, RtGpuBvh &out,
                      std::string &err, void *stream, bool det_cull = true, bool ploc = false,
-                     const RtGpuBuildLights *lights = nullptr);
+                     const RtGpuBuildLights *lights = nullptr, bool sah_collapse = false);
 /* Input checks shared by both builders (finite coordinates, indices in range, size limit). */
 bool rt_validate_mesh(const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris, std::string &err);
 

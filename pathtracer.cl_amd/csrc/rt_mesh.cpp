@@ -96,7 +96,7 @@ static void drop_mesh(rt_ctx *c)
    the lights' possible occluders (A) and the rest (B) apart (RT_LIGHT_CONE), in the host
    build's layout; without a split, one tree. */
 static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                              int kind, bool dynamic, uint32_t opts)
+                              int kind, bool dynamic, uint32_t opts, int collapse)
 {
     std::string err;
     if (!rt_validate_mesh(verts, n_verts, idx, n_tris, err)) return fail(c, RT_ERR_ARG, err);
@@ -121,7 +121,7 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
         bl.n_lights = (uint32_t)(lights.size() / 4);
     }
     const int e = rt_build_bvh_gpu(verts, n_verts, idx, n_tris, g, err, c->stream, det_cull, kind == RT_BUILD_GPU_PLOC,
-                                   bl.cull ? &bl : nullptr);
+                                   bl.cull ? &bl : nullptr, collapse == RT_COLLAPSE_SAH);
     const bool two = !e && g.n_nodes4_shadow > 0 && g.nodes4q;
     const uint32_t n_all = g.n_nodes4 + (two ? g.n_nodes4_shadow : 0u);
     c->d_nodes4.adopt(g.nodes4, 32ull * g.n_nodes4);
@@ -163,6 +163,7 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
     }
     c->mesh_builder = kind;
     c->mesh_build_opts = opts;
+    c->mesh_collapse = collapse;
     c->mesh_bounds_ok = mesh_bounds(verts, idx, n_tris, c->mesh_lo, c->mesh_hi);
     c->mesh_det_cull = det_cull;
     c->mesh_dynamic = dynamic;
@@ -170,15 +171,15 @@ static int set_mesh_build_gpu(rt_ctx *c, const float *verts, uint32_t n_verts, c
 }
 
 /* The build and the upload of rt_set_mesh (and of rt_update_mesh's rebuild): `builder`, `dynamic`
-   and `opts` (RT_BUILD_OPT_*: the device builders') are the context's choices for the next mesh,
-   or the current mesh's own. */
+   `opts` and `collapse` (RT_BUILD_OPT_*, RT_COLLAPSE_*: the device builders') are the context's
+   choices for the next mesh, or the current mesh's own. */
 static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                          int builder, bool dynamic, uint32_t opts)
+                          int builder, bool dynamic, uint32_t opts, int collapse)
 {
     std::string err;
     c->mesh_bounds_ok = false;
     if (builder == RT_BUILD_GPU || builder == RT_BUILD_GPU_PLOC)
-        return set_mesh_build_gpu(c, verts, n_verts, idx, n_tris, builder, dynamic, opts);
+        return set_mesh_build_gpu(c, verts, n_verts, idx, n_tris, builder, dynamic, opts, collapse);
     /* Two host trees over the same triangles: the closest-hit queries (camera rays, bounces, the
        seed passes) walk one split by surface area, the shadow queries one whose cost area leans
        toward the scene's lights (rt_bvh.cpp Builder::area) — three quarters of the dragon frame's
@@ -253,6 +254,7 @@ static int set_mesh_build(rt_ctx *c, const float *verts, uint32_t n_verts, const
     }
     c->mesh_builder = RT_BUILD_HOST;
     c->mesh_build_opts = 0; /* (the host build does all of it anyway) */
+    c->mesh_collapse = RT_COLLAPSE_SAH; /* (rt_bvh.cpp collapses by the same rule) */
     drop_mesh(c);
     HIPCHK(c, c->d_nodes4.reserve(b.nodes4.size()));
     if (!q4.empty()) HIPCHK(c, c->d_nodes4q.reserve(q4.size()));
@@ -350,11 +352,11 @@ static int refit_prepare(rt_ctx *c)
 /* rt_set_mesh, and rt_update_mesh's rebuild: the build, then what a later update needs of this
    mesh — its indices on the host and on the device. */
 static int set_mesh_keep(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *idx, uint32_t n_tris,
-                         int builder, bool dynamic, uint32_t opts)
+                         int builder, bool dynamic, uint32_t opts, int collapse)
 {
     c->refit = rt_ctx::Refit(); /* the refit's workspace: gone with the mesh it was sized for */
     c->have_update = false;
-    const int st = set_mesh_build(c, verts, n_verts, idx, n_tris, builder, dynamic, opts);
+    const int st = set_mesh_build(c, verts, n_verts, idx, n_tris, builder, dynamic, opts, collapse);
     if (st != RT_OK) return st;
     if (idx != c->h_idx.data()) c->h_idx.assign(idx, idx + 3ull * n_tris);
     c->n_verts = n_verts;
@@ -371,7 +373,7 @@ int rt_set_mesh(rt_ctx *c, const float *verts, uint32_t n_verts, const int32_t *
 try {
     if (!c || !verts || !idx || !n_verts || !n_tris) return fail(c, RT_ERR_ARG, "empty mesh");
     HIPCHK(c, hipSetDevice(c->device));
-    return set_mesh_keep(c, verts, n_verts, idx, n_tris, c->builder, c->dynamic, c->build_opts);
+    return set_mesh_keep(c, verts, n_verts, idx, n_tris, c->builder, c->dynamic, c->build_opts, c->collapse);
 } RT_CATCH(err_of(c))
 
 int rt_set_mesh_dynamic(rt_ctx *c, int on)
@@ -402,7 +404,7 @@ static int update_rebuild(rt_ctx *c, const float *verts, int flags, uint32_t rea
     const std::vector<int32_t> idx = std::move(c->h_idx);
     c->h_idx.clear();
     const int st = set_mesh_keep(c, verts, c->n_verts, idx.data(), c->n_tris, c->mesh_builder, c->mesh_dynamic,
-                                 c->mesh_build_opts);
+                                 c->mesh_build_opts, c->mesh_collapse);
     if (st != RT_OK) return st;
     c->last_update = {RT_MESH_UPDATE_REBUILT, reason, newly, 0u, 1.0f, 0.0f};
     c->have_update = true;
@@ -549,6 +551,7 @@ try {
     out->n_tris_tree = c->bvh.n_hit;
     out->cone_root = c->cone_root;
     out->n_tris_cone = c->n_cone;
+    out->collapse = (uint32_t)c->mesh_collapse;
     return RT_OK;
 } RT_CATCH(err_of(c))
 

@@ -12,6 +12,8 @@
  *              Every builder gives the same frames)
  *             [--build-lights]   (with --builder gpu|ploc: RT_BUILD_OPT_LIGHTS, the never-hit triangles left
  *              out and the shadow tree split by what can occlude the lights; the same frames again)
+ *             [--collapse greedy|sah]   (with --builder gpu|ploc: RT_COLLAPSE_*, how the binary tree becomes the
+ *              4-wide one, RayTracerHIP::setCollapse; default greedy; the same frames again)
  *             [--events d,d,l,d,m:5:-3,s:64:32,d,...]   (interactive replay: ProgressiveViewHIP
  *              display / arrow keys l r u n / drag motion / reshape, GlutCLWindow.cpp:136-301;
  *              one JSON line per event on stdout: the view state and whether a redisplay was
@@ -171,7 +173,7 @@ void add_scene(RayTracerHIP &rt, bool ply, rt_vec3 light_offset = {0.0f, 0.0f, 0
 int usage()
 {
     std::fprintf(stderr, "usage: rt_render [--scene main|ply] [--width W] [--height H] [--frames F] "
-                         "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--builder host|gpu|ploc] [--build-lights] [--raw f] [--pfm f] "
+                         "[--sample-rate S] [--depth D] [--mesh N | --ply FILE] [--linear] [--builder host|gpu|ploc] [--build-lights] [--collapse greedy|sah] [--raw f] [--pfm f] "
                          "[--device K] [--denoise [ITER]] [--temporal [MAXHIST]] [--variance-guided [SIGMA_LUM]] [--poses f] [--motion-carry [MAXHIST]] [--history-trust [TOL]] [--sphere-carry [MAXHIST]] (--events o:I:DX:DY:DZ[:DR] moves sphere I) [--denoised f] [--denoised-pfm f] [--features-out f] "
                          "[--raw-frames-out f] [--tonemap [clamp|reinhard|aces]] [--exposure auto|VALUE] [--adapt RATE] [--no-srgb] [--no-dither] "
                          "[--ppm f] [--frames8-out f] [--exposure-log f] [--converge [THRESHOLD]] [--converge-percentile Q] [--converge-min-frames N] "
@@ -266,6 +268,7 @@ int main(int argc, char **argv)
     bool linear = false;
     int builder = RT_BUILD_HOST;
     bool build_lights = false;
+    int collapse = RT_COLLAPSE_GREEDY;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -383,6 +386,11 @@ int main(int argc, char **argv)
         else if (a == "--depth") depth = (unsigned)std::atoi(v);
         else if (a == "--mesh") n_tris = (unsigned)std::atoi(v);
         else if (a == "--ply") ply_path = v;
+        else if (a == "--collapse") {
+            if (!std::strcmp(v, "greedy")) collapse = RT_COLLAPSE_GREEDY;
+            else if (!std::strcmp(v, "sah")) collapse = RT_COLLAPSE_SAH;
+            else return usage();
+        }
         else if (a == "--builder") {
             if (!std::strcmp(v, "host")) builder = RT_BUILD_HOST;
             else if (!std::strcmp(v, "gpu")) builder = RT_BUILD_GPU;
@@ -499,6 +507,7 @@ int main(int argc, char **argv)
         int kernel = RT_KERNEL_SPHERES;
         rt.setBuilder(builder);
         rt.setBuildOptions(build_lights ? RT_BUILD_OPT_LIGHTS : 0u);
+        rt.setCollapse(collapse);
         uint32_t n_verts = 0; /* of the mesh (--poses) */
         if (!ply_path.empty()) { /* plymain.cpp:121, with the mesh actually handed to the tracer */
             rt.setMeshFromPly(ply_path.c_str());

@@ -126,6 +126,18 @@ class RayTracer:
         self._check(self._lib.rt_get_build_options(self._h, ctypes.byref(o)), "rt_get_build_options")
         return int(o.value)
 
+    def setCollapse(self, mode: str) -> None:
+        """How the device builders ("gpu", "ploc") collapse their binary tree to the 4-wide one, for the
+        next setMesh: "greedy" (default) or "sah" (the host build's rule, by dynamic programming over the
+        binary tree). The host builder ignores it; results never depend on it."""
+        m = {"greedy": _abi.RT_COLLAPSE_GREEDY, "sah": _abi.RT_COLLAPSE_SAH}[mode]
+        self._check(self._lib.rt_set_collapse(self._h, m), "rt_set_collapse")
+
+    def getCollapse(self) -> str:
+        m = ctypes.c_int32(0)
+        self._check(self._lib.rt_get_collapse(self._h, ctypes.byref(m)), "rt_get_collapse")
+        return {_abi.RT_COLLAPSE_GREEDY: "greedy", _abi.RT_COLLAPSE_SAH: "sah"}[int(m.value)]
+
     def setNDRange(self, nd_y: int) -> None:
         """Work-group height of the reference launch (fixes the padded seed height)."""
         self._check(self._lib.rt_set_ndrange(self._h, int(nd_y)), "rt_set_ndrange")
